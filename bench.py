@@ -12,8 +12,14 @@ independent 640x480 pairs with 2000 patches each, inputs already resident in HBM
   BASELINE config C3's variant instead: every frame's patches are split over the ranks and the
   per-frame 6x6 H / 6x1 b sums are all-reduced (RCCL over xGMI) at every Gauss-Newton step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant kernel and
-`cpu_baseline` (host cores).  What the roofline object says and where every number in it comes from:
+A plain run sets up, warms up, times exactly K steps and prints the headline.  --full adds, outside the timed region,
+every distinct scene against the CPU oracle (`pose_err_vs_cpu_ref`), `cpu_baseline` (host cores), C0, the other
+arithmetic levels and configurations and the secondary sections (profiles/BENCH_KEYS.md).  --dump-outputs DIR writes
+what the last timed step computed, every frame pair's svo_hip_sia_result, as DIR/<field>.npy (float64); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+Prints ONE JSON line on rank 0 (keys: profiles/BENCH_KEYS.md) with `roofline` for the dominant kernel.  What the
+roofline object says and where every number in it comes from:
   * the dominant kernel (sia_fused_kernel) is bound by VALU issue, not by HBM: `bound` = "valu", `achieved` = issue
     cycles it needs per second (per-type VALU instruction counts from rocprofv3 PMC passes of this very command, stored
     in profiles/r*_pmc_fused.json: 2 cycles per wave64 f32/int instruction, 4 per f64, 8 per transcendental), `peak` =
@@ -77,17 +83,22 @@ def parse_args():
                          "(SVO_HIP_SIA_ARITH_EXACT: the reference's arithmetic statement by statement, f64 Jres moments -- the headline); "
                          "moments_f32 / fast = the two opt-in levels, for their PMC passes (tools/pmc_fused.sh <tag> --arith moments_f32), "
                          "reported as secondary sections")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline, outside the timed region: every scene against the CPU oracle, the CPU baseline, "
+                         "the other arithmetic levels, configurations and sizes (the secondary sections below); without it a run sets up, "
+                         "warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (every frame pair's result of rank 0) as DIR/<field>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and C0 legs")
     ap.add_argument("--verbose-json", action="store_true", help="keep the explanatory strings in the JSON line (default: numbers and sources only; "
                                                                 "what every key means is in profiles/BENCH_KEYS.md)")
     ap.add_argument("--cpu-frames-per-thread", type=int, default=16)
     ap.add_argument("--latency-probe", action="store_true",
-                    help="(kept for old command lines: the single-pair latency is measured by default, outside the timed region, unless --no-secondary)")
+                    help="(kept for old command lines: the single-pair latency is measured with --full, outside the timed region, unless --no-secondary)")
     ap.add_argument("--profile-events", type=int, default=1, help="record HIP events around the heavy kernels in the timed region")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the extra measurements outside the timed region (single-pair latency, single-stream tracking chain, reference early-stop "
-                         "semantics, streaming Jacobian pass, image uploads overlapped with the solve, the compact C2 / C4 blocks): use it when the run "
-                         "is profiled, the kernel average in the rocprofv3 summary must be that of the timed launches")
+                    help="--full without the extra measurements outside the timed region (single-pair latency, single-stream tracking chain, reference "
+                         "early-stop semantics, streaming Jacobian pass, image uploads overlapped with the solve, the compact C2 / C4 blocks)")
     ap.add_argument("--allow-stale-profile", action="store_true",
                     help="use a PMC profile under profiles/ although the kernel sources have changed since it was taken (A/B work only)")
     return ap.parse_args()
@@ -348,6 +359,15 @@ def slim(o, verbose=False):
     return o
 
 
+def dump_outputs(path, results):
+    """--dump-outputs: what a caller of svo_hip_sia_run receives (svo_hip_sia_result, every field) for every frame pair of the
+    last timed step, one row per pair, as <path>/<field>.npy in float64 (1.8 MB at the default 4096 pairs)"""
+    os.makedirs(path, exist_ok=True)
+    for name, ctype in hip.CSiaResult._fields_:
+        rows = [getattr(r, name)[:] if hasattr(ctype, "_length_") else getattr(r, name) for r in results]
+        np.save(os.path.join(path, name + ".npy"), np.array(rows, dtype=np.float64))
+
+
 def prewarm(ctx, fn, seconds=PREWARM_S):
     """Part of the set-up, never of a timed region: call fn (a launch of the workload about to be measured) for `seconds` so
     that the chip is at its running clocks.  Every measurement here follows seconds of host work (scene generation, uploads,
@@ -558,10 +578,15 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # what the last timed step left in the solver's results, before anything else runs
+    results = sia.download_all(n_slots)
+    res = results[0]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, results)
 
     # ---- single-pair latency with the reference's early-stop semantics (informative, outside the timed region)
     latency_ms = None
-    if rank == 0 and not allreduce and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and not allreduce and world == 1 and not args.no_secondary:
         sia1 = hip.SparseImgAlign(ctx, 1, n_feat)
         sia1.set_frames(ref, cur)
         sia1.upload_pair(0, fps[0])
@@ -578,16 +603,13 @@ def main():
 
     # ---- one camera, one frame at a time: the whole per-frame chain through svo_hip_tracker_track (outside the timed region)
     chain = None
-    if rank == 0 and not allreduce and world == 1 and not args.no_secondary and not args.early_stop and args.width == 640:
+    if args.full and rank == 0 and not allreduce and world == 1 and not args.no_secondary and not args.early_stop and args.width == 640:
         for d_ in ("tools", "tests"):
             if os.path.join(ROOT, d_) not in sys.path:
                 sys.path.insert(0, os.path.join(ROOT, d_))
         import chain_bench
         chain = chain_bench.single_stream_chain(ctx)
 
-    # ---- parity check (outside the timed region): EVERY distinct scene against the CPU oracle, every replica bitwise
-    res = sia.download(0)
-    results = sia.download_all(n_slots)
     frames_global = B * world
     value = frames_global * args.steps / dt
 
@@ -595,27 +617,32 @@ def main():
     if rank == 0:
         from oracle import orc          # checker + cpu_baseline leg only
         n_scenes = min(len(fps), n_slots)
-        oracle_res = [None] * n_scenes
+        o = None
+        if args.full:
+            # ---- parity check (outside the timed region): EVERY distinct scene against the CPU oracle, every replica bitwise
+            oracle_res = [None] * n_scenes
 
-        def oracle_worker(t, nt):
-            for i in range(t, n_scenes, nt):
-                oracle_res[i] = orc.sparse_img_align(fps[i], n_iter=30, early_stop=args.early_stop)
-        nt = max(1, min(host_cpus()[1], n_scenes))
-        ths = [threading.Thread(target=oracle_worker, args=(t, nt)) for t in range(nt)]
-        [t.start() for t in ths]
-        [t.join() for t in ths]
-        o = oracle_res[0]
-        rot, trans = synth.pose_error(np.array(res.T_cur_w), np.array(o.T_cur_w))
-        scene_err = np.array([synth.pose_error(np.array(results[i].T_cur_w), np.array(oracle_res[i].T_cur_w)) for i in range(n_scenes)])
-        tracked_equal = all(int(results[i].n_tracked) == int(oracle_res[i].n_tracked) for i in range(n_scenes))
-        # all replicated slots of one scene must agree bit for bit (deterministic reductions)
-        replicas_checked = 0
-        for i in range(n_scenes, n_slots):
-            assert list(results[i].T_cur_w) == list(results[i % n_scenes].T_cur_w), "slot %d differs from its scene's first slot" % i
-            replicas_checked += 1
+            def oracle_worker(t, nt):
+                for i in range(t, n_scenes, nt):
+                    oracle_res[i] = orc.sparse_img_align(fps[i], n_iter=30, early_stop=args.early_stop)
+            nt = max(1, min(host_cpus()[1], n_scenes))
+            ths = [threading.Thread(target=oracle_worker, args=(t, nt)) for t in range(nt)]
+            [t.start() for t in ths]
+            [t.join() for t in ths]
+            o = oracle_res[0]
+            rot, trans = synth.pose_error(np.array(res.T_cur_w), np.array(o.T_cur_w))
+            scene_err = np.array([synth.pose_error(np.array(results[i].T_cur_w), np.array(oracle_res[i].T_cur_w)) for i in range(n_scenes)])
+            tracked_equal = all(int(results[i].n_tracked) == int(oracle_res[i].n_tracked) for i in range(n_scenes))
+            # all replicated slots of one scene must agree bit for bit (deterministic reductions)
+            replicas_checked = 0
+            for i in range(n_scenes, n_slots):
+                assert list(results[i].T_cur_w) == list(results[i % n_scenes].T_cur_w), "slot %d differs from its scene's first slot" % i
+                replicas_checked += 1
         n_res_per_frame = res.n_residual_patches       # patches accumulated over all evaluations of one frame
         n_pre_per_frame = res.n_precompute_patches
         if allreduce:
+            if o is None:       # the whole frame's patch counts, from one oracle run of scene 0
+                o = orc.sparse_img_align(fps[0], n_iter=30, early_stop=args.early_stop)
             # counters are per rank shard; scale to the whole frame for the algorithmic-bytes figure
             n_res_per_frame = o.n_residual_patches
             n_pre_per_frame = o.n_precompute_patches
@@ -714,7 +741,7 @@ def main():
         m32_sec = None
         jac = None
         upl = None
-        if not allreduce and world == 1 and not args.no_secondary and not args.early_stop:
+        if args.full and not allreduce and world == 1 and not args.no_secondary and not args.early_stop:
             # (1) the same batch with the REFERENCE's Gauss-Newton exits (error increase, |x| <= eps)
             prm_es = sia.params(max_level=4, min_level=0, n_iter=30, eps=1e-6, early_stop=True)
             prewarm(ctx, lambda: sia.run(n_slots, prm_es))
@@ -810,7 +837,7 @@ def main():
         # SURVEY 8(d)'s algorithmic bytes over the HBM peak: at these sizes the kernels are launch- / latency-bound.
         c2 = None
         c4 = None
-        if not allreduce and world == 1 and not args.no_secondary and not args.early_stop:
+        if args.full and not allreduce and world == 1 and not args.no_secondary and not args.early_stop:
             import bench_c2
             c2 = {"what": "BASELINE config C2 on this GPU, inputs resident in HBM; per-call time = best of 3 rounds of back-to-back calls after 30 ms of warm-up (python bench_c2.py gives the long form)"}
             c2["align2d"], _ = bench_c2.measure_align2d(ctx, 5000, steps=20, warmup=3)
@@ -841,10 +868,10 @@ def main():
             sb4.free()
             [p_.destroy() for p_ in pyr4]
         c0 = None
-        if not args.no_cpu_baseline and world == 1 and not allreduce and not args.no_secondary and not args.early_stop and args.width == 640:
+        if args.full and not args.no_cpu_baseline and world == 1 and not allreduce and not args.no_secondary and not args.early_stop and args.width == 640:
             c0 = c0_leg(ctx)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:      # reported at N=1 only (rank 0)
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported at N=1 only (rank 0)
             cpu = cpu_baseline(fps[:16], n_iter=30, early_stop=args.early_stop, frames_per_thread=args.cpu_frames_per_thread)
             if early is not None:
                 # the reference's OWN compiled SparseImgAlign (oracle/_ref, kind "reference") on the early-stop workload
@@ -867,30 +894,33 @@ def main():
                        "distinct_scenes": args.distinct, "arithmetic": {"default": "EXACT (library default, the reference's)", "moments_f32": "MOMENTS_F32 (opt-in)", "fast": "FAST (opt-in)"}[args.arith],
                        **({"comm_ranks": comm_ranks} if comm_ranks is not None else {}),
                        "implementation": "fused" if (not allreduce and mode == 1) else "streaming"},     # one workgroup per pair, one launch per solve / one launch per GN evaluation
-            "pose_err_vs_cpu_ref": {"rot_rad": rot, "trans_m": trans, "tolerance": "1e-4 rad / 1e-3 m",
-                                    "scenes_checked": int(n_scenes), "max_rot_rad_over_scenes": float(scene_err[:, 0].max()),
-                                    "max_trans_m_over_scenes": float(scene_err[:, 1].max()), "n_tracked_equal_in_every_scene": bool(tracked_equal),
-                                    "replica_slots_bitwise_equal": int(replicas_checked)},
             "pose_err_vs_ground_truth": dict(zip(("rot_rad", "trans_m"), synth.pose_error(np.array(res.T_cur_w), fps[0].T_cur_w_true))),
             "gn_evaluations_per_frame": int(evals),
-            "single_pair_latency_ms_early_stop": latency_ms,
-            "single_stream_chain_ms": chain["L4_L2_shipping_default"]["ms_per_frame"] if chain else None,
-            "single_stream_chain": chain,
             "algorithmic_bytes_per_frame": int(bytes_frame),
             "whole_solve_algorithmic_GBps": bytes_frame * value / 1e9,
             "roofline": roofline,
-            "cpu_baseline": cpu,
-            "roofline_jacobian_pass": jac,
-            "reference_semantics": early,
-            "moments_f32_arithmetic": m32_sec,
-            "fast_arithmetic": fast,
-            "with_image_uploads": upl,
-            "c0": c0,
-            "c2": c2,
-            "c4_one_gpu": c4,
         }
-        assert scene_err[:, 0].max() < 1e-4 and scene_err[:, 1].max() < 1e-3, "pose parity violated: %s (rotation error per scene: %s)" % (scene_err.max(axis=0), np.array2string(scene_err[:, 0], precision=2))
-        assert tracked_equal or args.early_stop, "n_tracked differs from the oracle's in some scene"
+        if args.full:
+            out.update({
+                "pose_err_vs_cpu_ref": {"rot_rad": rot, "trans_m": trans, "tolerance": "1e-4 rad / 1e-3 m",
+                                        "scenes_checked": int(n_scenes), "max_rot_rad_over_scenes": float(scene_err[:, 0].max()),
+                                        "max_trans_m_over_scenes": float(scene_err[:, 1].max()), "n_tracked_equal_in_every_scene": bool(tracked_equal),
+                                        "replica_slots_bitwise_equal": int(replicas_checked)},
+                "single_pair_latency_ms_early_stop": latency_ms,
+                "single_stream_chain_ms": chain["L4_L2_shipping_default"]["ms_per_frame"] if chain else None,
+                "single_stream_chain": chain,
+                "cpu_baseline": cpu,
+                "roofline_jacobian_pass": jac,
+                "reference_semantics": early,
+                "moments_f32_arithmetic": m32_sec,
+                "fast_arithmetic": fast,
+                "with_image_uploads": upl,
+                "c0": c0,
+                "c2": c2,
+                "c4_one_gpu": c4,
+            })
+            assert scene_err[:, 0].max() < 1e-4 and scene_err[:, 1].max() < 1e-3, "pose parity violated: %s (rotation error per scene: %s)" % (scene_err.max(axis=0), np.array2string(scene_err[:, 0], precision=2))
+            assert tracked_equal or args.early_stop, "n_tracked differs from the oracle's in some scene"
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(slim(out, args.verbose_json), separators=(",", ":")) + "\n").encode())
     if multi:

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -16,8 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _torchrun(n, port, *args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--no-secondary",
-           "--no-cpu-baseline", "--distinct", "4"] + list(args)
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--full",
+           "--no-secondary", "--no-cpu-baseline", "--distinct", "4"] + list(args)
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
@@ -50,7 +51,7 @@ def _plain(script, *args):
 
 
 def test_bench_gpus_2_started_plainly_starts_its_own_ranks():
-    d = _plain("bench.py", "--gpus", "2", "--batch", "8", "--steps", "2", "--warmup", "1", "--no-secondary", "--no-cpu-baseline",
+    d = _plain("bench.py", "--gpus", "2", "--batch", "8", "--steps", "2", "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline",
                "--distinct", "4")
     assert d["n_gpus"] == 2 and "rehearsal" in d and d["config"]["global_frame_pairs_per_step"] == 16
     assert d["pose_err_vs_cpu_ref"]["max_rot_rad_over_scenes"] < 1e-4
@@ -69,14 +70,14 @@ def test_bench_c4_gpus_2_started_plainly():
 
 
 def test_default_bench_line_fits_the_drivers_tail_and_carries_the_contract():
-    """`python bench.py` as the driver runs it (N = 1, every secondary section on): ONE JSON line of at most 6 KiB (round 3's 14 kB
+    """`python bench.py --full` (N = 1, every secondary section on): ONE JSON line of at most 6 KiB (round 3's 14 kB
     line lost its first half in the driver's tail), with the contract keys, `roofline` and `cpu_baseline` objects, the per-stage
     bounds of the depth filter and the drop-in entry's timing.  (One of the two places where a process on the GPU box maps reference object code: bench.py's `cpu_baseline` / `c0` legs
     time the reference's own compiled SparseImgAlign where the prebuilt oracle/_ref/libsvo_ref.so is present; the other is
     tests/test_gpu_dropin_binding.py, which RUNS the drop-in bindings against the reference's own types.)"""
     d_line = None
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"], cwd=ROOT, env=env, capture_output=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=400)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
@@ -113,3 +114,43 @@ def test_default_bench_line_fits_the_drivers_tail_and_carries_the_contract():
     assert ch["group_frames_per_s"]["8"] > 2.0 * ch["group_frames_per_s"]["1"] and ch["cameras_frames_per_s"]["1"] > 0
     for stage in ("search", "align"):
         assert 0.0 < df["roofline"][stage]["lane_util"] <= 1.0
+
+
+def test_plain_bench_line_is_the_headline_and_dumps_the_timed_outputs(tmp_path):
+    """`python bench.py` without --full: exactly --steps timed steps, the headline keys and none of --full's sections.
+    --dump-outputs writes every frame pair's result of the last timed step, float64, the same bits in a second run (seeded
+    inputs), and those results are the oracle's poses."""
+    from android_svo_amd import synth
+    from oracle import orc
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                            "--distinct", "4", "--features", "600", "--dump-outputs", str(out_dir)], cwd=ROOT, env=env,
+                           capture_output=True, text=True, timeout=280)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+        assert abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]           # value and ms_per_step: the same timed steps
+        for k in ("pose_err_vs_cpu_ref", "cpu_baseline", "c0", "c2", "c4_one_gpu", "single_stream_chain", "reference_semantics",
+                  "moments_f32_arithmetic", "fast_arithmetic", "with_image_uploads", "roofline_jacobian_pass"):
+            assert k not in d, k
+        files = sorted(f.name for f in out_dir.iterdir())
+        assert files == sorted(n + ".npy" for n in ("T_cur_w", "n_tracked", "H", "chi2", "stop", "iters", "n_precompute_patches",
+                                                    "n_residual_patches")), files
+        arrs = {f[:-4]: np.load(out_dir / f) for f in files}
+        assert all(a.dtype == np.float64 and len(a) == 8 for a in arrs.values())
+        assert arrs["T_cur_w"].shape == (8, 7) and arrs["H"].shape == (8, 36) and sum(a.nbytes for a in arrs.values()) < 64 << 20
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True), k
+    for i in range(4):                     # slot i and slot i + 4 hold scene i (bench.py's seeds), solved as the oracle solves it
+        o = orc.sparse_img_align(synth.make_frame_pair(seed=12345 + i, n_features=600), n_iter=30, early_stop=False)
+        for s in (i, i + 4):
+            rot, trans = synth.pose_error(dumps[0]["T_cur_w"][s], np.array(o.T_cur_w))
+            assert rot < 1e-4 and trans < 1e-3 and dumps[0]["n_tracked"][s] == o.n_tracked

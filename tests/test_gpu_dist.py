@@ -29,7 +29,7 @@ def test_allreduce_solve_native_and_torch_driver():
     (a) through the C-ABI (svo_hip_sia_run_sharded: libsvo_hip.so calls RCCL itself) and (b) driven from Python through
     torch.distributed -- the same kernels and the same sums, so the same bits."""
     common = ["bench.py", "--gpus", "1", "--batch", "4", "--features", "600", "--steps", "2", "--warmup", "1", "--distinct", "4",
-              "--no-cpu-baseline", "--profile-events", "0"]
+              "--full", "--no-cpu-baseline", "--profile-events", "0"]
     native = _torchrun(common + ["--mode", "allreduce"], 29541)
     torch_driver = _torchrun(common + ["--mode", "allreduce-torch"], 29542)
     for d in (native, torch_driver):

@@ -27,7 +27,7 @@ for ctr in FETCH_SIZE WRITE_SIZE; do
   python3 "$root/tools/pmc_summary.py" "$csv" sia_ >> "$out/${tag}_pmc.txt"
 done
 echo "pmc -> $out/${tag}_pmc.txt"
-# 3. the plain bench line (no profiler attached)
+# 3. the whole bench line, every section (no profiler attached)
 cd "$root"
-python3 bench.py "$@" > "$out/${tag}_bench.json" 2>> "$out/${tag}_rocprof.log"
+python3 bench.py --full "$@" > "$out/${tag}_bench.json" 2>> "$out/${tag}_rocprof.log"
 cat "$out/${tag}_bench.json"
