@@ -390,13 +390,11 @@ template <bool EXPLICIT_DEPTH>
 __global__ __launch_bounds__(256) void df_geometry_kernel(
     DfFrame fr, int n, const double* __restrict__ px, const double* __restrict__ f, const int32_t* __restrict__ level,
     const float* __restrict__ smu, const float* __restrict__ ssigma2, const double* __restrict__ dep,
-    double* __restrict__ epi_len_out, SeedRec* __restrict__ recs, const uint8_t* __restrict__ alive = nullptr,
-    int* __restrict__ ev_hist = nullptr) {
+    double* __restrict__ epi_len_out, SeedRec* __restrict__ recs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ev_hist && i < 8) ev_hist[i] = 0;                   // status histogram of the pass (filled by the finalize stage)
   if (i >= n) return;
   df_geometry_seed<EXPLICIT_DEPTH>(fr.cam, fr.T_cur_ref_vis, fr.T_cur_ref, fr.n_pyr_levels, fr.max_epi_search_steps, 0, i, n, px, f,
-                                   level, smu, ssigma2, dep, epi_len_out, recs + i, alive);
+                                   level, smu, ssigma2, dep, epi_len_out, recs + i, nullptr);
 }
 
 // ---- image windows in LDS -------------------------------------------------------------------------------------
@@ -769,9 +767,7 @@ SVO_DEV void df_search_block(const DfFrame& fr, const uint8_t* __restrict__ ref_
 
 __global__ __launch_bounds__(256, 7) void df_search_kernel(
     DfFrame fr, const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes, const uint8_t* __restrict__ cur_pyr, int n,
-    const int32_t* __restrict__ level, SeedRec* __restrict__ recs, uint32_t* __restrict__ pwb_t, int n_pad,
-    const int* __restrict__ n_dev = nullptr) {
-  if (n_dev) { const int nd = *n_dev; n = nd < n ? nd : n; }       // item count left by an earlier kernel of the stream (svo_track.hip)
+    const int32_t* __restrict__ level, SeedRec* __restrict__ recs, uint32_t* __restrict__ pwb_t, int n_pad) {
   df_search_block(fr, ref_base, ref_pyr_bytes, cur_pyr, n, level, recs, pwb_t, n_pad, blockIdx.x);
 }
 
@@ -841,15 +837,13 @@ SVO_DEV void df_align_quad(const DfFrame& fr, const uint8_t* __restrict__ cur_py
 
 template <bool ONE_D>
 __global__ __launch_bounds__(ALIGN_BLOCK) void df_align_kernel(DfFrame fr, const uint8_t* __restrict__ cur_pyr, int n, int n_pad,
-                                                               const uint32_t* __restrict__ pwb_t, SeedRec* __restrict__ recs,
-                                                               const int* __restrict__ n_dev = nullptr) {
-  if (n_dev) { const int nd = *n_dev; n = nd < n ? nd : n; }
+                                                               const uint32_t* __restrict__ pwb_t, SeedRec* __restrict__ recs) {
   const int i = blockIdx.x * ALIGN_PATCHES + (threadIdx.x >> 2);
   df_align_quad<ONE_D>(fr, cur_pyr, n_pad, pwb_t, recs, i, i < n);
 }
 
-// ---- the warp / search and alignment stages over the candidates of SEVERAL cameras (svo_hip_tracker_group): camera c's
-// records are [c * cap, c * cap + n_c) of one record array (cap a multiple of the 16 items a block takes, so a block never
+// ---- the warp / search and alignment stages over the candidates of the cameras of a tracker (svo_track.hip; a lone tracker
+// is a group of one): camera c's records are [c * cap, c * cap + n_c) of one record array (cap a multiple of the 16 items a block takes, so a block never
 // straddles two cameras), n_c = counters[c * counter_stride] as the camera's planning kernel left it, its current image is
 // slot c of the frame pyramid batch; the reference keyframe of an item is the slot in its record, as always.
 __global__ __launch_bounds__(256, 7) void df_search_cams_kernel(
@@ -873,12 +867,7 @@ __global__ __launch_bounds__(ALIGN_BLOCK) void df_align_cams_kernel(DfFrame fr, 
   df_align_quad<ONE_D>(fr, cur_base + (size_t)c * cur_pyr_bytes, n_pad, pwb_t, recs, i, i < c * cap + n_c);
 }
 
-// EVENTS (device-resident seed batches, svo_hip_seed_batch_*): the kernel also counts, per block, the seeds whose outcome
-// the HOST has to hear about -- converged and NaN seeds (callback / erase, depth_filter.cpp:310-337) and, on keyframes
-// (report_updated), every updated seed (its px_cur marks the detector grid, :302-306) -- clears their `alive` flag where
-// the reference erases them, and adds the block's status histogram to ev_hist[8] (slot status + 1; slot 0 = erased).
-//
-// (the per-seed body: seed i of the arrays, its record `rc`; returns the seed's status)
+// (the per-seed body of the finalize stage: seed i of the arrays, its record `rc`; returns the seed's status)
 SVO_DEV int df_finalize_seed(const Cam& cam, const double* T_cur_ref, const double* T_ref_cur, const double* T_ref_inv,
                              double px_error_angle, double conv_thresh, int i, const SeedRec& rc, const double* __restrict__ f,
                              float* __restrict__ sa, float* __restrict__ sb, float* __restrict__ smu,
@@ -942,8 +931,11 @@ SVO_DEV int df_finalize_seed(const Cam& cam, const double* T_cur_ref, const doub
   return st;
 }
 
-// (the block's part of the EVENTS bookkeeping: every thread of the 256-thread block calls it; `block` = the block's index
-// within the batch)
+// Events of a device-resident seed batch (svo_hip_seed_batch_*): the finalize stage also counts, per block, the seeds whose
+// outcome the HOST has to hear about -- converged and NaN seeds (callback / erase, depth_filter.cpp:310-337) and, on keyframes
+// (report_updated), every updated seed (its px_cur marks the detector grid, :302-306) -- clears their `alive` flag where the
+// reference erases them, and adds the block's status histogram to ev_hist[8] (slot status + 1; slot 0 = erased).
+// (every thread of the 256-thread block calls it; `block` = the block's index within the batch)
 SVO_DEV void df_finalize_events(int st, int i, int n, int block, uint8_t* __restrict__ alive, int report_updated,
                                 int* __restrict__ ev_block_count, int* __restrict__ ev_hist) {
   const bool gone = st == SVO_HIP_SEED_CONVERGED || st == SVO_HIP_SEED_NAN;      // the reference erases these (:330, :336)
@@ -961,22 +953,17 @@ SVO_DEV void df_finalize_events(int st, int i, int n, int block, uint8_t* __rest
   if (threadIdx.x < 8 && s_hist[threadIdx.x]) atomicAdd(&ev_hist[threadIdx.x], s_hist[threadIdx.x]);
 }
 
-template <bool EVENTS>
 __global__ __launch_bounds__(256) void df_finalize_kernel(
     DfFrame fr, int n, const double* __restrict__ f, const SeedRec* __restrict__ recs, float* __restrict__ sa,
     float* __restrict__ sb, float* __restrict__ smu, const float* __restrict__ sz_range, float* __restrict__ ssigma2,
     int32_t* __restrict__ status, double* __restrict__ z_out, double* __restrict__ xyz_world,
     int32_t* __restrict__ n_zmssd_out, int32_t* __restrict__ n_align_out, double* __restrict__ px_cur_out,
-    int32_t* __restrict__ search_level_out, uint8_t* __restrict__ alive = nullptr, int report_updated = 0,
-    int* __restrict__ ev_block_count = nullptr, int* __restrict__ ev_hist = nullptr) {
+    int32_t* __restrict__ search_level_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  int st = SVO_HIP_SEED_ERASED;
-  if (i < n) {
-    const SeedRec rc = recs[i];                            // (a copy: the whole record is asked for at once)
-    st = df_finalize_seed(fr.cam, fr.T_cur_ref, fr.T_ref_cur, fr.T_ref_inv, fr.px_error_angle, fr.conv_thresh, i, rc, f, sa, sb,
-                          smu, sz_range, ssigma2, status, z_out, xyz_world, n_zmssd_out, n_align_out, px_cur_out, search_level_out);
-  }
-  if (EVENTS) df_finalize_events(st, i, n, blockIdx.x, alive, report_updated, ev_block_count, ev_hist);
+  if (i >= n) return;
+  const SeedRec rc = recs[i];                              // (a copy: the whole record is asked for at once)
+  (void)df_finalize_seed(fr.cam, fr.T_cur_ref, fr.T_ref_cur, fr.T_ref_inv, fr.px_error_angle, fr.conv_thresh, i, rc, f, sa, sb,
+                         smu, sz_range, ssigma2, status, z_out, xyz_world, n_zmssd_out, n_align_out, px_cur_out, search_level_out);
 }
 
 // Matcher::findEpipolarMatchDirect called directly (explicit depth interval): the tail of the function,
@@ -1012,21 +999,14 @@ __global__ __launch_bounds__(256) void epi_finalize_kernel(
 // ---- Matcher::findMatchDirect over n (map point, reference feature) pairs (S/matcher.cpp:156-202) ----
 // (MdFrame, md_geometry_item: svo_match_device.h)
 // thread per item: frame test, depth, affine warp, search level -> SeedRec (path 0 = align2D, 3 = align1D)
-__global__ __launch_bounds__(256) void md_geometry_kernel(
+// (five waves per SIMD, what the kernel reaches with 96 VGPRs: left to itself the scheduler takes 98 and four)
+__global__ __launch_bounds__(256, 5) void md_geometry_kernel(
     MdFrame fr, int n, const double* __restrict__ T_ref_w /*[n_kf][7]*/, const int32_t* __restrict__ kf_slot,
     const double* __restrict__ px_ref, const double* __restrict__ f_ref, const int32_t* __restrict__ level,
     const double* __restrict__ pt_pos, const uint8_t* __restrict__ edgelet, const double* __restrict__ grad,
-    const double* __restrict__ px_cur, SeedRec* __restrict__ recs, const double* __restrict__ T_cur_w_dev,
-    const int* __restrict__ n_dev) {
+    const double* __restrict__ px_cur, SeedRec* __restrict__ recs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  // the item count and the frame pose may come from earlier kernels of the same stream; the launch then covers the
-  // capacity and the items past the count become records no later stage touches
-  if (n_dev && i >= *n_dev) { recs[i] = md_dead_record(); return; }
-  if (T_cur_w_dev) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) fr.T_cur_w[k] = T_cur_w_dev[k];
-  }
   const double g[2] = {grad ? grad[2 * (size_t)i] : 1.0, grad ? grad[2 * (size_t)i + 1] : 0.0};
   recs[i] = md_geometry_item(fr, T_ref_w, kf_slot[i], level[i], px_ref + 2 * (size_t)i, f_ref + 3 * (size_t)i, pt_pos + 3 * (size_t)i,
                              edgelet && edgelet[i], g, px_cur + 2 * (size_t)i);
@@ -1047,10 +1027,9 @@ __global__ void md_finalize_kernel(int n, const SeedRec* __restrict__ recs, doub
 
 // the alignment stage over records [0, n)
 template <bool ONE_D>
-void launch_df_align(svo_hip_ctx* ctx, const DfFrame& fr, const uint8_t* cur_img, int n, int n_pad, const uint32_t* pwb_t, SeedRec* recs,
-                     const int* n_dev = nullptr) {
+void launch_df_align(svo_hip_ctx* ctx, const DfFrame& fr, const uint8_t* cur_img, int n, int n_pad, const uint32_t* pwb_t, SeedRec* recs) {
   hipLaunchKernelGGL(df_align_kernel<ONE_D>, dim3((n + ALIGN_PATCHES - 1) / ALIGN_PATCHES), dim3(ALIGN_BLOCK), 0, ctx->stream, fr, cur_img, n,
-                     n_pad, pwb_t, recs, n_dev);
+                     n_pad, pwb_t, recs);
 }
 
 int grid_for(int n, int block) {
@@ -1314,21 +1293,13 @@ static int df_scratch(svo_hip_ctx* ctx, int n, SeedRec** recs, uint32_t** pwb_t,
 
 }  // extern "C"
 
-// events of a device-resident seed batch (see svo_hip_seed_batch_* below): where the finalize stage leaves its counts
-struct DfEvents {
-  uint8_t* alive = nullptr;          // [n] in/out: 0 = erased from the list; cleared for seeds that converge / turn NaN
-  int report_updated = 0;
-  int* block_count = nullptr;        // [(n + 255) / 256]
-  int* hist = nullptr;               // [8]
-};
-
 // One DepthFilter::updateSeeds pass over n seeds in device SoA arrays: geometry -> search -> align -> finalize on the
-// context stream (shared by svo_hip_depth_filter_update_dev and the seed batches).
+// context stream (the stateless entries svo_hip_depth_filter_update[_dev]; the seed batches have their own launches below).
 static int df_run_pass(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, int ref_slot, const svo_hip_pyramid* cur, int cur_slot,
                        const svo_hip_camera* cam, const double T_ref_w[7], const double T_cur_w[7], int n, const double* px,
                        const double* f, const int32_t* level, float* a, float* b, float* mu, const float* z_range, float* sigma2,
                        const svo_hip_df_params* prm, int32_t* status, double* z, double* xyz_world, int32_t* n_zmssd,
-                       int32_t* n_align_iters, double* px_cur, int32_t* search_level, const DfEvents* ev) {
+                       int32_t* n_align_iters, double* px_cur, int32_t* search_level) {
   if (!ctx || !ref || !cur || !cam || !T_ref_w || !T_cur_w || !prm) return SVO_HIP_ERR_INVALID;
   SVO_REQUIRE(ctx, ref_slot >= 0 && ref_slot < ref->batch && cur_slot >= 0 && cur_slot < cur->batch);
   SVO_REQUIRE(ctx, ref->width == cam->width && ref->height == cam->height);
@@ -1354,8 +1325,7 @@ static int df_run_pass(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, int ref_slo
   auto stamp = [&](int k) { if (prof) (void)hipEventRecord(ctx->df_ev[k], ctx->stream); };
   stamp(0);
   hipLaunchKernelGGL(df_geometry_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, fr, n, px, f, level, mu, sigma2,
-                     (const double*)nullptr, (double*)nullptr, recs, ev ? (const uint8_t*)ev->alive : (const uint8_t*)nullptr,
-                     ev ? ev->hist : (int*)nullptr);
+                     (const double*)nullptr, (double*)nullptr, recs);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   stamp(1);
   hipLaunchKernelGGL(df_search_kernel, dim3((n + SEEDS_PER_BLOCK - 1) / SEEDS_PER_BLOCK), dim3(256), 0, ctx->stream, fr, ref_img, (size_t)0, cur_img, n, level, recs, pwb_t, n_pad);
@@ -1365,14 +1335,8 @@ static int df_run_pass(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, int ref_slo
   SVO_CHECK_HIP(ctx, hipGetLastError());
   stamp(3);
   struct Last { const bool on; svo_hip_ctx* c; ~Last() { if (on) { (void)hipEventRecord(c->df_ev[4], c->stream); c->df_ev_recorded = true; } } } last{prof, ctx};
-  if (ev) {
-    hipLaunchKernelGGL(df_finalize_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, fr, n, f, recs, a, b, mu, z_range,
-                       sigma2, status, z, xyz_world, n_zmssd, n_align_iters, px_cur, search_level, ev->alive, ev->report_updated,
-                       ev->block_count, ev->hist);
-  } else {
-    hipLaunchKernelGGL(df_finalize_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, fr, n, f, recs, a, b, mu, z_range,
-                       sigma2, status, z, xyz_world, n_zmssd, n_align_iters, px_cur, search_level);
-  }
+  hipLaunchKernelGGL(df_finalize_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, fr, n, f, recs, a, b, mu, z_range, sigma2,
+                     status, z, xyz_world, n_zmssd, n_align_iters, px_cur, search_level);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   return SVO_HIP_OK;
 }
@@ -1410,7 +1374,7 @@ int svo_hip_depth_filter_update_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* ref
                                     int32_t* status, double* z, double* xyz_world, int32_t* n_zmssd,
                                     int32_t* n_align_iters, double* px_cur, int32_t* search_level) {
   return df_run_pass(ctx, ref, ref_slot, cur, cur_slot, cam, T_ref_w, T_cur_w, n, px, f, level, a, b, mu, z_range, sigma2, prm, status, z,
-                     xyz_world, n_zmssd, n_align_iters, px_cur, search_level, nullptr);
+                     xyz_world, n_zmssd, n_align_iters, px_cur, search_level);
 }
 
 int svo_hip_epipolar_match_batch_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, int ref_slot,
@@ -1457,36 +1421,12 @@ int svo_hip_epipolar_match_batch_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* re
 }  // extern "C"
 
 // The middle stages of the findMatchDirect pipeline for callers that form the records themselves (svo_track.hip): scratch
-// for n_cap records + word-transposed patches, then warp / align2D (/ align1D) over records [0, min(n_cap, *n_dev)).
+// for n_cap records + word-transposed patches, then warp / align2D (/ align1D) over the records of n_cams cameras in one set
+// of launches (see df_search_cams_kernel)
 int svo_match_scratch(svo_hip_ctx* ctx, int n_cap, svo_dev::SeedRec** recs, uint32_t** pwb_t, int* n_pad) {
   return df_scratch(ctx, n_cap, recs, pwb_t, n_pad);
 }
 
-int svo_match_stages(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, int cur_slot, const svo_hip_camera* cam,
-                     int n_cap, const int* n_dev, const int32_t* level_ref_dev, svo_dev::SeedRec* recs, uint32_t* pwb_t, int n_pad,
-                     int n_pyr_levels, int align_max_iter, bool edgelets) {
-  if (!ctx || !ref || !cur || !cam || !recs || !pwb_t || !level_ref_dev) return SVO_HIP_ERR_INVALID;
-  SVO_REQUIRE(ctx, n_cap > 0 && cur_slot >= 0 && cur_slot < cur->batch);
-  DfFrame fr;
-  memset(&fr, 0, sizeof(fr));
-  fr.cam = svo_make_cam(*cam);
-  for (int l = 0; l < ref->n_levels; ++l) fr.ref_level_off[l] = ref->level_offset[l];
-  for (int l = 0; l < cur->n_levels; ++l) fr.cur_level_off[l] = cur->level_offset[l];
-  fr.n_pyr_levels = n_pyr_levels; fr.align_max_iter = align_max_iter; fr.keep_px_on_failure = 1;
-  const uint8_t* cur_img = cur->base + (size_t)cur_slot * cur->pyr_bytes;
-  hipLaunchKernelGGL(df_search_kernel, dim3((n_cap + SEEDS_PER_BLOCK - 1) / SEEDS_PER_BLOCK), dim3(256), 0, ctx->stream, fr, ref->base, ref->pyr_bytes,
-                     cur_img, n_cap, level_ref_dev, recs, pwb_t, n_pad, n_dev);
-  SVO_CHECK_HIP(ctx, hipGetLastError());
-  launch_df_align<false>(ctx, fr, cur_img, n_cap, n_pad, pwb_t, recs, n_dev);
-  SVO_CHECK_HIP(ctx, hipGetLastError());
-  if (edgelets) {
-    launch_df_align<true>(ctx, fr, cur_img, n_cap, n_pad, pwb_t, recs, n_dev);
-    SVO_CHECK_HIP(ctx, hipGetLastError());
-  }
-  return SVO_HIP_OK;
-}
-
-// the same stages for n_cams cameras in one set of launches (svo_hip_tracker_group_track): see df_search_cams_kernel
 int svo_match_stages_cams(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, const svo_hip_camera* cam, int n_cams,
                           int cap, const int* counters_dev, int counter_stride, const int32_t* level_ref_dev, svo_dev::SeedRec* recs,
                           uint32_t* pwb_t, int n_pad, int n_pyr_levels, int align_max_iter, bool edgelets) {
@@ -1514,16 +1454,16 @@ int svo_match_stages_cams(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const sv
   return SVO_HIP_OK;
 }
 
-// svo_hip_match_direct_batch_dev with, optionally, the pose of the current frame and the number of items left on the
-// device by earlier kernels of the stream (T_cur_w_dev / n_dev non-null: the tracking chain of svo_track.hip; n is then
-// the capacity the launches cover)
-int svo_match_direct_internal(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, int cur_slot,
-                              const svo_hip_camera* cam, int n_kf, const double* T_ref_w_dev, const double* T_cur_w,
-                              const double* T_cur_w_dev, int n, const int* n_dev, const int32_t* kf_slot_dev,
-                              const double* px_ref_dev, const double* f_ref_dev, const int32_t* level_ref_dev,
-                              const double* pt_pos_dev, const uint8_t* edgelet_dev, const double* grad_dev, int n_pyr_levels,
-                              int align_max_iter, double* px_cur_dev, uint8_t* success_dev, int32_t* search_level_dev) {
-  if (!ctx || !ref || !cur || !cam || (!T_cur_w && !T_cur_w_dev)) return SVO_HIP_ERR_INVALID;
+extern "C" {
+
+int svo_hip_match_direct_batch_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, int cur_slot,
+                                   const svo_hip_camera* cam, int n_kf, const double* T_ref_w_dev,
+                                   const double T_cur_w[7], int n, const int32_t* kf_slot_dev, const double* px_ref_dev,
+                                   const double* f_ref_dev, const int32_t* level_ref_dev, const double* pt_pos_dev,
+                                   const uint8_t* edgelet_dev, const double* grad_dev, int n_pyr_levels,
+                                   int align_max_iter, double* px_cur_dev, uint8_t* success_dev,
+                                   int32_t* search_level_dev) {
+  if (!ctx || !ref || !cur || !cam || !T_cur_w) return SVO_HIP_ERR_INVALID;
   SVO_REQUIRE(ctx, cur_slot >= 0 && cur_slot < cur->batch && n_kf >= 1 && n_kf <= ref->batch);
   SVO_REQUIRE(ctx, ref->width == cam->width && ref->height == cam->height && cur->width == cam->width && cur->height == cam->height);
   SVO_REQUIRE(ctx, n_pyr_levels >= 1 && n_pyr_levels <= ref->n_levels && n_pyr_levels <= cur->n_levels && align_max_iter >= 0);
@@ -1540,8 +1480,7 @@ int svo_match_direct_internal(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, cons
   }
   MdFrame mf;
   mf.cam = svo_make_cam(*cam);
-  if (T_cur_w) memcpy(mf.T_cur_w, T_cur_w, sizeof(double) * 7);
-  else memset(mf.T_cur_w, 0, sizeof(double) * 7);
+  memcpy(mf.T_cur_w, T_cur_w, sizeof(double) * 7);
   mf.n_pyr_levels = n_pyr_levels;
   mf.n_kf = n_kf; mf.n_ref_levels = ref->n_levels; mf.slot_base = 0;
   DfFrame fr;
@@ -1551,7 +1490,7 @@ int svo_match_direct_internal(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, cons
   for (int l = 0; l < cur->n_levels; ++l) fr.cur_level_off[l] = cur->level_offset[l];
   fr.n_pyr_levels = n_pyr_levels; fr.align_max_iter = align_max_iter; fr.keep_px_on_failure = 1;
   hipLaunchKernelGGL(md_geometry_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, mf, n, T_ref_w_dev, kf_slot_dev,
-                     px_ref_dev, f_ref_dev, level_ref_dev, pt_pos_dev, edgelet_dev, grad_dev, px_cur_dev, recs, T_cur_w_dev, n_dev);
+                     px_ref_dev, f_ref_dev, level_ref_dev, pt_pos_dev, edgelet_dev, grad_dev, px_cur_dev, recs);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(df_search_kernel, dim3((n + SEEDS_PER_BLOCK - 1) / SEEDS_PER_BLOCK), dim3(256), 0, ctx->stream, fr, ref->base, ref->pyr_bytes,
                      cur->base + (size_t)cur_slot * cur->pyr_bytes, n, level_ref_dev, recs, pwb_t, n_pad);
@@ -1566,21 +1505,6 @@ int svo_match_direct_internal(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, cons
                      search_level_dev);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   return SVO_HIP_OK;
-}
-
-extern "C" {
-
-int svo_hip_match_direct_batch_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, int cur_slot,
-                                   const svo_hip_camera* cam, int n_kf, const double* T_ref_w_dev,
-                                   const double T_cur_w[7], int n, const int32_t* kf_slot_dev, const double* px_ref_dev,
-                                   const double* f_ref_dev, const int32_t* level_ref_dev, const double* pt_pos_dev,
-                                   const uint8_t* edgelet_dev, const double* grad_dev, int n_pyr_levels,
-                                   int align_max_iter, double* px_cur_dev, uint8_t* success_dev,
-                                   int32_t* search_level_dev) {
-  if (!T_cur_w) return SVO_HIP_ERR_INVALID;
-  return svo_match_direct_internal(ctx, ref, cur, cur_slot, cam, n_kf, T_ref_w_dev, T_cur_w, nullptr, n, nullptr, kf_slot_dev, px_ref_dev,
-                                   f_ref_dev, level_ref_dev, pt_pos_dev, edgelet_dev, grad_dev, n_pyr_levels, align_max_iter, px_cur_dev,
-                                   success_dev, search_level_dev);
 }
 
 // host-buffer convenience form: copies the SoA arrays in, runs, copies the results out, synchronises
@@ -1811,11 +1735,6 @@ SVO_DEV void ev_scan_block(int n_blocks, int* __restrict__ block_count, const in
   if (threadIdx.x < 7) header->counts[threadIdx.x] = hist[threadIdx.x];
 }
 
-__global__ __launch_bounds__(1024) void ev_scan_kernel(int n_blocks, int* __restrict__ block_count, const int* __restrict__ hist,
-                                                       EvHeader* __restrict__ header, int* __restrict__ n_events_dev) {
-  ev_scan_block(n_blocks, block_count, hist, header, n_events_dev);
-}
-
 // The events, ascending seed index (56 B records).  A handful of them -- every frame but a keyframe's -- goes straight into
 // the page-locked host block (no copy, no second wait); more than EV_DIRECT_MAX are packed in device memory and fetched
 // with one transfer after the wait (scattered 56-byte stores over the link run at a few GB/s: 100 k events took 1.4 ms).
@@ -1846,19 +1765,10 @@ SVO_DEV void ev_scatter_block(int block, int n, int report_updated, const int32_
   events[off] = e;
 }
 
-__global__ __launch_bounds__(256) void ev_scatter_kernel(int n, int report_updated, const int32_t* __restrict__ status,
-                                                         const float* __restrict__ mu, const float* __restrict__ sigma2,
-                                                         const double* __restrict__ xyz, const double* __restrict__ px_cur,
-                                                         const int* __restrict__ block_offset, const int* __restrict__ n_events_dev,
-                                                         svo_hip_seed_event* __restrict__ events_host,
-                                                         svo_hip_seed_event* __restrict__ events_dev) {
-  ev_scatter_block(blockIdx.x, n, report_updated, status, mu, sigma2, xyz, px_cur, block_offset, n_events_dev, events_host, events_dev);
-}
-
-// ---- one launch set for SEVERAL batches (svo_hip_seed_batch_update_group_async) ------------------------------------------
-// A frame of the reference's depth filter updates the seeds of a few keyframes, a few hundred each: per batch that is six
-// launches of a handful of workgroups -- launch-bound (4 x 500 seeds: 105 us, profiles/r04_df_realistic_sizes.txt).  Here the
-// batches of a frame go through the stages together: batch j owns the blocks [first_block, first_block + n_blocks) of the
+// ---- one launch set for one or SEVERAL batches (svo_hip_seed_batch_update[_group]_async; a single batch is a group of one) --
+// A frame of the reference's depth filter updates the seeds of a few keyframes, a few hundred each: one launch set per batch
+// is six launches of a handful of workgroups -- launch-bound (4 x 500 seeds: 105 us, profiles/r04_df_realistic_sizes.txt).  Here
+// the batches of a frame go through the stages together: batch j owns the blocks [first_block, first_block + n_blocks) of the
 // thread-per-seed stages (a block never straddles two batches, so the batch -- its arrays, its keyframe's transforms -- is
 // block-uniform and lives in scalar registers), its records sit at first_block * 256 of the pass's scratch, the tail of its
 // last block is filled with inert records, and the pixel stages (search, align) run over the concatenation unchanged: a
@@ -2197,42 +2107,6 @@ int svo_hip_seed_batch_size(const svo_hip_seed_batch* sb, int* n, int* n_alive) 
   return SVO_HIP_OK;
 }
 
-static int sb_enqueue_jobs(svo_hip_ctx* ctx, int n_jobs, svo_hip_seed_batch* const* batches, const svo_hip_pyramid* ref, const int* ref_slots,
-                           const svo_hip_pyramid* cur, int cur_slot, const svo_hip_camera* cam, const double* T_ref_w,
-                           const double T_cur_w[7], const svo_hip_df_params* prm, int report_updated);
-static int sb_check_pass_args(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, int cur_slot, const svo_hip_camera* cam,
-                              const svo_hip_df_params* prm);
-
-int svo_hip_seed_batch_update_async(svo_hip_seed_batch* sb, const svo_hip_pyramid* ref, int ref_slot, const svo_hip_pyramid* cur,
-                                    int cur_slot, const svo_hip_camera* cam, const double T_ref_w[7], const double T_cur_w[7],
-                                    const svo_hip_df_params* prm, int report_updated) {
-  if (!sb) return SVO_HIP_ERR_INVALID;
-  svo_hip_ctx* ctx = sb->ctx;
-  if (sb->pending) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_seed_batch_update_async", "the previous pass has not been collected");
-  if (sb->n_blocks * 256 <= ctx->df_small_max) {           // a small batch: the two-launch form (sb_enqueue_jobs)
-    if (!ref || !cur || !cam || !T_ref_w || !T_cur_w || !prm) return SVO_HIP_ERR_INVALID;
-    SVO_REQUIRE(ctx, ref_slot >= 0 && ref_slot < ref->batch);
-    const int rc = sb_check_pass_args(ctx, ref, cur, cur_slot, cam, prm);
-    if (rc != SVO_HIP_OK) return rc;
-    SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return sb_enqueue_jobs(ctx, 1, &sb, ref, &ref_slot, cur, cur_slot, cam, T_ref_w, T_cur_w, prm, report_updated);
-  }
-  DfEvents ev;
-  ev.alive = sb->alive; ev.report_updated = report_updated ? 1 : 0; ev.block_count = sb->block_count; ev.hist = sb->hist;
-  const int rc = df_run_pass(ctx, ref, ref_slot, cur, cur_slot, cam, T_ref_w, T_cur_w, sb->n, sb->px, sb->f, sb->level, sb->a, sb->b, sb->mu,
-                             sb->z_range, sb->sigma2, prm, sb->status, nullptr, sb->xyz, nullptr, nullptr, sb->px_cur, nullptr, &ev);
-  if (rc != SVO_HIP_OK) return rc;
-  hipLaunchKernelGGL(ev_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, sb->n_blocks, sb->block_count, sb->hist,
-                     reinterpret_cast<EvHeader*>(sb->host_dev), sb->hist + 8);
-  hipLaunchKernelGGL(ev_scatter_kernel, dim3(sb->n_blocks), dim3(256), 0, ctx->stream, sb->n, ev.report_updated, sb->status, sb->mu,
-                     sb->sigma2, sb->xyz, sb->px_cur, sb->block_count, sb->hist + 8,
-                     reinterpret_cast<svo_hip_seed_event*>(sb->host_dev + kEvHeaderBytes), sb->events_dev);
-  SVO_CHECK_HIP(ctx, hipGetLastError());
-  sb->pending = true;
-  sb->report_updated = ev.report_updated;
-  return SVO_HIP_OK;
-}
-
 // one launch set over at most DF_GROUP_MAX batches (arguments checked by the callers)
 static int sb_enqueue_jobs(svo_hip_ctx* ctx, int n_jobs, svo_hip_seed_batch* const* batches, const svo_hip_pyramid* ref, const int* ref_slots,
                            const svo_hip_pyramid* cur, int cur_slot, const svo_hip_camera* cam, const double* T_ref_w,
@@ -2317,8 +2191,6 @@ int svo_hip_seed_batch_update_group_async(int n_batches, svo_hip_seed_batch* con
   if (n_batches < 1 || !batches || !batches[0]) return SVO_HIP_ERR_INVALID;
   svo_hip_ctx* ctx = batches[0]->ctx;
   if (!ref || !ref_slots || !cur || !cam || !T_ref_w || !T_cur_w || !prm) return svo_fail(ctx, SVO_HIP_ERR_INVALID, "svo_hip_seed_batch_update_group_async", "null argument");
-  if (n_batches == 1)
-    return svo_hip_seed_batch_update_async(batches[0], ref, ref_slots[0], cur, cur_slot, cam, T_ref_w, T_cur_w, prm, report_updated);
   // every batch's arguments are checked before anything is enqueued; up to DF_GROUP_MAX batches per set of launches
   for (int k = 0; k < n_batches; ++k) {
     svo_hip_seed_batch* sb = batches[k];
@@ -2339,6 +2211,13 @@ int svo_hip_seed_batch_update_group_async(int n_batches, svo_hip_seed_batch* con
     if (rc != SVO_HIP_OK) return rc;
   }
   return SVO_HIP_OK;
+}
+
+// a single batch is a group of one
+int svo_hip_seed_batch_update_async(svo_hip_seed_batch* sb, const svo_hip_pyramid* ref, int ref_slot, const svo_hip_pyramid* cur,
+                                    int cur_slot, const svo_hip_camera* cam, const double T_ref_w[7], const double T_cur_w[7],
+                                    const svo_hip_df_params* prm, int report_updated) {
+  return svo_hip_seed_batch_update_group_async(1, &sb, ref, &ref_slot, cur, cur_slot, cam, T_ref_w, T_cur_w, prm, report_updated);
 }
 
 int svo_hip_df_set_small_pass_limit(svo_hip_ctx* ctx, int max_seeds) {

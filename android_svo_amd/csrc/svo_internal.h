@@ -257,15 +257,6 @@ const svo_dev::FrameState* svo_sia_state_dev(const svo_hip_sia* s, int slot);
 int svo_sia_slot_arrays(svo_hip_sia* s, int slot, svo_dev::FrameConst** fc, double** px, double** f, double** pos, uint8_t** has_point, int* max_n);
 int svo_sia_note_device_slot(svo_hip_sia* s, int slot, const svo_hip_camera* cam, int n_feat_host);
 
-// svo_depth.hip: Matcher::findMatchDirect over n items (svo_hip_match_direct_batch_dev) with, optionally, the current
-// frame's pose and the item count read from device memory
-int svo_match_direct_internal(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, int cur_slot,
-                              const svo_hip_camera* cam, int n_kf, const double* T_ref_w_dev, const double* T_cur_w,
-                              const double* T_cur_w_dev, int n, const int* n_dev, const int32_t* kf_slot_dev,
-                              const double* px_ref_dev, const double* f_ref_dev, const int32_t* level_ref_dev,
-                              const double* pt_pos_dev, const uint8_t* edgelet_dev, const double* grad_dev, int n_pyr_levels,
-                              int align_max_iter, double* px_cur_dev, uint8_t* success_dev, int32_t* search_level_dev);
-
 // ---- svo_sia.hip <-> svo_nlls.hip: the solver's other NLLSSolver branches (Levenberg-Marquardt, robust weights) run
 // on the streaming solver's buffers.  The view is valid between svo_hip_sia_level_begin and the next call that changes
 // the solver.
@@ -291,13 +282,11 @@ void svo_nlls_free(svo_nlls_ext* e);
 
 namespace svo_dev { struct SeedRec; }
 int svo_match_scratch(svo_hip_ctx* ctx, int n_cap, svo_dev::SeedRec** recs, uint32_t** pwb_t, int* n_pad);
-int svo_match_stages(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, int cur_slot, const svo_hip_camera* cam,
-                     int n_cap, const int* n_dev, const int32_t* level_ref_dev, svo_dev::SeedRec* recs, uint32_t* pwb_t, int n_pad,
-                     int n_pyr_levels, int align_max_iter, bool edgelets);
 int svo_match_stages_cams(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, const svo_hip_camera* cam, int n_cams,
                           int cap, const int* counters_dev, int counter_stride, const int32_t* level_ref_dev, svo_dev::SeedRec* recs,
                           uint32_t* pwb_t, int n_pad, int n_pyr_levels, int align_max_iter, bool edgelets);
-// svo_refine.hip: svo_hip_pose_optimize_batch_dev with the counts / poses of the batch n_feat_stride ints / T_stride doubles apart
+// svo_refine.hip: the pose refinement of a batch whose counts / poses lie n_feat_stride ints / T_stride doubles apart
+// (svo_hip_pose_optimize_batch_dev: 1 and 7)
 int svo_pose_optimize_batch_strided(svo_hip_ctx* ctx, int batch, int max_n, const int32_t* n_feat_dev, int n_feat_stride,
                                     const double* T_f_w_dev, int T_stride, const double* f_dev, const double* pos_dev,
                                     const int32_t* level_dev, uint8_t* has_point_dev, double error_multiplier2,

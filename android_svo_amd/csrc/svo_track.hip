@@ -3,10 +3,12 @@
 //
 //   new_frame->T_f_w_ = last_frame->T_f_w_                                   (:175)
 //   SparseImgAlign(kltMaxLevel, kltMinLevel, 30, GaussNewton).run(last, new)  (:186-188)   svo_sia.hip, fused kernel
-//   Reprojector::reprojectMap(new_frame, overlap_kfs)                         (:203)       trk_plan_kernel -> Matcher::findMatchDirect
-//                                                                                          batch (svo_depth.hip) -> trk_replay_kernel
+//   Reprojector::reprojectMap(new_frame, overlap_kfs)                         (:203)       trk_plan_cams_kernel -> Matcher::findMatchDirect
+//                                                                                          batch (svo_depth.hip) -> trk_replay_cams_kernel
 //   pose_optimizer::optimizeGaussNewton(...)                                  (:226-229)   svo_refine.hip
-//   last_frame_ = new_frame_                                                  (frame_handler_mono.cpp:91)   trk_finish_kernel
+//   last_frame_ = new_frame_                                                  (frame_handler_mono.cpp:91)   trk_finish_cams_kernel
+//
+// A lone tracker is a group of one: the same launches serve one camera and the N cameras of svo_hip_tracker_group_track.
 //
 // What stays on the device between the stages: the pose SparseImgAlign leaves (read by the reprojection and by the pose
 // refinement straight from the solver's record), the candidates of every grid cell, the matches, and -- across frames --
@@ -658,8 +660,8 @@ SVO_DEV void trk_finish_body(const TrkMap& m, const TrkPlan& pl, const TrkFeat& 
   if (t == 0) __hip_atomic_store(done_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// ---- the kernels of one camera's chain, and the same bodies for the cameras of a tracker group: workgroup c of a launch takes
-// camera c's arguments from a table in device memory (svo_hip_tracker_group_track rewrites it every call)
+// ---- the kernels of the chain: workgroup c of a launch takes camera c's arguments from a table in device memory (a lone
+// tracker is a group of one; trk_track_all uploads the table when it changes)
 struct TrkCamArgs {
   TrkMap m;
   TrkPlan pl;
@@ -673,47 +675,37 @@ struct TrkCamArgs {
   const svo_hip_pose_opt_result* po;
   char* res;                           // the camera's result block (device address of page-locked memory)
   size_t o_px, o_f, o_level, o_point, o_edge, o_grad, o_pt, o_flag;
-  int n_points_cap;                    // (unused by the kernels; keeps the layout self-describing)
-  unsigned long long seq;
 };
 
-__global__ __launch_bounds__(TRK_THREADS) void trk_plan_kernel(TrkMap m, TrkPlan pl, MdFrame mf, const double* __restrict__ T_slot_w,
-                                                               SeedRec* __restrict__ recs, const FrameState* __restrict__ sia_state) {
-  trk_plan_body(m, pl, mf, T_slot_w, recs, sia_state);
-}
-__global__ __launch_bounds__(TRK_THREADS) void trk_plan_cams_kernel(const TrkCamArgs* __restrict__ args) {
-  const TrkCamArgs& a = args[blockIdx.x];
-  trk_plan_body(a.m, a.pl, a.mf, a.T_slot_w, a.recs, a.sia_state);
-}
-
-__global__ __launch_bounds__(TRK_THREADS) void trk_replay_kernel(TrkMap m, TrkPlan pl, TrkFeat ft, Cam cam, const FrameState* __restrict__ sia_state,
-                                                                 const SeedRec* __restrict__ recs, int* __restrict__ cell_winner,
-                                                                 int* __restrict__ cell_cum, int max_fts, int quality_min_fts) {
-  trk_replay_body(m, pl, ft, cam, sia_state, recs, cell_winner, cell_cum, max_fts, quality_min_fts);
-}
-__global__ __launch_bounds__(TRK_THREADS) void trk_replay_cams_kernel(const TrkCamArgs* __restrict__ args, int max_fts, int quality_min_fts) {
-  const TrkCamArgs& a = args[blockIdx.x];
+SVO_DEV void trk_plan_args(const TrkCamArgs& a) { trk_plan_body(a.m, a.pl, a.mf, a.T_slot_w, a.recs, a.sia_state); }
+SVO_DEV void trk_replay_args(const TrkCamArgs& a, int max_fts, int quality_min_fts) {
   trk_replay_body(a.m, a.pl, a.ft, a.mf.cam, a.sia_state, a.recs, a.cell_winner, a.cell_cum, max_fts, quality_min_fts);
 }
-
-SVO_DEV void trk_finish_from_args(const TrkCamArgs& a) {
+// seq: the frame's sequence number (every camera of the group advances with every call)
+SVO_DEV void trk_finish_args(const TrkCamArgs& a, unsigned long long seq) {
   char* rd = a.res;
   int* pt = reinterpret_cast<int*>(rd + a.o_pt);
   trk_finish_body(a.m, a.pl, a.ft, a.last, a.mf.cam, a.sia_state, a.po, reinterpret_cast<svo_hip_track_result*>(rd),
                   reinterpret_cast<double*>(rd + a.o_px), reinterpret_cast<double*>(rd + a.o_f), reinterpret_cast<int*>(rd + a.o_level),
                   reinterpret_cast<int*>(rd + a.o_point), reinterpret_cast<uint8_t*>(rd + a.o_edge), reinterpret_cast<double*>(rd + a.o_grad),
-                  pt, pt + a.m.n_points, pt + 2 * (size_t)a.m.n_points, reinterpret_cast<unsigned long long*>(rd + a.o_flag), a.seq);
+                  pt, pt + a.m.n_points, pt + 2 * (size_t)a.m.n_points, reinterpret_cast<unsigned long long*>(rd + a.o_flag), seq);
 }
-__global__ __launch_bounds__(256) void trk_finish_kernel(TrkMap m, TrkPlan pl, TrkFeat ft, TrkLast last, Cam cam, const FrameState* __restrict__ sia_state,
-                                                         const svo_hip_pose_opt_result* __restrict__ po, svo_hip_track_result* __restrict__ res,
-                                                         double* __restrict__ out_px, double* __restrict__ out_f, int* __restrict__ out_level,
-                                                         int* __restrict__ out_point, uint8_t* __restrict__ out_edgelet, double* __restrict__ out_grad,
-                                                         int* __restrict__ out_pt_type, int* __restrict__ out_pt_failed, int* __restrict__ out_pt_succeeded,
-                                                         unsigned long long* __restrict__ done_flag, unsigned long long seq) {
-  trk_finish_body(m, pl, ft, last, cam, sia_state, po, res, out_px, out_f, out_level, out_point, out_edgelet, out_grad, out_pt_type, out_pt_failed,
-                  out_pt_succeeded, done_flag, seq);
+
+__global__ __launch_bounds__(TRK_THREADS) void trk_plan_cams_kernel(const TrkCamArgs* __restrict__ args) { trk_plan_args(args[blockIdx.x]); }
+__global__ __launch_bounds__(TRK_THREADS) void trk_replay_cams_kernel(const TrkCamArgs* __restrict__ args, int max_fts, int quality_min_fts) {
+  trk_replay_args(args[blockIdx.x], max_fts, quality_min_fts);
 }
-__global__ __launch_bounds__(256) void trk_finish_cams_kernel(const TrkCamArgs* __restrict__ args) { trk_finish_from_args(args[blockIdx.x]); }
+__global__ __launch_bounds__(256) void trk_finish_cams_kernel(const TrkCamArgs* __restrict__ args, unsigned long long seq) {
+  trk_finish_args(args[blockIdx.x], seq);
+}
+// ... and the same for a lone tracker with its one entry passed by value, not uploaded: the pointers inside a by-value kernel
+// argument address global memory by the ABI, those read from the table are generic pointers, and every memory access of the
+// bodies becomes a flat instruction (measured: the lone chain 3 us a frame slower through the table kernels)
+__global__ __launch_bounds__(TRK_THREADS) void trk_plan_one_kernel(TrkCamArgs a) { trk_plan_args(a); }
+__global__ __launch_bounds__(TRK_THREADS) void trk_replay_one_kernel(TrkCamArgs a, int max_fts, int quality_min_fts) {
+  trk_replay_args(a, max_fts, quality_min_fts);
+}
+__global__ __launch_bounds__(256) void trk_finish_one_kernel(TrkCamArgs a, unsigned long long seq) { trk_finish_args(a, seq); }
 
 // Point::pos_ of n points after the host optimised them: one staged block in, one launch
 __global__ void trk_scatter_positions_kernel(int n, const int* __restrict__ idx, const double* __restrict__ pos, double* __restrict__ pt_pos) {
@@ -746,15 +738,19 @@ struct svo_hip_tracker_shared {
   uint8_t* img_dev = nullptr;
   size_t img_stride = 0;
   // [n_cams][...] arrays of the stages that run over all cameras at once
+  int rec_stride = 0;                       // a camera's candidate records / levels: max_items rounded up to the 16 a block takes
   int* counters = nullptr;                  // [n_cams][8]
-  int* cand_level_ref = nullptr;            // [n_cams][cap]
+  int* cand_level_ref = nullptr;            // [n_cams][rec_stride]
   double *ft_f = nullptr, *ft_pos = nullptr;   // [n_cams][NF][3]
   int* ft_level = nullptr;                  // [n_cams][NF]
   uint8_t* ft_has_point = nullptr;          // [n_cams][NF]
   svo_hip_pose_opt_result* po = nullptr;    // [n_cams]
-  // the group's argument table (TrkCamArgs per camera): page-locked staging + device copy
-  char* args_host = nullptr;
-  char* args_dev = nullptr;
+  // the argument table of the chain's kernels (TrkCamArgs per camera): built on the host every call, uploaded when it changed
+  std::vector<TrkCamArgs> args_next;
+  TrkCamArgs* args_host = nullptr;          // page-locked: the bytes of the last upload
+  TrkCamArgs* args_dev = nullptr;
+  bool args_valid = false;                  // args_dev holds args_host
+  unsigned long long seq = 0;               // frames tracked: the hand-over kernel stores it behind every camera's block (o_flag)
   std::vector<svo_hip_tracker*> members;
   std::vector<void*> dev_allocs;
 };
@@ -789,7 +785,6 @@ struct svo_hip_tracker {
   // result block: [svo_hip_track_result][px][f][level][point][edgelet][grad][pt_type][pt_failed][pt_succeeded]
   char* res_dev = nullptr;                  // device address of res_host
   char* res_host = nullptr;                 // page-locked, mapped into the device: the hand-over kernel writes it directly
-  unsigned long long seq = 0;               // frames tracked: the kernel stores it behind the block (o_flag) when the block is complete
   size_t o_flag = 0;
   uint8_t* img_dev = nullptr;               // device address of img_host (this camera's part of the shared image block)
   char* st_host = nullptr;                  // page-locked result of svo_hip_tracker_optimize_structure: [pos 64 x 3][iters 64][flag]
@@ -807,6 +802,7 @@ namespace {
 
 TrkMap make_map(const svo_hip_tracker* t) {
   TrkMap m;
+  memset(&m, 0, sizeof(m));                 // (no stray padding bytes: trk_track_all compares argument tables byte by byte)
   m.n_kf = t->n_kf; m.n_points = t->n_points; m.n_candidates = t->n_candidates;
   m.T_kf_w = t->T_kf_w; m.kf_slot = t->kf_slot; m.kf_key_point = t->kf_key_point; m.kf_ftr_offset = t->kf_ftr_offset;
   m.kf_ftr_point = t->kf_ftr_point; m.pt_pos = t->pt_pos; m.pt_type = t->pt_type; m.pt_n_failed = t->pt_n_failed;
@@ -897,16 +893,16 @@ static int trk_shared_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const 
   A(svo_hip_sia_create(ctx, n_cams, cfg->max_frame_features, &sh->sia));
   // (the library default, pinned here: the chain's decisions -- matches per cell, frame by frame -- equal the CPU chain's)
   if (rc == SVO_HIP_OK) rc = svo_hip_sia_set_option(sh->sia, SVO_HIP_SIA_OPT_ARITH, SVO_HIP_SIA_ARITH_EXACT);
-  const size_t N = (size_t)n_cams, C = cfg->max_items, NF = cfg->max_frame_features;
-  D(&sh->counters, N * 8); D(&sh->cand_level_ref, N * C);
+  sh->rec_stride = (cfg->max_items + 15) / 16 * 16;
+  const size_t N = (size_t)n_cams, NF = cfg->max_frame_features;
+  D(&sh->counters, N * 8); D(&sh->cand_level_ref, N * sh->rec_stride);
   D(&sh->ft_f, N * NF * 3); D(&sh->ft_pos, N * NF * 3); D(&sh->ft_level, N * NF); D(&sh->ft_has_point, N * NF); D(&sh->po, N);
   sh->img_stride = ((size_t)cam->width * cam->height + 64 + 255) & ~(size_t)255;
   if (rc == SVO_HIP_OK && hipHostMalloc((void**)&sh->img_host, N * sh->img_stride, hipHostMallocMapped) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
   if (rc == SVO_HIP_OK && hipHostGetDevicePointer((void**)&sh->img_dev, sh->img_host, 0) != hipSuccess) rc = SVO_HIP_ERR_DEVICE;
-  if (n_cams > 1) {
-    if (rc == SVO_HIP_OK && hipHostMalloc((void**)&sh->args_host, N * sizeof(TrkCamArgs), hipHostMallocDefault) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
-    D(&sh->args_dev, N * sizeof(TrkCamArgs));
-  }
+  if (rc == SVO_HIP_OK && hipHostMalloc((void**)&sh->args_host, N * sizeof(TrkCamArgs), hipHostMallocDefault) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
+  D(&sh->args_dev, N);
+  if (rc == SVO_HIP_OK) sh->args_next.resize(N);
   if (rc != SVO_HIP_OK) { trk_shared_destroy(sh); return rc; }
   *out = sh;
   return SVO_HIP_OK;
@@ -939,7 +935,7 @@ static int trk_member_create(svo_hip_tracker_shared* sh, int index, const svo_hi
   D(&pl.seg, C); D(&pl.seg_key, C); D(&pl.cell_count, NC + 1); D(&pl.cell_fill, NC); D(&pl.cell_offset, NC + 1); D(&pl.overlap_kf, TRK_MAX_SEL);
   D(&pl.overlap_count, TRK_MAX_SEL); D(&pl.cand_point, C); D(&pl.cand_obs, C); D(&pl.cand_deleted, C);
   pl.counters = sh->counters + 8 * (size_t)index;                              // (per-camera entries of the shared arrays)
-  pl.cand_level_ref = sh->cand_level_ref + C * (size_t)index;
+  pl.cand_level_ref = sh->cand_level_ref + sh->rec_stride * (size_t)index;
   D(&t->cell_winner, NC + 1); D(&t->cell_cum, NC + 1);
   t->po = sh->po + index;
   const size_t NF = cfg->max_frame_features;
@@ -1275,76 +1271,61 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
   SeedRec* recs = nullptr;
   uint32_t* pwb_t = nullptr;
   int n_pad = 0;
-  const int cap = t0->pl.cap;
-  rc = svo_match_scratch(ctx, N * cap, &recs, &pwb_t, &n_pad);
+  const int stride = sh->rec_stride;
+  rc = svo_match_scratch(ctx, N * stride, &recs, &pwb_t, &n_pad);
   if (rc != SVO_HIP_OK) return rc;
   MdFrame mf;
   memset(&mf, 0, sizeof(mf));
   mf.cam = cam; mf.n_pyr_levels = c.n_pyr_levels; mf.n_kf = c.max_keyframes; mf.n_ref_levels = c.n_levels;
-  if (N == 1) {
-    svo_hip_tracker* t = t0;
-    const TrkMap m = make_map(t);
-    const FrameState* st = svo_sia_state_dev(sh->sia, 0);
-    hipLaunchKernelGGL(trk_plan_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, m, t->pl, mf, t->T_slot_w, recs, st);
-    SVO_CHECK_HIP(ctx, hipGetLastError());
-    // warp + align2D (+ align1D when the map holds edgelets) over the candidates
-    rc = svo_match_stages(ctx, sh->kf_pyr, cur, 0, &t->cam, t->pl.cap, t->pl.counters, t->pl.cand_level_ref, recs, pwb_t, n_pad, c.n_pyr_levels,
-                          c.align_max_iter, t->any_edgelet);
-    if (rc != SVO_HIP_OK) return rc;
-    hipLaunchKernelGGL(trk_replay_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, m, t->pl, t->ft, cam, st, recs, t->cell_winner, t->cell_cum,
-                       c.max_fts, c.quality_min_fts);
-    SVO_CHECK_HIP(ctx, hipGetLastError());
-    // ---- pose_optimizer::optimizeGaussNewton(poseOptimThresh, poseOptimNumIter, ...) on the matched features, from the aligned pose
-    rc = svo_hip_pose_optimize_batch_dev(ctx, 1, c.max_frame_features, t->pl.counters + 5, st->T_cur_w, t->ft.f, t->ft.pos, t->ft.level, t->ft.has_point,
-                                         fabs(t->cam.fx), c.pose_optim_thresh, c.pose_optim_num_iter, t->po);
-    if (rc != SVO_HIP_OK) return rc;
-    // ---- hand-over + result: written straight into the page-locked block, the frame's sequence number last
-    char* rd = t->res_dev;
-    const unsigned long long seq = ++t->seq;
-    hipLaunchKernelGGL(trk_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, m, t->pl, t->ft, t->last, cam, st, t->po,
-                       reinterpret_cast<svo_hip_track_result*>(rd), reinterpret_cast<double*>(rd + t->o_px), reinterpret_cast<double*>(rd + t->o_f),
-                       reinterpret_cast<int*>(rd + t->o_level), reinterpret_cast<int*>(rd + t->o_point), reinterpret_cast<uint8_t*>(rd + t->o_edge),
-                       reinterpret_cast<double*>(rd + t->o_grad), reinterpret_cast<int*>(rd + t->o_pt), reinterpret_cast<int*>(rd + t->o_pt) + t->n_points,
-                       reinterpret_cast<int*>(rd + t->o_pt) + 2 * (size_t)t->n_points, reinterpret_cast<unsigned long long*>(rd + t->o_flag), seq);
-    SVO_CHECK_HIP(ctx, hipGetLastError());
-  } else {
-    // the cameras' arguments: one table, one transfer (the previous call's kernels are through with it: this thread waited for them)
-    TrkCamArgs* ah = reinterpret_cast<TrkCamArgs*>(sh->args_host);
-    for (int k = 0; k < N; ++k) {
-      svo_hip_tracker* t = sh->members[(size_t)k];
-      TrkCamArgs& a = ah[k];
-      memset(&a, 0, sizeof(a));
-      a.m = make_map(t); a.pl = t->pl; a.ft = t->ft; a.last = t->last;
-      a.mf = mf; a.mf.slot_base = k * c.max_keyframes;
-      a.T_slot_w = t->T_slot_w;
-      a.recs = recs + (size_t)k * cap;
-      a.sia_state = svo_sia_state_dev(sh->sia, k);
-      a.cell_winner = t->cell_winner; a.cell_cum = t->cell_cum;
-      a.po = t->po;
-      a.res = t->res_dev;
-      a.o_px = t->o_px; a.o_f = t->o_f; a.o_level = t->o_level; a.o_point = t->o_point; a.o_edge = t->o_edge; a.o_grad = t->o_grad; a.o_pt = t->o_pt;
-      a.o_flag = t->o_flag;
-      a.n_points_cap = c.max_points;
-      a.seq = ++t->seq;
-    }
-    SVO_CHECK_HIP(ctx, hipMemcpyAsync(sh->args_dev, sh->args_host, (size_t)N * sizeof(TrkCamArgs), hipMemcpyHostToDevice, ctx->stream));
-    const TrkCamArgs* ad = reinterpret_cast<const TrkCamArgs*>(sh->args_dev);
-    hipLaunchKernelGGL(trk_plan_cams_kernel, dim3(N), dim3(TRK_THREADS), 0, ctx->stream, ad);
-    SVO_CHECK_HIP(ctx, hipGetLastError());
-    rc = svo_match_stages_cams(ctx, sh->kf_pyr, cur, &t0->cam, N, cap, sh->counters, 8, sh->cand_level_ref, recs, pwb_t, n_pad, c.n_pyr_levels,
-                               c.align_max_iter, any_edgelet);
-    if (rc != SVO_HIP_OK) return rc;
-    hipLaunchKernelGGL(trk_replay_cams_kernel, dim3(N), dim3(TRK_THREADS), 0, ctx->stream, ad, c.max_fts, c.quality_min_fts);
-    SVO_CHECK_HIP(ctx, hipGetLastError());
-    const FrameState* st0 = svo_sia_state_dev(sh->sia, 0);
-    static_assert(sizeof(FrameState) % sizeof(double) == 0, "the solver records are a whole number of doubles apart");
-    rc = svo_pose_optimize_batch_strided(ctx, N, c.max_frame_features, sh->counters + 5, 8, st0->T_cur_w, (int)(sizeof(FrameState) / sizeof(double)),
-                                         sh->ft_f, sh->ft_pos, sh->ft_level, sh->ft_has_point, fabs(t0->cam.fx), c.pose_optim_thresh,
-                                         c.pose_optim_num_iter, sh->po);
-    if (rc != SVO_HIP_OK) return rc;
-    hipLaunchKernelGGL(trk_finish_cams_kernel, dim3(N), dim3(256), 0, ctx->stream, ad);
-    SVO_CHECK_HIP(ctx, hipGetLastError());
+  // the cameras' arguments: one table, uploaded only when it differs from the last upload (the map, the scratch behind the
+  // records); the previous call's kernels are through with the staging copy: this thread waited for them.  A lone tracker
+  // passes its entry by value instead (trk_plan_one_kernel).
+  TrkCamArgs* an = sh->args_next.data();
+  memset(an, 0, (size_t)N * sizeof(TrkCamArgs));
+  for (int k = 0; k < N; ++k) {
+    svo_hip_tracker* t = sh->members[(size_t)k];
+    TrkCamArgs& a = an[k];
+    a.m = make_map(t); a.pl = t->pl; a.ft = t->ft; a.last = t->last;
+    a.mf = mf; a.mf.slot_base = k * c.max_keyframes;
+    a.T_slot_w = t->T_slot_w;
+    a.recs = recs + (size_t)k * stride;
+    a.sia_state = svo_sia_state_dev(sh->sia, k);
+    a.cell_winner = t->cell_winner; a.cell_cum = t->cell_cum;
+    a.po = t->po;
+    a.res = t->res_dev;
+    a.o_px = t->o_px; a.o_f = t->o_f; a.o_level = t->o_level; a.o_point = t->o_point; a.o_edge = t->o_edge; a.o_grad = t->o_grad; a.o_pt = t->o_pt;
+    a.o_flag = t->o_flag;
   }
+  const size_t args_bytes = (size_t)N * sizeof(TrkCamArgs);
+  if (N > 1 && (!sh->args_valid || memcmp(sh->args_host, an, args_bytes) != 0)) {
+    sh->args_valid = false;
+    memcpy(sh->args_host, an, args_bytes);
+    SVO_CHECK_HIP(ctx, hipMemcpyAsync(sh->args_dev, sh->args_host, args_bytes, hipMemcpyHostToDevice, ctx->stream));
+    sh->args_valid = true;
+  }
+  const TrkCamArgs* ad = sh->args_dev;
+  if (N == 1) hipLaunchKernelGGL(trk_plan_one_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, an[0]);
+  else hipLaunchKernelGGL(trk_plan_cams_kernel, dim3(N), dim3(TRK_THREADS), 0, ctx->stream, ad);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  // warp + align2D (+ align1D when a map holds edgelets) over every camera's candidates
+  rc = svo_match_stages_cams(ctx, sh->kf_pyr, cur, &t0->cam, N, stride, sh->counters, 8, sh->cand_level_ref, recs, pwb_t, n_pad, c.n_pyr_levels,
+                             c.align_max_iter, any_edgelet);
+  if (rc != SVO_HIP_OK) return rc;
+  if (N == 1) hipLaunchKernelGGL(trk_replay_one_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, an[0], c.max_fts, c.quality_min_fts);
+  else hipLaunchKernelGGL(trk_replay_cams_kernel, dim3(N), dim3(TRK_THREADS), 0, ctx->stream, ad, c.max_fts, c.quality_min_fts);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  // ---- pose_optimizer::optimizeGaussNewton(poseOptimThresh, poseOptimNumIter, ...) on the matched features, from the aligned pose
+  const FrameState* st0 = svo_sia_state_dev(sh->sia, 0);
+  static_assert(sizeof(FrameState) % sizeof(double) == 0, "the solver records are a whole number of doubles apart");
+  rc = svo_pose_optimize_batch_strided(ctx, N, c.max_frame_features, sh->counters + 5, 8, st0->T_cur_w, (int)(sizeof(FrameState) / sizeof(double)),
+                                       sh->ft_f, sh->ft_pos, sh->ft_level, sh->ft_has_point, fabs(t0->cam.fx), c.pose_optim_thresh,
+                                       c.pose_optim_num_iter, sh->po);
+  if (rc != SVO_HIP_OK) return rc;
+  // ---- hand-over + result: written straight into the page-locked blocks, the frame's sequence number last
+  const unsigned long long seq = ++sh->seq;
+  if (N == 1) hipLaunchKernelGGL(trk_finish_one_kernel, dim3(1), dim3(256), 0, ctx->stream, an[0], seq);
+  else hipLaunchKernelGGL(trk_finish_cams_kernel, dim3(N), dim3(256), 0, ctx->stream, ad, seq);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
   // the one synchronisation of the frame: wait for every camera's sequence number (a spin on host memory: no driver call on the
   // way back), with the stream's own synchronisation as the fall-back and the error check
   {
@@ -1354,7 +1335,7 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
       for (int k = 0; k < N && all; ++k) {
         svo_hip_tracker* t = sh->members[(size_t)k];
         volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(t->res_host + t->o_flag);
-        all = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == t->seq;
+        all = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq;
       }
       if (!all) __builtin_ia32_pause();
     }
@@ -1362,7 +1343,7 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
     for (int k = 0; k < N; ++k) {
       svo_hip_tracker* t = sh->members[(size_t)k];
       volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(t->res_host + t->o_flag);
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != t->seq) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "the frame's kernels did not complete");
+      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "the frame's kernels did not complete");
     }
   }
   sh->last_idx = 1 - sh->last_idx;          // the new frames' pyramids are the next call's references

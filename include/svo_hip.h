@@ -493,7 +493,8 @@ int svo_hip_seed_batch_create(svo_hip_ctx* ctx, int n, const double* px, const d
                               svo_hip_seed_batch** out);                     /* host arrays, uploaded once */
 int svo_hip_seed_batch_destroy(svo_hip_seed_batch* batch);
 int svo_hip_seed_batch_size(const svo_hip_seed_batch* batch, int* n, int* n_alive);     /* n_alive: as of the last collect */
-/* enqueue one updateSeeds pass of the batch against cur->cur_slot on the context stream (returns at once) */
+/* enqueue one updateSeeds pass of the batch against cur->cur_slot on the context stream (returns at once): the group call
+ * below with one batch */
 int svo_hip_seed_batch_update_async(svo_hip_seed_batch* batch, const svo_hip_pyramid* ref, int ref_slot,
                                     const svo_hip_pyramid* cur, int cur_slot, const svo_hip_camera* cam,
                                     const double T_ref_w[7], const double T_cur_w[7], const svo_hip_df_params* prm,

@@ -119,8 +119,9 @@ def test_two_batches_enqueued_back_to_back_one_wait(ctx):
 def test_grouped_pass_over_several_keyframes_equals_one_pass_per_keyframe(ctx, sizes, small_limit):
     """svo_hip_seed_batch_update_group_async: the seeds of every keyframe of a frame through ONE set of launches --
     states, events and status counts per batch bit-identical to one svo_hip_seed_batch_update_async per keyframe (sizes
-    that end inside a block, a single seed, more batches than one launch set takes).  The passes per keyframe run as six
-    launches each (the two-launch form of small passes switched off); the grouped ones in both forms."""
+    that end inside a block, a single seed, more batches than one launch set takes).  The passes per keyframe run as
+    groups of one in the six-launch form (the two-launch form of small passes switched off); the grouped ones in both
+    forms."""
     mk = seedsynth.make_multi_keyframe_case(sizes, seed=31)
     K = len(sizes)
     kf = hip.Pyramid(ctx, mk.cam.width, mk.cam.height, 5, K)
