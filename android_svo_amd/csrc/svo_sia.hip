@@ -861,7 +861,15 @@ SVO_DEV void fused_interp_W(const uint2* F, float w_tl, float w_tr, float w_bl, 
 // (tests/test_gpu_parity.py::test_batch_ragged_and_empty) where the factored one returned a finite pose.  The launcher
 // picks the EXACT_ROWS instance of a shape for a batch that holds such a frame; every other frame of that batch still
 // takes the factored rows, so its result does not depend on the company it is launched in.
-template <int NW, int TPW, int CK, int VARIANT>
+//
+// TORD (SVO_HIP_SIA_REDUCTION_TILE_ORDER): the 29 sums of an evaluation are grouped by TILE instead of by wave.  Every tile
+// is reduced over its 64 lanes on its own (wave_reduce8 applied to one tile; for H the tile's row, which is such a total
+// already), the totals go to the tile's LDS row next to its H row, and wave 0 adds the rows of tiles 0, 1, 2, ... in that
+// order inside the one-lane window.  The sums of a frame are then a function of the frame's own patches and of nothing
+// that describes the launch (NW, TPW, CK, tiles_young, n_extra, the slot): a tile this frame does not have contributes a
+// row of +0.0, and x + (+0.0) is x bit for bit once the chain has left its initial +0.0 (it can never return to -0.0).
+// The default instances (TORD = false) carry none of this.
+template <int NW, int TPW, int CK, int VARIANT, bool TORD>
 __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
     const FrameConst* __restrict__ fc, FrameState* __restrict__ st, const uint8_t* __restrict__ ref_base,
     const uint8_t* __restrict__ cur_base, size_t pyr_bytes, FusedLevels lv, int max_n, const double* __restrict__ px,
@@ -875,6 +883,10 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
   // without either, 2.36 ms with the slot, 2.98 ms with both)
   constexpr bool LEAN = TPW >= 5;
   constexpr int P_EXTRA = (!LEAN && CK > 0 && TPW > CK) ? 1 : -1;   // plan order is L G L G ...: position 1
+  // The two forms of the outside-the-image correction (in the tile loop, patch by patch and entry by entry; after it, all
+  // of a tile's patches at once with the factored rows) round differently.  The tile-order instances all take the second
+  // one, whatever their shape: a frame's H rows must not depend on the shape class of the launch either.
+  constexpr bool CORR_IN_LOOP = LEAN && !TORD;
   const bool extra_lds = wave_of_thread() < n_extra;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   // The interpolated reference patch of every feature -- the 32 values W from which reference value, dx and dy of its
@@ -882,8 +894,10 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
   // theirs in LDS ([slot][8][64] float4, slot = position * 8 + wave), the others in memory ([frame][tile][8][64]
   // float4, L2 / Infinity-Cache resident: 8 coalesced 1-KiB loads per tile and evaluation, issued one tile ahead).
   float4* wc = reinterpret_cast<float4*>(smem);
-  __shared__ double red[NW][29];                              // 21 H + 6 Jres + chi2 + n_meas per wave
-  __shared__ double s_th[NW * TPW * 21];                      // per-tile H rows (lane e keeps entry e)
+  // TORD: no per-wave partials; a tile's row is 21 H + 6 Jres moments + chi2 + n_meas (see above)
+  constexpr int ROWW = TORD ? 29 : 21;
+  __shared__ double red[TORD ? 1 : NW][29];                   // 21 H + 6 Jres + chi2 + n_meas per wave
+  __shared__ double s_th[NW * TPW * ROWW];                    // per-tile H rows (lane e keeps entry e)
   __shared__ double s_x[8];
   __shared__ double s_last[TPW >= 5 ? 29 : 1];               // register-bound shapes only (see LEAN below)
   __shared__ double s_Hc[21], s_fac[21], s_inv[36];   // H of the previous evaluation, its LDL^T factor (lower triangle), H^-1 by columns
@@ -942,8 +956,8 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
   const int favoured_half = (5 * my_tiles) % 8 >= 4 ? favoured_tiles : -1;   // then the first half of this one
   auto tile_of = [&](int k) -> int { return k < my_tiles ? simd + 4 * (first_j + k) : n_tiles; };
   // per-tile H row of this wave (lane e keeps entry e): in LDS, read once per tile and evaluation
-  auto th_get = [&](int k) -> double { return lane < 21 ? s_th[(wave * TPW + k) * 21 + lane] : 0.0; };
-  auto th_set = [&](int k, double v) { if (lane < 21) s_th[(wave * TPW + k) * 21 + lane] = v; };
+  auto th_get = [&](int k) -> double { return lane < 21 ? s_th[(wave * TPW + k) * ROWW + lane] : 0.0; };
+  auto th_set = [&](int k, double v) { if (lane < 21) s_th[(wave * TPW + k) * ROWW + lane] = v; };
 
   if (threadIdx.x == 0) {
     double Tinv[7], T[7];
@@ -968,6 +982,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
     const int i_own = tile * TILE + lane;
     X[k] = make_double4(0, 0, 1, 1);
     th_set(k, 0.0);
+    if (TORD && lane >= 21 && lane < 29) s_th[(wave * TPW + k) * ROWW + lane] = 0.0;   // the row of a tile that does not exist stays +0.0
     fl[k] = 0;
     pxf[k][0] = pxf[k][1] = 0.0f;
     if (tile < n_tiles && i_own < n) {
@@ -1260,8 +1275,28 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         // ---- normal equations
         if (FAST || M32) { sdx = (double)sdxf; sdy = (double)sdyf; }
         const bool lin = ok && jvalid;
-        if (ok) { acc_chi += (double)chi; acc_n += 16; }
-        if (lin) {
+        if (TORD) {
+          // this tile's own totals: the same per-patch terms as below, reduced over the tile's 64 lanes and kept in the
+          // tile's LDS row (sign, fx/2^L and the undoing of the halved weights are applied once, to the frame's sums)
+          double v8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+          if (ok) { v8[6] = (double)chi; v8[7] = 16.0; }
+          if (lin) {
+            double zi = X[k].w;
+            asm volatile("" : "+v"(zi));
+            const double u = X[k].x * zi, v = X[k].y * zi;
+            const double a = __builtin_fma(u, sdx, v * sdy);
+            v8[0] = zi * sdx;
+            v8[1] = zi * sdy;
+            v8[2] = zi * a;
+            v8[3] = __builtin_fma(v, a, sdy);
+            v8[4] = __builtin_fma(u, a, sdx);
+            v8[5] = __builtin_fma(v, sdx, -(u * sdy));
+          }
+          const double t = wave_reduce8(v8);                   // lanes 8j..8j+7: the tile's total of value j
+          if ((lane & 7) == 0) s_th[(wave * TPW + k) * ROWW + 21 + (lane >> 3)] = t;
+        }
+        if (!TORD && ok) { acc_chi += (double)chi; acc_n += 16; }
+        if (!TORD && lin) {
           double zi = X[k].w;
           asm volatile("" : "+v"(zi));                       // opaque: nothing derived from it is kept in registers across evaluations
           // Jres_ -= J res (:273) with J = dx A + dy B summed over the patch: A sdx + B sdy written out in the
@@ -1282,19 +1317,19 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         // correction itself reads memory, and a load inside this loop -- even in a branch that is almost never taken
         // -- makes the compiler drain the loads in flight at every tile.
         const bool out_now = jvalid && !ok;
-        if (!LEAN) {
+        if (!CORR_IN_LOOP) {
           // no branch here (a taken scalar branch costs a wave ~20 cycles, a not-taken one ~10; tools/probes/branch_probe.hip):
           // the flag is rewritten by every lane and the change goes into a scalar bit
           const bool was_out = (fl[k] & F_GONE) != 0;
           gone_changed |= __ballot(out_now != was_out) != 0ull ? 1u << k : 0u;
           fl[k] = (uint8_t)((fl[k] & ~F_GONE) | (out_now ? F_GONE : 0));
         }
-        const unsigned long long gone_now = LEAN ? __ballot(out_now) : 0ull;
-        const unsigned long long gone_prev = LEAN ? __ballot((fl[k] & F_GONE) != 0) : 0ull;
-        if (LEAN && gone_now != gone_prev) {                   // wave-uniform
+        const unsigned long long gone_now = CORR_IN_LOOP ? __ballot(out_now) : 0ull;
+        const unsigned long long gone_prev = CORR_IN_LOOP ? __ballot((fl[k] & F_GONE) != 0) : 0ull;
+        if (CORR_IN_LOOP && gone_now != gone_prev) {           // wave-uniform
           gone_changed |= 1u << k;
           fl[k] = (uint8_t)((fl[k] & ~F_GONE) | (out_now ? F_GONE : 0));
-          if (LEAN) {                                          // register-bound shapes: correct the row right here
+          if (CORR_IN_LOOP) {                                  // register-bound shapes: correct the row right here
             const int tile_base = tile * TILE;
             double t = 0.0;
             if (lane < 21) t = tile_h[((size_t)b * max_tiles + tile) * TILE_ROW + lane];
@@ -1319,7 +1354,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
             th_set(k, t);
           }
         }
-        if (LEAN) { const double thk = th_get(k); if (lane < 21) accH += thk; }
+        if (LEAN && !TORD) { const double thk = th_get(k); if (lane < 21) accH += thk; }
       }
 
       __builtin_amdgcn_s_setprio(0);
@@ -1328,7 +1363,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
       // wave reduces: ~350 instructions per tile whatever the number of patches; walking the patches one after the
       // other -- a dependent load and a rank update each -- cost ~500 cycles per patch, and a coarse level can have 45
       // of a tile's 64 outside: the slowest of 64 scenes spent 9 % of its time there)
-      if (!LEAN && gone_changed) {                             // wave-uniform
+      if (!CORR_IN_LOOP && gone_changed) {                     // wave-uniform
 #pragma unroll
         for (int k = 0; k < TPW; ++k) {
           if (!((gone_changed >> k) & 1u)) continue;
@@ -1346,7 +1381,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
           th_set(k, t - out_row);
         }
       }
-      if (!LEAN) {
+      if (!LEAN && !TORD) {
 #pragma unroll
         for (int k = 0; k < TPW; ++k) {                        // rows of tiles that do not exist are zero
           const double thk = th_get(k);
@@ -1358,7 +1393,8 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
 #pragma unroll
       for (int j = 0; j < 5; ++j) pf[j] = load_row8(cur_img + off0 + j * stride);
       // ---- wave reduction, then the waves in fixed order, then the solve on one lane
-      {
+      // (TORD: the tiles' rows are in LDS already; wave 0 adds them in tile order after the barrier)
+      if (!TORD) {
         // lanes 8j..8j+7 receive the wave total of value j: 0..5 = Jres moments (sign and fx/2^L applied here),
         // 6 = chi2, 7 = number of measurements; red[wave][0..20] = H, [21..26] = Jres, [27] = chi2, [28] = n_meas
         double v8[8];
@@ -1382,8 +1418,14 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
       // rollback copy of the pose) is written AFTER the second one.
       double chi2_old = 0.0, nres_old = 0.0, hc_prev = 0.0;
       double coef[8], inv_row[6], cur[7];
+      double row_scale = 1.0;                // TORD, wave 0: what the frame's sum on this lane is multiplied by (1 for H)
       int it = 0, stop_old = 0, iters_l = 0, fac_valid = 0;
       if (wave == 0) {
+        if (TORD) {
+          // lanes 21..26 = Jres moments (sign and fx/2^L, x2 for the halved weights), 27 = chi2 (x4), 28 = n_meas
+          const int j = lane - 21;
+          row_scale = lane < 21 ? 1.0 : (j == 0 || j == 1 || j == 4) ? 2.0 * jscale : (j < 6 ? -2.0 * jscale : (j == 6 ? 4.0 : 1.0));
+        }
 #pragma unroll
         for (int i = 0; i < 7; ++i) cur[i] = s_model[i];        // (= T, which lives in scalar registers that are needed elsewhere by now)
         chi2_old = s_chi2; nres_old = s_nres; hc_prev = s_Hc[lane < 21 ? lane : 0];   // H of the previous evaluation
@@ -1402,7 +1444,21 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
       double new_chi2 = 0.0;
       bool rollback = false;
       if (wave == 0) {
-        {
+        if (TORD) {
+          // tile t lives on SIMD t & 3 as that SIMD's tile number t >> 2: row (wave, k) of its owner (see tile_of).  Every
+          // row this shape can hold is read -- no branch on the frame's own tile count, rows beyond it are +0.0
+          constexpr int MAXT = (NW == 8 ? 8 : 4) * TPW < FUSED_MAX_TILES ? (NW == 8 ? 8 : 4) * TPW : FUSED_MAX_TILES;
+          const double* rows_l = s_th + (lane < 29 ? lane : 28);
+          double r[MAXT];
+#pragma unroll
+          for (int t = 0; t < MAXT; ++t) {                                         // all rows asked for at once
+            const int j = t >> 2, old = (NW == 4 || j < TPW) ? 1 : 0;
+            r[t] = rows_l[(((t & 3) + (old ? 0 : 4)) * TPW + (old ? j : j - TPW)) * ROWW];
+          }
+#pragma unroll
+          for (int t = 0; t < MAXT; ++t) v += r[t];                                // the tiles in ascending order
+          v *= row_scale;
+        } else {
           double r[NW];
 #pragma unroll
           for (int w = 0; w < NW; ++w) r[w] = red[w][lane < 29 ? lane : 28];       // all partials asked for at once
@@ -1660,6 +1716,7 @@ struct svo_hip_sia {
   // NLLSSolver's other branches (svo_nlls.hip): method_, setRobustCostFunction
   int opt_method = SVO_HIP_SIA_METHOD_GAUSS_NEWTON, opt_scale = SVO_HIP_SIA_SCALE_UNIT, opt_weight = SVO_HIP_SIA_WEIGHT_UNIT;
   int opt_chi2 = SVO_HIP_SIA_CHI2_PER_PATCH;
+  int opt_reduction = SVO_HIP_SIA_REDUCTION_PER_WAVE;
   svo_nlls_ext* nlls = nullptr;
   // stepwise state
   svo_hip_sia_params prm{};
@@ -1739,11 +1796,11 @@ int flush_fc(svo_hip_sia* s) {
 }
 
 // One launch of the fused kernel over slots [0, n_launch).
-template <int NW, int TPW, int CK, int VARIANT>
+template <int NW, int TPW, int CK, int VARIANT, bool TORD>
 int launch_fused_x(svo_hip_sia* s, int n_launch, const svo_hip_sia_params* prm, size_t lds_bytes, int tiles_young, int n_extra = 0) {
   svo_hip_ctx* ctx = s->ctx;
   // > 64 KiB of dynamic LDS has to be allowed explicitly (per device: set it on every launch, it is cheap)
-  SVO_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&sia_fused_kernel<NW, TPW, CK, VARIANT>),
+  SVO_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&sia_fused_kernel<NW, TPW, CK, VARIANT, TORD>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   FusedLevels lv;
   memset(&lv, 0, sizeof(lv));
@@ -1755,7 +1812,7 @@ int launch_fused_x(svo_hip_sia* s, int n_launch, const svo_hip_sia_params* prm, 
   fp.max_level = prm->max_level; fp.min_level = prm->min_level; fp.n_iter = prm->n_iter;
   fp.early_stop = prm->early_stop; fp.eps = prm->eps;
   fp.moments_f32 = s->opt_arith == SVO_HIP_SIA_ARITH_MOMENTS_F32 ? 1 : 0;
-  hipLaunchKernelGGL((sia_fused_kernel<NW, TPW, CK, VARIANT>), dim3(n_launch), dim3(NW * 64), lds_bytes, ctx->stream, s->fc, s->st,
+  hipLaunchKernelGGL((sia_fused_kernel<NW, TPW, CK, VARIANT, TORD>), dim3(n_launch), dim3(NW * 64), lds_bytes, ctx->stream, s->fc, s->st,
                      s->ref->base, s->cur->base, s->ref->pyr_bytes, lv, s->max_n, s->px, s->f, s->pos, s->has_point, s->sxyz, s->tile_h,
                      s->wmem, s->max_tiles, fp, tiles_young, n_extra);
   SVO_CHECK_HIP(ctx, hipGetLastError());
@@ -1763,13 +1820,14 @@ int launch_fused_x(svo_hip_sia* s, int n_launch, const svo_hip_sia_params* prm, 
 }
 
 // LDS tiles (8 KiB) the 8-wave shape can hold beyond ck per wave: what 160 KiB leave next to the kernel's static LDS
-template <int TPW, int CK>
+// (the tile-order instances have wider tile rows and no per-wave partials: asked for on their own)
+template <int TPW, int CK, bool TORD>
 int fused_extra_tiles_t() {
   static int cached = -1;
   if (cached < 0) {
     hipFuncAttributes at;
     cached = 0;
-    if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&sia_fused_kernel<8, TPW, CK, FUSED_PLAIN>)) == hipSuccess) {
+    if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&sia_fused_kernel<8, TPW, CK, FUSED_PLAIN, TORD>)) == hipSuccess) {
       const long free_b = 160L * 1024 - (long)at.sharedSizeBytes - (long)FUSED_WAVES * CK * FUSED_WC_BYTES;
       cached = free_b > 0 ? (int)(free_b / FUSED_WC_BYTES) : 0;
       if (cached > FUSED_EXTRA_TILES) cached = FUSED_EXTRA_TILES;
@@ -1777,11 +1835,11 @@ int fused_extra_tiles_t() {
   }
   return cached;
 }
-int fused_extra_tiles(int tpw, int ck) {
+int fused_extra_tiles(int tpw, int ck, bool tord) {
   (void)ck;
   switch (tpw) {
-    case 3: return fused_extra_tiles_t<3, 2>();
-    case 4: return fused_extra_tiles_t<4, 2>();
+    case 3: return tord ? fused_extra_tiles_t<3, 2, true>() : fused_extra_tiles_t<3, 2, false>();
+    case 4: return tord ? fused_extra_tiles_t<4, 2, true>() : fused_extra_tiles_t<4, 2, false>();
     default: return 0;
   }
 }
@@ -1799,7 +1857,7 @@ int fused_old_share(const svo_hip_sia* s, int max_n, int* per_simd_out) {
 }
 
 // The shape of the fused kernel for a launch of n_launch pairs whose largest frame has max_n patches.
-template <int VARIANT>
+template <int VARIANT, bool TORD = false>
 int launch_fused_shape(svo_hip_sia* s, int n_launch, int max_n, const svo_hip_sia_params* prm) {
   svo_hip_ctx* ctx = s->ctx;
   int per_simd = 1;
@@ -1813,10 +1871,10 @@ int launch_fused_shape(svo_hip_sia* s, int n_launch, int max_n, const svo_hip_si
   if (four) {
     const size_t lds4 = (size_t)4 * (per_simd < 2 ? 1 : 2) * FUSED_WC_BYTES;
     switch (per_simd) {                                                // tiles per wave (3 runs as 4 with an empty slot)
-      case 1: return launch_fused_x<4, 1, 1, VARIANT>(s, n_launch, prm, lds4, 0);
-      case 2: return launch_fused_x<4, 2, 2, VARIANT>(s, n_launch, prm, lds4, 0);
+      case 1: return launch_fused_x<4, 1, 1, VARIANT, TORD>(s, n_launch, prm, lds4, 0);
+      case 2: return launch_fused_x<4, 2, 2, VARIANT, TORD>(s, n_launch, prm, lds4, 0);
       case 3:
-      case 4: return launch_fused_x<4, 4, 2, VARIANT>(s, n_launch, prm, lds4, 0);
+      case 4: return launch_fused_x<4, 4, 2, VARIANT, TORD>(s, n_launch, prm, lds4, 0);
       default: break;
     }
   }
@@ -1824,17 +1882,17 @@ int launch_fused_shape(svo_hip_sia* s, int n_launch, int max_n, const svo_hip_si
   SVO_REQUIRE(ctx, ty >= 0 && ty <= tpw);
   // two tiles per wave keep their interpolated patches in LDS (8 waves x 2 x 8 KiB), the others in memory
   const int ck = tpw < 2 ? tpw : 2;
-  int n_extra = tpw > ck ? fused_extra_tiles(tpw, ck) : 0;
+  int n_extra = tpw > ck ? fused_extra_tiles(tpw, ck, TORD) : 0;
   if (s->opt_extra_lds >= 0) n_extra = tpw > ck ? s->opt_extra_lds : 0;   // diagnostic override
-  if (n_extra < 0 || n_extra > (tpw > ck ? fused_extra_tiles(tpw, ck) : 0)) n_extra = 0;
+  if (n_extra < 0 || n_extra > (tpw > ck ? fused_extra_tiles(tpw, ck, TORD) : 0)) n_extra = 0;
   const size_t lds = (size_t)(FUSED_WAVES * ck + n_extra) * FUSED_WC_BYTES;
   switch (tpw) {                 // tiles of an older wave
-    case 1: return launch_fused_x<8, 1, 1, VARIANT>(s, n_launch, prm, lds, ty);
-    case 2: return launch_fused_x<8, 2, 2, VARIANT>(s, n_launch, prm, lds, ty);
-    case 3: return launch_fused_x<8, 3, 2, VARIANT>(s, n_launch, prm, lds, ty, n_extra);
-    case 4: return launch_fused_x<8, 4, 2, VARIANT>(s, n_launch, prm, lds, ty, n_extra);
-    case 5: return launch_fused_x<8, 5, 2, VARIANT>(s, n_launch, prm, lds, ty, n_extra);
-    case 6: return launch_fused_x<8, 6, 2, VARIANT>(s, n_launch, prm, lds, ty, n_extra);
+    case 1: return launch_fused_x<8, 1, 1, VARIANT, TORD>(s, n_launch, prm, lds, ty);
+    case 2: return launch_fused_x<8, 2, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty);
+    case 3: return launch_fused_x<8, 3, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty, n_extra);
+    case 4: return launch_fused_x<8, 4, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty, n_extra);
+    case 5: return launch_fused_x<8, 5, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty, n_extra);
+    case 6: return launch_fused_x<8, 6, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty, n_extra);
     default: break;
   }
   return svo_fail(ctx, SVO_HIP_ERR_INVALID, "fused SparseImgAlign", "unsupported tiles-per-wave");
@@ -1885,10 +1943,13 @@ int run_fused(svo_hip_sia* s, int n_slots, const svo_hip_sia_params* prm) {
   hipEvent_t* ev = next_events(s, s->ev_res, s->ev_res_used);
   if (ev) (void)hipEventRecord(ev[0], ctx->stream);
   // (the fast arithmetic is an option of the plain instance: a batch with a tiny frame runs with exact or f32 moments, as set)
-  rc = tiny ? launch_fused_shape<FUSED_EXACT_ROWS>(s, n_slots, max_n, prm)
-            : s->opt_arith == SVO_HIP_SIA_ARITH_FAST ? launch_fused_shape<FUSED_FAST>(s, n_slots, max_n, prm)
-            : s->opt_arith == SVO_HIP_SIA_ARITH_MOMENTS_F32 ? launch_fused_shape<FUSED_M32>(s, n_slots, max_n, prm)
-                                                            : launch_fused_shape<FUSED_PLAIN>(s, n_slots, max_n, prm);
+  if (s->opt_reduction == SVO_HIP_SIA_REDUCTION_TILE_ORDER)     // exact arithmetic only (svo_hip_sia_run has refused the others)
+    rc = tiny ? launch_fused_shape<FUSED_EXACT_ROWS, true>(s, n_slots, max_n, prm) : launch_fused_shape<FUSED_PLAIN, true>(s, n_slots, max_n, prm);
+  else
+    rc = tiny ? launch_fused_shape<FUSED_EXACT_ROWS>(s, n_slots, max_n, prm)
+              : s->opt_arith == SVO_HIP_SIA_ARITH_FAST ? launch_fused_shape<FUSED_FAST>(s, n_slots, max_n, prm)
+              : s->opt_arith == SVO_HIP_SIA_ARITH_MOMENTS_F32 ? launch_fused_shape<FUSED_M32>(s, n_slots, max_n, prm)
+                                                              : launch_fused_shape<FUSED_PLAIN>(s, n_slots, max_n, prm);
   if (ev) (void)hipEventRecord(ev[1], ctx->stream);
   return rc;
 }
@@ -2177,6 +2238,16 @@ int svo_hip_sia_run(svo_hip_sia* s, int n_slots, const svo_hip_sia_params* prm) 
   if (s->shard_world != 1)     // (svo_hip_sia_run_sharded / the step-wise entry points are the sharded forms)
     return svo_fail(s->ctx, SVO_HIP_ERR_STATE, "svo_hip_sia_run", "a patch shard is set on this solver: the whole solve needs the all-reduce of svo_hip_sia_run_sharded");
   // Levenberg-Marquardt, a robust cost (I/nlls_solver.h:46-48), chi2 in the reference's order: their own driver over the streaming kernels
+  if (s->opt_reduction == SVO_HIP_SIA_REDUCTION_TILE_ORDER) {
+    // the tile-order sums exist in the fused kernel only (the streaming kernels group by `chunks`, which follows the batch
+    // size): whatever would take another path is refused, never run with sums that depend on the batch after all
+    const char* why = nullptr;
+    if (nlls_branches(s)) why = "SVO_HIP_SIA_REDUCTION_TILE_ORDER: Levenberg-Marquardt / robust weights / reference-order chi2 run through the streaming kernels, whose sums depend on the batch";
+    else if (s->opt_arith != SVO_HIP_SIA_ARITH_EXACT) why = "SVO_HIP_SIA_REDUCTION_TILE_ORDER exists for SVO_HIP_SIA_ARITH_EXACT only";
+    else if (s->opt_mode == SVO_HIP_SIA_MODE_STREAM) why = "SVO_HIP_SIA_REDUCTION_TILE_ORDER: SVO_HIP_SIA_MODE_STREAM forces the streaming kernels, whose sums depend on the batch";
+    else if (n_slots > 0 && n_slots <= s->batch && !fused_applies(s, n_slots)) why = "SVO_HIP_SIA_REDUCTION_TILE_ORDER: a frame of more than 2816 patches takes the streaming kernels, whose sums depend on the batch";
+    if (why) return svo_fail(s->ctx, SVO_HIP_ERR_STATE, "svo_hip_sia_run", why);
+  }
   if (nlls_branches(s)) return svo_nlls_run(s, n_slots, prm, s->opt_method, s->opt_scale, s->opt_weight);
   if (n_slots > 0 && n_slots <= s->batch && fused_applies(s, n_slots)) return run_fused(s, n_slots, prm);
   s->last_mode = 0;
@@ -2310,6 +2381,10 @@ int svo_hip_sia_set_option(svo_hip_sia* s, int option, int value) {
     case SVO_HIP_SIA_OPT_SCALE_ESTIMATOR: SVO_REQUIRE(ctx, value >= SVO_HIP_SIA_SCALE_UNIT && value <= SVO_HIP_SIA_SCALE_NORMAL); s->opt_scale = value; break;
     case SVO_HIP_SIA_OPT_WEIGHT_FUNCTION: SVO_REQUIRE(ctx, value >= SVO_HIP_SIA_WEIGHT_UNIT && value <= SVO_HIP_SIA_WEIGHT_HUBER); s->opt_weight = value; break;
     case SVO_HIP_SIA_OPT_CHI2: SVO_REQUIRE(ctx, value == SVO_HIP_SIA_CHI2_PER_PATCH || value == SVO_HIP_SIA_CHI2_REFERENCE_ORDER); s->opt_chi2 = value; break;
+    case SVO_HIP_SIA_OPT_REDUCTION:
+      SVO_REQUIRE(ctx, value == SVO_HIP_SIA_REDUCTION_PER_WAVE || value == SVO_HIP_SIA_REDUCTION_TILE_ORDER);
+      s->opt_reduction = value;
+      break;
     default: return svo_fail(ctx, SVO_HIP_ERR_INVALID, "svo_hip_sia_set_option", "unknown option");
   }
   return SVO_HIP_OK;

@@ -1436,6 +1436,15 @@ int svo_hip_tracker_last_result(svo_hip_tracker* t, svo_hip_track_result* result
   return SVO_HIP_OK;
 }
 
+int svo_hip_tracker_set_sia_option(svo_hip_tracker* t, int option, int value) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  // the one option that changes no decision of the chain, only the grouping of the solver's sums; the solver is the
+  // shared one: a camera of a group sets it for the group
+  if (option != SVO_HIP_SIA_OPT_REDUCTION)
+    return svo_fail(t->ctx, SVO_HIP_ERR_INVALID, "svo_hip_tracker_set_sia_option", "only SVO_HIP_SIA_OPT_REDUCTION can be set on a tracker's solver");
+  return svo_hip_sia_set_option(t->sh->sia, option, value);
+}
+
 int svo_hip_tracker_image_buffer(svo_hip_tracker* t, uint8_t** buffer) {
   if (!t || !buffer) return SVO_HIP_ERR_INVALID;
   *buffer = reinterpret_cast<uint8_t*>(t->img_host);

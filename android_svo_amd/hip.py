@@ -23,6 +23,8 @@ SEED_BEHIND, SEED_NOT_IN_FRAME, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEE
 SIA_OPT_MODE, SIA_OPT_WAVES, SIA_OPT_CHUNKS, SIA_OPT_EXTRA_LDS, SIA_OPT_OLD_TILES, SIA_OPT_ARITH = range(6)
 SIA_OPT_METHOD, SIA_OPT_SCALE_ESTIMATOR, SIA_OPT_WEIGHT_FUNCTION, SIA_OPT_CHI2 = 6, 7, 8, 9
 SIA_CHI2_PER_PATCH, SIA_CHI2_REFERENCE_ORDER = 0, 1
+SIA_OPT_REDUCTION = 10
+SIA_REDUCTION_PER_WAVE, SIA_REDUCTION_TILE_ORDER = 0, 1      # fused kernel: sums grouped by wave (default) / by tile, in tile order (batch-invariant)
 # vk::NLLSSolver's enumerators (I/nlls_solver.h:46-48)
 SIA_METHOD_GAUSS_NEWTON, SIA_METHOD_LEVENBERG_MARQUARDT = 0, 1
 SIA_SCALE_UNIT, SIA_SCALE_TDIST, SIA_SCALE_MAD, SIA_SCALE_NORMAL = range(4)
@@ -936,6 +938,11 @@ class Tracker:
         self.n_cells, self.grid_cols, self.grid_rows = nc.value, gc.value, gr.value
         self.n_points = 0
 
+    def set_sia_option(self, option: int, value: int):
+        """svo_hip_tracker_set_sia_option: SIA_OPT_REDUCTION on the SparseImgAlign solver this tracker uses (a camera of a group:
+        the group's shared solver, so the setting holds for every camera of the group)"""
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_set_sia_option(self.h, int(option), int(value)), "tracker_set_sia_option")
+
     def upload_keyframe(self, slot: int, img: np.ndarray):
         im = np.ascontiguousarray(img, dtype=np.uint8)
         assert im.shape == (self.cam.height, self.cam.width)
@@ -1068,6 +1075,10 @@ class TrackerGroup:
             self.cameras.append(Tracker(ctx, cam, _group_handle=th, _cfg=self.cfg))
         self._ptrs = (C.POINTER(C.c_uint8) * self.n)()
         self._res = (CTrackResult * self.n)()
+
+    def set_sia_option(self, option: int, value: int):
+        """SIA_OPT_REDUCTION on the solver the cameras share (svo_hip_tracker_set_sia_option on camera 0's handle)"""
+        self.cameras[0].set_sia_option(option, value)
 
     def track(self, imgs) -> list:
         """one frame of every camera; imgs[c]: (height, width) u8 (camera c's image_buffer() array is not copied).  Returns the

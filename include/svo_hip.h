@@ -228,11 +228,16 @@ int svo_hip_sia_set_reduce_buffer(svo_hip_sia* sia, void* dev_ptr);
 #define SVO_HIP_SIA_OPT_SCALE_ESTIMATOR 7 /* setRobustCostFunction's first argument (:47): SVO_HIP_SIA_SCALE_UNIT (default: no weights), _TDIST, _MAD, _NORMAL */
 #define SVO_HIP_SIA_OPT_WEIGHT_FUNCTION 8 /* ... and its second (:48): SVO_HIP_SIA_WEIGHT_UNIT (default), _TDIST, _TUKEY, _HUBER */
 #define SVO_HIP_SIA_OPT_CHI2 9            /* SVO_HIP_SIA_CHI2_PER_PATCH (default) or _REFERENCE_ORDER, see below */
+#define SVO_HIP_SIA_OPT_REDUCTION 10      /* fused kernel: SVO_HIP_SIA_REDUCTION_PER_WAVE (default) or _TILE_ORDER (opt-in), see below */
 #define SVO_HIP_SIA_MODE_AUTO 0
 #define SVO_HIP_SIA_MODE_STREAM 1
 /* Arithmetic levels of the fused kernel.  At every level the image math is the reference's f32, pixel choice, projection,
  * H_ (formed once per level from the patches' gradient sums), normal equations, solve and the Gauss-Newton control flow are
- * unchanged: H_, the tracked-patch count and -- on every scene tested -- the iteration counts are bit for bit the same.
+ * unchanged: H_, the tracked-patch count and -- on every scene tested -- the iteration counts are bit for bit the same
+ * from one level to the other, for the same batch.  (What a frame's bits owe to the OTHER frames of its batch is a matter of
+ * the grouping of the sums, not of the arithmetic level: SVO_HIP_SIA_OPT_REDUCTION below.  In the default grouping H_, Jres_
+ * and chi2 depend in their last bits on the batch's largest frame and size at every level; in _TILE_ORDER, which exists for
+ * EXACT only, nothing does.)
  * EXACT (the default; round 4 shipped MOMENTS_F32 as the default, round 5 took that back: every caller that sets nothing --
  *   the drop-in SparseImgAlign::run binding included -- gets the reference's arithmetic): the reference's arithmetic
  *   statement by statement -- uncontracted f32 interpolation, residual products and Jacobian moments in f64
@@ -283,6 +288,32 @@ int svo_hip_sia_set_reduce_buffer(svo_hip_sia* sia, void* dev_ptr);
  * Levenberg-Marquardt and the robust costs always use it. */
 #define SVO_HIP_SIA_CHI2_PER_PATCH 0
 #define SVO_HIP_SIA_CHI2_REFERENCE_ORDER 1
+/* SVO_HIP_SIA_OPT_REDUCTION: how the fused kernel groups the 29 sums of an evaluation (21 entries of H_, 6 of Jres_, chi2,
+ * n_meas).  Everything before the sums is per patch or per 64-patch tile and everything after them is a function of the sums,
+ * so the grouping is the only thing through which the other frame pairs of a launch can reach a frame's result.
+ * _PER_WAVE (default): a wave adds the lane values of all the tiles it owns, reduces once, and the waves are added in fixed
+ *   order.  Which tiles a wave owns is the kernel shape, chosen per launch from the launch's largest frame and its number of
+ *   pairs (and by SVO_HIP_SIA_OPT_WAVES / _OLD_TILES): the last bits of a frame's H_, Jres_ and chi2 -- and through them of
+ *   its pose; on a borderline frame an iteration count -- depend on the company the frame is launched in.  Reproducible run
+ *   to run for the same batch.
+ * _TILE_ORDER (opt-in): every tile is reduced over its 64 lanes on its own and the tiles' totals are added in ascending
+ *   tile order, in f64, by one wave.  Every field of svo_hip_sia_result is then a function of the frame pair alone: equal
+ *   bytes whatever the batch size, the other frames, the slot, the kernel shape and the diagnostic shape options
+ *   (tests/test_gpu_sia_batch_invariance.py).  The results differ from _PER_WAVE's in the last bits and meet the same
+ *   tolerances against the reference.  Measured cost (profiles/HISTORY.md): C1 -- 2000 patches, 4096 pairs per launch, fixed
+ *   work -- 21.16 against 19.08 ms per step, a time ratio of 1.11 (193.6 k against 214.7 k frames/s); by kernel shape between
+ *   0.88 and 1.11 (tools/reduction_shapes.py); the lone tracking chain +0.7 % per frame, inside its run-to-run spread.
+ *   Besides the sums, the mode's kernels take ONE form of the outside-the-image correction of a tile's H row in every shape:
+ *   the default kernels for more than 2048 patches use another form than the smaller shapes, which is a second way the
+ *   largest frame of a batch reaches the others' last bits in the default mode.
+ *   svo_hip_sia_run must take the fused kernel then.  Where it cannot it fails with SVO_HIP_ERR_STATE and runs nothing:
+ *   SVO_HIP_SIA_MODE_STREAM, a frame of more than 2816 patches, Levenberg-Marquardt, a robust cost,
+ *   SVO_HIP_SIA_CHI2_REFERENCE_ORDER (the streaming kernels group by workgroups per frame, which follow the batch size) and
+ *   an arithmetic level other than SVO_HIP_SIA_ARITH_EXACT (the mode's kernels exist for that level only).
+ *   The step-wise entry points (svo_hip_sia_begin ... _finish) and svo_hip_sia_run_sharded always run the streaming kernels
+ *   and are not affected by this option. */
+#define SVO_HIP_SIA_REDUCTION_PER_WAVE 0
+#define SVO_HIP_SIA_REDUCTION_TILE_ORDER 1
 #define SVO_HIP_SIA_METHOD_GAUSS_NEWTON 0
 #define SVO_HIP_SIA_METHOD_LEVENBERG_MARQUARDT 1
 #define SVO_HIP_SIA_SCALE_UNIT 0
@@ -313,8 +344,10 @@ int svo_hip_sia_solver_state(svo_hip_sia* sia, int slot, float* scale, double* m
  * 0 = the streaming kernels (one launch per Gauss-Newton evaluation; always used by the step-wise entry
  * points).  svo_hip_sia_set_option(SVO_HIP_SIA_OPT_MODE, SVO_HIP_SIA_MODE_STREAM) forces 0.  In a batch that holds
  * frames with fewer than 16 patches those frames take the entry-by-entry Hessian rows a rank-deficient system needs
- * (chosen per workgroup); the other frames' results are bit for bit what they are without such company.  A frame's
- * result does depend on the kernel shape, i.e. on the largest frame of the batch and on the number of pairs. */
+ * (chosen per workgroup); the other frames' results are bit for bit what they are without such company.  With the
+ * default SVO_HIP_SIA_REDUCTION_PER_WAVE a frame's result does depend, in the last bits, on the kernel shape, i.e. on the
+ * largest frame of the batch and on the number of pairs; with SVO_HIP_SIA_REDUCTION_TILE_ORDER it depends on nothing but
+ * the frame pair (SVO_HIP_SIA_OPT_REDUCTION above). */
 int svo_hip_sia_last_run_mode(svo_hip_sia* sia, int* mode);
 /* Optional timing of the two heavy kernels with HIP events recorded on the context stream around
  * each launch (precompute: one per level; residual: one per Gauss-Newton evaluation; in fused mode the single
@@ -704,6 +737,11 @@ int svo_hip_tracker_set_last_frame(svo_hip_tracker* trk, const uint8_t* level0, 
  * saves that copy (about 10 us of a 640x480 frame).  The buffer belongs to the tracker, is free again when
  * svo_hip_tracker_track returns, and lives until svo_hip_tracker_destroy. */
 int svo_hip_tracker_image_buffer(svo_hip_tracker* trk, uint8_t** buffer);
+/* An option of the SparseImgAlign solver this tracker uses.  SVO_HIP_SIA_OPT_REDUCTION only (see svo_hip_sia_set_option;
+ * any other option: SVO_HIP_ERR_INVALID -- the chain fixes the solver's method, cost and arithmetic).  The cameras of a group
+ * share one solver: set on a handle from svo_hip_tracker_group_camera it holds for EVERY camera of that group.  Takes
+ * effect from the next tracked frame. */
+int svo_hip_tracker_set_sia_option(svo_hip_tracker* trk, int option, int value);
 /* One frame.  Outputs (host, any may be NULL except result): the new frame's features in creation order -- px[n][2],
  * f[n][3], level[n], point[n] (-1 where the pose refinement dropped the observation, pose_optimizer.cpp:154-157),
  * edgelet[n], grad[n][2], capacity max_frame_features -- and the point counters after the frame (capacity n_points of
@@ -722,9 +760,14 @@ int svo_hip_tracker_track(svo_hip_tracker* trk, const uint8_t* level0, svo_hip_t
  * workgroup (or one slice of its grid) per camera, the cameras' arguments come from a table in device memory.
  * A camera's handle (svo_hip_tracker_group_camera) takes every svo_hip_tracker_* call except _track and _destroy: its map,
  * its last frame, its keyframe slots (0 .. max_keyframes - 1, its own), structure optimisation, image buffer.  Outcomes are
- * bit for bit those of the same camera tracked by a lone svo_hip_tracker (tests/test_gpu_tracker_group.py), provided the
- * SparseImgAlign kernel shape is the same: it is chosen by the largest feature count among the cameras' last frames
- * (svo_hip_sia_last_run_mode).  cfg->max_items must be a multiple of 16 when n_cameras > 1. */
+ * bit for bit those of the same camera tracked by a lone svo_hip_tracker (tests/test_gpu_tracker_group.py) in one of two
+ * ways.  By default (SVO_HIP_SIA_REDUCTION_PER_WAVE) only while the SparseImgAlign kernel shape is the same: it is chosen
+ * by the largest feature count among the cameras' last frames and by the number of cameras (svo_hip_sia_last_run_mode), and a
+ * camera that tracks beside a larger one gets the last bits of its SparseImgAlign pose from another grouping of the sums
+ * than alone (rounding level on that frame; every later frame starts from that pose).  With
+ * svo_hip_tracker_set_sia_option(SVO_HIP_SIA_OPT_REDUCTION, SVO_HIP_SIA_REDUCTION_TILE_ORDER) on the group AND on the lone
+ * tracker nothing depends on the company: every camera equals its lone tracker whatever the other cameras hold
+ * (tests/test_gpu_tracker_invariance.py).  cfg->max_items must be a multiple of 16 when n_cameras > 1. */
 typedef struct svo_hip_tracker_group svo_hip_tracker_group;
 int svo_hip_tracker_group_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const svo_hip_tracker_config* cfg, int n_cameras,
                                  svo_hip_tracker_group** out);

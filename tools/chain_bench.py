@@ -147,7 +147,7 @@ def single_stream_chain(ctx, n_frames=20):
     return out
 
 
-def tracker_leg(ctx, seq, min_level, repeats=3):
+def tracker_leg(ctx, seq, min_level, repeats=3, tile_order=False):
     """The same frames through svo_hip_tracker_track: the whole chain of a frame enqueued on one stream with the aligned
     pose, the candidates and the matches staying on the device, level 0 of the new image from page-locked staging, one
     synchronisation per frame.  Timed around the C call (the wall time a C++ caller sees)."""
@@ -156,6 +156,8 @@ def tracker_leg(ctx, seq, min_level, repeats=3):
     n = len(seq["px0"])
     trk = hip.Tracker(ctx, seq["cam"], max_keyframes=2, max_points=1024, max_obs=1024, max_kf_features=1024, max_candidates=16, max_items=1024,
                       max_frame_features=1024, grid_size=tc.CELL, max_fts=tc.MAX_FTS, klt_min_level=min_level)
+    if tile_order:                                                  # the batch-invariant sums of the SparseImgAlign kernel (--tile-order)
+        trk.set_sia_option(hip.SIA_OPT_REDUCTION, hip.SIA_REDUCTION_TILE_ORDER)
     trk.upload_keyframe(0, seq["pyrs"][0][0])
     imgs = [np.ascontiguousarray(p[0]) for p in seq["pyrs"]]
     res = hip.CTrackResult()
@@ -331,6 +333,7 @@ def main():
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--min-level", type=int, default=2)     # the shipping default: L4 -> L2
     ap.add_argument("--tracker-only", action="store_true")
+    ap.add_argument("--tile-order", action="store_true", help="with --tracker-only: SIA_REDUCTION_TILE_ORDER on the tracker's solver")
     ap.add_argument("--cameras", action="store_true", help="only the multi-camera figure (1 / 2 / 4 / 8 trackers on as many host threads)")
     ap.add_argument("--camera-counts", default="1,2,4,8")
     ap.add_argument("--group-only", action="store_true", help="only svo_hip_tracker_group_track for --camera-counts (tools/trace_group.sh)")
@@ -348,7 +351,7 @@ def main():
         return
     if args.tracker_only:
         seq = tc.make_sequence(n_frames=args.frames)
-        print(json.dumps({"hip_tracker": tracker_leg(hip.Context(0), seq, args.min_level)}))
+        print(json.dumps({"hip_tracker": tracker_leg(hip.Context(0), seq, args.min_level, tile_order=args.tile_order), "tile_order": args.tile_order}))
         return
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_gpu_sequence import HipStages
