@@ -321,7 +321,10 @@ SVO_DEV void df_geometry_seed(const Cam& cam, const double* T_cur_ref_vis, const
       double pc[2];
       world2cam(cam, xyz_f, pc);
       const int ox = (int)pc[0], oy = (int)pc[1];
-      if (!(ox >= 0 && ox < cam.width && oy >= 0 && oy < cam.height)) { rc.status = SVO_HIP_SEED_NOT_IN_FRAME; live = false; }
+      // A seed whose mu is NaN projects to NaN.  cast<int>() of a NaN is INT_MIN in the x86-64 build the oracle follows
+      // (not in frame, the seed is left alone) but 0 on the device (pixel (0,0): in frame, searched, b += 1): spelled out.
+      const bool nan_px = pc[0] != pc[0] || pc[1] != pc[1];
+      if (nan_px || !(ox >= 0 && ox < cam.width && oy >= 0 && oy < cam.height)) { rc.status = SVO_HIP_SEED_NOT_IN_FRAME; live = false; }
     }
     const float z_inv_min = mu + sqrtf(sigma2);
     rc.z_inv_min = z_inv_min;

@@ -14,53 +14,7 @@ import numpy as np
 
 from oracle import orc
 
-F32, F64 = np.float32, np.float64
-SQRT_2_PI = 1.41421356237309505            # depth_filter.cpp:360 -- sqrt(2), not sqrt(2 pi): kept
-PI = 3.14159265                            # I/global.h:92
-
-
-def update_seed_typed(x, tau2, a, b, mu, z_range, sigma2):
-    """depth_filter.cpp:368-391 on float32 arrays; every line keeps the type the C++ expression has"""
-    d = lambda v: v.astype(F64)
-    f = lambda v: v.astype(F32)
-    norm_scale = np.sqrt(sigma2 + tau2)                                          # float
-    s2 = f(1.0 / (1.0 / d(sigma2) + 1.0 / d(tau2)))                              # 1. literals: double, truncated
-    m = s2 * (mu / sigma2 + x / tau2)                                            # float
-    exponent = -0.5 * ((d(x) - d(mu)) / d(norm_scale)) ** 2                      # normal_pdf: all double
-    pdf = (1.0 / (d(norm_scale) * SQRT_2_PI)) * np.exp(exponent)
-    C1 = f(d(a / (a + b)) * pdf)
-    C2 = f(d(b / (a + b)) * 1.0 / d(z_range))
-    nc = C1 + C2
-    C1 = C1 / nc
-    C2 = C2 / nc
-    ab = a + b                                                                   # float
-    ff = f(d(C1) * (d(a) + 1.0) / (d(ab) + 1.0) + d(C2 * a) / (d(ab) + 1.0))
-    e = f(d(C1) * (d(a) + 1.0) * (d(a) + 2.0) / ((d(ab) + 1.0) * (d(ab) + 2.0)) +
-          d(C2 * a * (a + F32(1.0)) / ((ab + F32(1.0)) * (ab + F32(2.0)))))
-    mu_new = C1 * m + C2 * mu
-    sigma2_new = C1 * (s2 + m * m) + C2 * (sigma2 + mu * mu) - mu_new * mu_new
-    a_new = (e - ff) / (ff - e / ff)
-    b_new = a_new * (F32(1.0) - ff) / ff
-    return a_new, b_new, mu_new, sigma2_new
-
-
-def update_seed_exact(x, tau2, a, b, mu, z_range, sigma2):
-    L = np.longdouble
-    x, tau2, a, b, mu, z_range, sigma2 = (v.astype(L) for v in (x, tau2, a, b, mu, z_range, sigma2))
-    ns = np.sqrt(sigma2 + tau2)
-    s2 = 1 / (1 / sigma2 + 1 / tau2)
-    m = s2 * (mu / sigma2 + x / tau2)
-    pdf = (1 / (ns * L(SQRT_2_PI))) * np.exp(-0.5 * ((x - mu) / ns) ** 2)
-    C1 = a / (a + b) * pdf
-    C2 = b / (a + b) / z_range
-    nc = C1 + C2
-    C1, C2 = C1 / nc, C2 / nc
-    ff = C1 * (a + 1) / (a + b + 1) + C2 * a / (a + b + 1)
-    e = C1 * (a + 1) * (a + 2) / ((a + b + 1) * (a + b + 2)) + C2 * a * (a + 1) / ((a + b + 1) * (a + b + 2))
-    mu_new = C1 * m + C2 * mu
-    sigma2_new = C1 * (s2 + m * m) + C2 * (sigma2 + mu * mu) - mu_new * mu_new
-    a_new = (e - ff) / (ff - e / ff)
-    return a_new, a_new * (1 - ff) / ff, mu_new, sigma2_new
+from seed_reference import F32, F64, update_seed_exact, update_seed_typed, compute_tau_np   # shared with the edge-case and GPU tests
 
 
 def random_seeds(n, rng):
@@ -105,19 +59,6 @@ def test_update_seed_against_two_independent_evaluations():
     np.testing.assert_allclose(kat[[0, 1, 2, 4]], [10.4296455, 9.88126183, 0.511521995, 0.0118117034], rtol=3e-7)
     kt = update_seed_typed(*(np.array([v], F32) for v in (0.52, 0.01, 10, 10, 0.5, 1.0, 1.0 / 36)))
     np.testing.assert_allclose([kt[0][0], kt[1][0], kt[2][0], kt[3][0]], [10.4296455, 9.88126183, 0.511521995, 0.0118117034], rtol=3e-7)
-
-
-def compute_tau_np(t, f, z, px_error_angle, dtype):
-    """depth_filter.cpp:396-416"""
-    t, f, z = t.astype(dtype), f.astype(dtype), z.astype(dtype)
-    a = f * z[:, None] - t
-    t_norm = np.sqrt((t * t).sum(axis=1))
-    a_norm = np.sqrt((a * a).sum(axis=1))
-    alpha = np.arccos((f * t).sum(axis=1) / t_norm)
-    beta = np.arccos((a * -t).sum(axis=1) / (t_norm * a_norm))
-    beta_plus = beta + dtype(px_error_angle)
-    gamma_plus = dtype(PI) - alpha - beta_plus
-    return t_norm * np.sin(beta_plus) / np.sin(gamma_plus) - z
 
 
 def test_compute_tau_against_two_independent_evaluations():
