@@ -79,6 +79,20 @@ SVO_DEV void se3_act(const double* T, const double* p, double* out) {
   out[0] = T[0] + r[0]; out[1] = T[1] + r[1]; out[2] = T[2] + r[2];
 }
 
+// se3_act with the doubled vector part q2 = 2 q.xyz formed by the caller (once for many points): uv = q2 x p is, product
+// by product and difference by difference, exactly the double of q x p (a power-of-two factor commutes with every
+// rounding; nothing here is near the ends of the exponent range), so so3_rotate's three additions uv + uv disappear and
+// the result has the same bits.  The rest is so3_rotate's order.
+SVO_DEV void se3_act_q2(const double* T, const double* q2, const double* p, double* out) {
+  double uv[3], quv[3];
+  cross3(q2, p, uv);
+  cross3(T + 3, uv, quv);
+  const double x = (p[0] + T[6] * uv[0]) + quv[0];
+  const double y = (p[1] + T[6] * uv[1]) + quv[1];
+  const double z = (p[2] + T[6] * uv[2]) + quv[2];
+  out[0] = T[0] + x; out[1] = T[1] + y; out[2] = T[2] + z;
+}
+
 // sin and cos of a small angle by their Taylor series in Horner form (|x| <= 0.5: truncation error < 2e-23,
 // rounding ~1 ulp, i.e. the same accuracy class as a libm call at a tenth of the instructions); the
 // Gauss-Newton update angles are tiny, larger arguments take the library path.

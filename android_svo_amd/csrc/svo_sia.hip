@@ -566,6 +566,11 @@ __global__ void sia_finish_kernel(const FrameConst* __restrict__ fc, FrameState*
 //     time, 12 waves 85 k, 4 waves 68 k.  Packed f32 (v_pk_mul_f32 / v_pk_add_f32) was measured too: CDNA4's SIMD
 //     already issues a plain wave64 f32 op in 2 cycles, the packed forms take two passes (18 % slower);
 //   * the two waves of a SIMD are balanced with s_setprio (see tile_of in the kernel);
+//   * the tile loop is bound by the waves' issue interval, so it carries no instruction it can do without: what is uniform
+//     and constant over a level or an evaluation (camera, pose, doubled quaternion, image base, stride, scale, bounds) sits in
+//     scalar registers and none of it is spilled inside the loop (per-tile conditions are bits of one scalar, tested where they
+//     are used: prio_plan, n_have), row addresses are 32-bit offsets on the scalar image base, the in-image test is four
+//     f32 comparisons on the floors, and the usual division path is straight-line code;
 //   * the Gauss-Newton state lives in LDS; the solve runs between two barriers: H^-1 by columns on six lanes when H
 //     changed, a 6x6 matrix-vector product otherwise, SE3::exp and the pose product on one lane.
 // Data-dependent exits are real `break`s here, so a converged frame costs nothing further.
@@ -626,24 +631,26 @@ struct LeanCam {
 SVO_DEV void div2_by(double x, double y, double z, double& qx, double& qy) {
   const unsigned ez = (unsigned)__double2hiint(z) & 0x7ff00000u;                  // biased exponent << 20
   const bool mid = ez - (123u << 20) < (1800u << 20);                             // 2^-900 <= |z| < 2^900 (no 0, inf, NaN, subnormal)
-  if (__ballot(!mid) == 0ull) {                                                   // wave-uniform
-    double r = __builtin_amdgcn_rcp(z);
-    double e = __builtin_fma(-z, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-z, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    const double q0 = x * r, p0 = y * r;
-    qx = __builtin_fma(__builtin_fma(-z, q0, x), r, q0);
-    qy = __builtin_fma(__builtin_fma(-z, p0, y), r, p0);
-  } else {
+  // (straight-line, and replaced afterwards by the wave that needs it: as an if / else the compiler put this path, the
+  // one every wave takes, out of line behind two taken branches per tile)
+  double r = __builtin_amdgcn_rcp(z);
+  double e = __builtin_fma(-z, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  e = __builtin_fma(-z, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  const double q0 = x * r, p0 = y * r;
+  qx = __builtin_fma(__builtin_fma(-z, q0, x), r, q0);
+  qy = __builtin_fma(__builtin_fma(-z, p0, y), r, p0);
+  if (__builtin_expect(__ballot(!mid) != 0ull, 0)) {                              // wave-uniform
     qx = x / z;
     qy = y / z;
   }
 }
 
 // projection of one patch into the current level image (:220-236); the weights come back halved (see the caller)
-SVO_DEV LppGeom lpp_project(const double* T, const LeanCam& cam, const double4& X, bool visible, float scale, int cols,
-                            int rows, int stride) {
+// (colsf, rowsf: the level's cols - border and rows - border as floats)
+SVO_DEV LppGeom lpp_project(const double* T, const double* q2, const LeanCam& cam, const double4& X, bool visible, float scale, float colsf,
+                            float rowsf, int stride) {
   LppGeom g;
   // (no `if (visible)` around this: a patch that is not visible carries finite coordinates, and a branch costs more
   // than the work it would skip in the rare wave without a single visible patch)
@@ -651,7 +658,7 @@ SVO_DEV LppGeom lpp_project(const double* T, const LeanCam& cam, const double4& 
     const int border = 3;
     const double xyz_ref[3] = {X.x, X.y, X.z};
     double xyz_cur[3], pxd[2];
-    se3_act(T, xyz_ref, xyz_cur);
+    se3_act_q2(T, q2, xyz_ref, xyz_cur);                 // q2 = 2 T.q.xyz, formed once per evaluation: same bits as se3_act
     double un, vn;
     div2_by(xyz_cur[0], xyz_cur[1], xyz_cur[2], un, vn);
     if (__builtin_expect(cam.d == nullptr, 1)) {
@@ -667,20 +674,26 @@ SVO_DEV LppGeom lpp_project(const double* T, const LeanCam& cam, const double4& 
     }
     const float u_cur = (float)pxd[0] * scale;
     const float v_cur = (float)pxd[1] * scale;
-    const int u_cur_i = (int)floorf(u_cur);
-    const int v_cur_i = (int)floorf(v_cur);
-    g.ok = visible && (u_cur_i >= 0 && v_cur_i >= 0 && u_cur_i - border >= 0 && v_cur_i - border >= 0 &&
-            u_cur_i < cols - border && v_cur_i < rows - border) && u_cur == u_cur && v_cur == v_cur;       // (no u_cur_i + border: the conversion saturates)
-    const float subpix_u = u_cur - u_cur_i;
-    const float subpix_v = v_cur - v_cur_i;
+    const float u_fl = floorf(u_cur), v_fl = floorf(v_cur);
+    const int u_cur_i = (int)u_fl;
+    const int v_cur_i = (int)v_fl;
+    // the reference's test u_cur_i >= 0 && u_cur_i - border >= 0 && u_cur_i < cols - border (and v alike, and neither position
+    // a NaN) on the floors themselves, which are integers in f32: four comparisons instead of nine.  A NaN fails them, and
+    // so does a position beyond the int range, as its saturated conversion did.
+    g.ok = visible && u_fl >= (float)border && v_fl >= (float)border && u_fl < colsf && v_fl < rowsf;
+    // (float)u_cur_i is u_fl again for every position that passes the test; the weights of the others are not used
+    const float subpix_u = u_cur - u_fl;
+    const float subpix_v = v_cur - v_fl;
     // (float)((1.0 - su) * (1.0 - sv)) of the reference, in f32: inside the image u_cur >= 3, so su = u_cur - floor(u_cur)
     // is a multiple of 2^-22 below 1, 1 - su is exact in f32 (<= 22 significant bits) and the product of two such
     // numbers (<= 44 bits, exact in f64) is rounded to f32 once on either path.  Outside the image the weights are not used.
     const float ou = 1.0f - subpix_u, ov = 1.0f - subpix_v;
-    g.w_tl = 0.5f * (ou * ov);
-    g.w_tr = 0.5f * (subpix_u * ov);
-    g.w_bl = 0.5f * (ou * subpix_v);
-    g.w_br = 0.5f * (subpix_u * subpix_v);
+    // halved once per axis: (0.5f * a) * b == 0.5f * (a * b) bit for bit (no operand is subnormal: multiples of 2^-22)
+    const float h_ou = 0.5f * ou, h_su = 0.5f * subpix_u;
+    g.w_tl = h_ou * ov;
+    g.w_tr = h_su * ov;
+    g.w_bl = h_ou * subpix_v;
+    g.w_br = h_su * subpix_v;
     g.off = g.ok ? (v_cur_i - 2) * stride + (u_cur_i - 2) : 0;
   }
   return g;
@@ -837,10 +850,11 @@ SVO_DEV double fused_tile_row(double x, double y, double z_inv, double jscale, d
 SVO_DEV void fused_ref_weights(float u_ref, float v_ref, int u_ref_i, int v_ref_i, float* w) {
   const float su = u_ref - u_ref_i, sv = v_ref - v_ref_i;
   const float ou = 1.0f - su, ov = 1.0f - sv;
-  w[0] = 0.5f * (ou * ov);
-  w[1] = 0.5f * (su * ov);
-  w[2] = 0.5f * (ou * sv);
-  w[3] = 0.5f * (su * sv);
+  const float h_ou = 0.5f * ou, h_su = 0.5f * su;      // (0.5f * a) * b == 0.5f * (a * b), see lpp_project
+  w[0] = h_ou * ov;
+  w[1] = h_su * ov;
+  w[2] = h_ou * sv;
+  w[3] = h_su * sv;
 }
 
 // the 32 interpolated values of a patch (6 x 6 without the corners) from its seven 8-byte footprint rows.  (The fused
@@ -955,6 +969,21 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
   const int favoured_tiles = (5 * my_tiles) / 8;                        // whole tiles at raised priority
   const int favoured_half = (5 * my_tiles) % 8 >= 4 ? favoured_tiles : -1;   // then the first half of this one
   auto tile_of = [&](int k) -> int { return k < my_tiles ? simd + 4 * (first_j + k) : n_tiles; };
+  // the priority schedule of a younger wave as ONE scalar (an older wave: 0): bit k = tile k starts at raised priority, bit
+  // 8 + k = at normal priority, bit 16 + k = it drops to normal half-way through tile k.  (Written as conditions on k, wave and
+  // favoured_* in the tile loop, the compiler kept one 64-bit lane mask per tile and condition alive across the whole
+  // kernel -- sixteen scalar registers that it spilled and restored inside the loop.)
+  // how many of the wave's tiles exist (they are the first ones): one scalar, compared with k in the loops
+  int n_have = 0;
+#pragma unroll
+  for (int k = 0; k < TPW; ++k) n_have += tile_of(k) < n_tiles ? 1 : 0;
+  n_have = __builtin_amdgcn_readfirstlane(n_have);
+  unsigned prio_plan = 0;
+  if (NW == 8 && wave >= 4) {
+#pragma unroll
+    for (int k = 0; k < TPW; ++k)
+      prio_plan |= ((k < favoured_tiles || k == favoured_half) ? 1u : 0x100u) << k | (k == favoured_half ? 0x10000u << k : 0u);
+  }
   // per-tile H row of this wave (lane e keeps entry e): in LDS, read once per tile and evaluation
   auto th_get = [&](int k) -> double { return lane < 21 ? s_th[(wave * TPW + k) * ROWW + lane] : 0.0; };
   auto th_set = [&](int k, double v) { if (lane < 21) s_th[(wave * TPW + k) * ROWW + lane] = v; };
@@ -1003,9 +1032,14 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
     const int cols = lv.cols[level], rows = lv.rows[level], stride = cols;
     const uint8_t* ref_img = ref_base + (size_t)b * pyr_bytes + lv.ref_off[level];
     const uint8_t* cur_img = cur_base + (size_t)b * pyr_bytes + lv.cur_off[level];
-    const float scale = 1.0f / (1 << level);
-    const double jscale = fabs(cam.fx) / (1 << level);
+    const float scale = __int_as_float((127 - level) << 23);           // 1.0f / (1 << level), formed by the scalar unit
     const int border = 3;
+    // wave-uniform values of the level that the tile loop reads: in scalar registers, not one vector register each
+    const float colsf = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)(cols - border))));
+    const float rowsf = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)(rows - border))));
+    const double jscale_v = fabs(cam.fx) / (1 << level);
+    const double jscale = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(jscale_v)),
+                                           __builtin_amdgcn_readfirstlane(__double2loint(jscale_v)));
     if (threadIdx.x == 0) {
       for (int i = 0; i < 7; ++i) s_old[i] = s_model[i];     // rollback copy (:33)
       s_iter = 0;
@@ -1149,6 +1183,13 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         T[i] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
                                 __builtin_amdgcn_readfirstlane(__double2loint(v)));
       }
+      double q2[3];                          // 2 q.xyz (exact), wave-uniform like T: see se3_act_q2
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double v = s_model[3 + i] + s_model[3 + i];
+        q2[i] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                                 __builtin_amdgcn_readfirstlane(__double2loint(v)));
+      }
       double accH = 0.0;
       unsigned gone_changed = 0;                              // bit k: tile k's outside-the-image set changed
       double accJ[6] = {0, 0, 0, 0, 0, 0};
@@ -1162,20 +1203,22 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
       float4 Wn[8];                                           // patches of the next tile, on their way from memory
       LppGeom gq[2];
       uint2 Crq[2][5];
-      gq[0] = lpp_project(T, cam, X[0], (fl[0] & F_VISIBLE) != 0, scale, cols, rows, stride);
+      gq[0] = lpp_project(T, q2, cam, X[0], (fl[0] & F_VISIBLE) != 0, scale, colsf, rowsf, stride);
       const int off0 = gq[0].off;
       if (__ballot(off0 != pf_off) == 0ull) {                 // wave-uniform
 #pragma unroll
         for (int j = 0; j < 5; ++j) Crq[0][j] = pf[j];
       } else {
 #pragma unroll
-        for (int j = 0; j < 5; ++j) Crq[0][j] = load_row8(cur_img + off0 + j * stride);
+        for (int j = 0; j < 5; ++j) Crq[0][j] = load_row8(cur_img + (unsigned)(off0 + j * stride));     // (offsets are >= 0: 32 bits on the scalar base)
       }
 #pragma unroll
       for (int k = 0; k < TPW; ++k) {
         const int tile = tile_of(k);
         // the younger wave of a SIMD is favoured by the arbiter during its first tiles (see tile_of)
-        if (NW == 8 && wave >= 4) { if (k < favoured_tiles || k == favoured_half) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+        unsigned prio = prio_plan;
+        if (TPW > 1) asm volatile("" : "+s"(prio));          // opaque: tested bit by bit here, nothing derived from it is kept
+        if (NW == 8) { if (prio & (1u << k)) __builtin_amdgcn_s_setprio(1); else if (prio & (0x100u << k)) __builtin_amdgcn_s_setprio(0); }
 
         // this tile's interpolated patches: from LDS, or what was asked for while the previous tile was computed
         float4 Wq[8];
@@ -1192,9 +1235,9 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
           for (int c4 = 0; c4 < 8; ++c4) Wq[c4] = Wn[c4];
         }
         if (k + 1 < TPW) {
-          gq[(k + 1) & 1] = lpp_project(T, cam, X[k + 1], (fl[k + 1] & F_VISIBLE) != 0, scale, cols, rows, stride);
+          gq[(k + 1) & 1] = lpp_project(T, q2, cam, X[k + 1], (fl[k + 1] & F_VISIBLE) != 0, scale, colsf, rowsf, stride);
 #pragma unroll
-          for (int j = 0; j < 5; ++j) Crq[(k + 1) & 1][j] = load_row8(cur_img + gq[(k + 1) & 1].off + j * stride);
+          for (int j = 0; j < 5; ++j) Crq[(k + 1) & 1][j] = load_row8(cur_img + (unsigned)(gq[(k + 1) & 1].off + j * stride));
           if (!Plan::in_lds(k + 1)) {
             const int tile_n = tile_of(k + 1) < n_tiles ? tile_of(k + 1) : (tile < n_tiles ? tile : 0);
             const float4* src = wmem + ((size_t)b * max_tiles + tile_n) * 8 * TILE + lane;
@@ -1204,7 +1247,9 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
             for (int c4 = 0; c4 < 8; ++c4) Wn[c4] = src[c4 * c4_stride];
           }
         }
-        if (tile >= n_tiles) continue;                       // wave-uniform: the tiles that follow do not exist either
+        int have = n_have;
+        if (TPW > 1) asm volatile("" : "+s"(have));          // opaque: one comparison per tile instead of a lane mask per tile kept alive
+        if (k >= have) continue;                             // wave-uniform (tile >= n_tiles): the tiles that follow do not exist either
         // ---- projection into the current image (:220-236): done one tile ahead
         const LppGeom g = gq[k & 1];
         const bool ok = g.ok;
@@ -1239,7 +1284,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
           }
 #pragma unroll
           for (int y = 0; y < 4; ++y) {
-            if (NW == 8 && y == 2 && k == favoured_half && wave >= 4) __builtin_amdgcn_s_setprio(0);
+            if (NW == 8 && y == 2 && (prio & (0x10000u << k))) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
               const float refv = W[y + 1][x + 1];                                  // half the reference value
@@ -1391,7 +1436,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
 
       pf_off = off0;
 #pragma unroll
-      for (int j = 0; j < 5; ++j) pf[j] = load_row8(cur_img + off0 + j * stride);
+      for (int j = 0; j < 5; ++j) pf[j] = load_row8(cur_img + (unsigned)(off0 + j * stride));
       // ---- wave reduction, then the waves in fixed order, then the solve on one lane
       // (TORD: the tiles' rows are in LDS already; wave 0 adds them in tile order after the barrier)
       if (!TORD) {
