@@ -116,7 +116,7 @@ struct LevelDims { int w[SVO_HIP_MAX_LEVELS]; };
 
 // ordered compaction of the winning corners (cell order, as the reference's for_each over `corners`), one workgroup
 __global__ __launch_bounds__(256) void detect_compact_kernel(const unsigned long long* __restrict__ cells, int n_cells,
-                                                             float threshold, LevelDims dims, Cam cam, int want_f,
+                                                             double threshold, LevelDims dims, Cam cam, int want_f,
                                                              int* __restrict__ n_out, double* __restrict__ px_out,
                                                              double* __restrict__ f_out, int* __restrict__ level_out,
                                                              float* __restrict__ score_out) {
@@ -131,7 +131,10 @@ __global__ __launch_bounds__(256) void detect_compact_kernel(const unsigned long
     bool keep = false;
     if (k < n_cells) {
       key = cells[k];
-      keep = (double)__uint_as_float((unsigned)(key >> 32)) > (double)threshold;            // :115
+      // :117 tests the float score against the caller's double.  A cell that kept its initial key (score (float)threshold,
+      // order 0) passes when the f32 rounding of the threshold lies above it, and decodes to the reference's
+      // Feature(px (0,0), level 0) of such a cell
+      keep = (double)__uint_as_float((unsigned)(key >> 32)) > threshold;
     }
     const unsigned long long m = __ballot(keep);
     const int before = __popcll(m & ((1ull << lane) - 1ull));
@@ -191,6 +194,7 @@ int svo_hip_detect_features_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, in
   SVO_REQUIRE(ctx, n_out_dev && px_dev && level_dev);
   SVO_REQUIRE(ctx, !f_dev || cam);
   SVO_REQUIRE(ctx, (size_t)pyr->width * pyr->height < (1u << 24));
+  SVO_REQUIRE(ctx, !(detection_threshold < 0.0));               // the cells' keys order non-negative floats only (NaN: no feature)
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
   int gc = 0, gr = 0;
   svo_hip_detect_grid(pyr->width, pyr->height, cell_size, &gc, &gr);
@@ -202,7 +206,9 @@ int svo_hip_detect_features_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, in
   if (rc != SVO_HIP_OK) return rc;
   unsigned long long* cells = reinterpret_cast<unsigned long long*>(ws);
   uint8_t* score = reinterpret_cast<uint8_t*>(cells + n_cells);
-  const float thr = (float)detection_threshold;                 // Corner::score is a float (I/feature_detection.h:34)
+  // Corner::score is a float (I/feature_detection.h:34).  -0.0 becomes +0.0: with the sign bit set the initial key of a cell
+  // would lie above every score's
+  const float thr = detection_threshold == 0.0 ? 0.0f : (float)detection_threshold;
   hipLaunchKernelGGL(cell_init_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, ctx->stream, cells, n_cells, thr);
   const uint8_t* base = pyr->base + (size_t)slot * pyr->pyr_bytes;
   LevelDims dims;
@@ -220,8 +226,8 @@ int svo_hip_detect_features_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, in
   Cam c;
   memset(&c, 0, sizeof(c));
   if (cam) c = svo_make_cam(*cam);
-  hipLaunchKernelGGL(detect_compact_kernel, dim3(1), dim3(256), 0, ctx->stream, cells, n_cells, thr, dims, c, f_dev ? 1 : 0,
-                     n_out_dev, px_dev, f_dev, level_dev, score_dev);
+  hipLaunchKernelGGL(detect_compact_kernel, dim3(1), dim3(256), 0, ctx->stream, cells, n_cells, detection_threshold, dims, c,
+                     f_dev ? 1 : 0, n_out_dev, px_dev, f_dev, level_dev, score_dev);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   return SVO_HIP_OK;
 }
@@ -231,6 +237,7 @@ int svo_hip_detect_features(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int sl
                             int32_t* n_out, double* px, double* f, int32_t* level, float* score) {
   if (!ctx) return SVO_HIP_ERR_INVALID;
   SVO_REQUIRE(ctx, pyr && n_out && px && level && cell_size > 0);
+  SVO_REQUIRE(ctx, !(detection_threshold < 0.0));               // refused before the occupancy goes down
   int gc = 0, gr = 0;
   svo_hip_detect_grid(pyr->width, pyr->height, cell_size, &gc, &gr);
   const size_t nc = (size_t)gc * gr;

@@ -795,7 +795,11 @@ int svo_hip_ldlt6_solve_batch(svo_hip_ctx* ctx, int n, const double* H /*[n][36]
  * levels of pyramid slot `slot`, one corner per grid cell (cell_size level-0 pixels) chosen by vk::shiTomasiScore,
  * strictly above detection_threshold; cells flagged in occupancy[grid_rows*grid_cols] (setExistingFeatures) are
  * skipped.  Outputs in cell order (capacity = number of cells): px[n][2] level-0 pixel, optional f[n][3] =
- * cam->cam2world(px) (distortion-free cameras only), level[n], optional score[n]; *n_out = n. */
+ * cam->cam2world(px) (distortion-free cameras only), level[n], optional score[n]; *n_out = n.
+ * The final test is the reference's: the float score against the double detection_threshold.  Where the threshold's f32
+ * rounding lies above it (10.1, not 10.0), every cell without a winner yields the reference's Feature(px (0,0), level 0),
+ * with score (float)detection_threshold.  -0.0 counts as 0.0; NaN yields no feature.  A negative detection_threshold is
+ * refused with SVO_HIP_ERR_INVALID by both entry points before anything is launched. */
 int svo_hip_detect_grid(int width, int height, int cell_size, int* grid_cols, int* grid_rows);
 int svo_hip_detect_features_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam,
                                 int n_pyr_levels, int cell_size, const uint8_t* occupancy_dev,
