@@ -29,6 +29,7 @@
 #include <climits>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "svo_internal.h"
@@ -475,6 +476,44 @@ SVO_DEV void trk_replay_body(const TrkMap& m, const TrkPlan& pl, const TrkFeat& 
   }
 }
 
+// The value of a feature for key-point slot j (0: distance from the centre, smaller is better; 1..4: the quadrant products,
+// larger is better, -inf outside the quadrant -- the two left quadrants test x against cv as the reference does,
+// S/frame.cpp:133,142).  Shared by the re-selection after deletions and by the selection for a promoted keyframe.
+SVO_DEV double key_slot_value(int cu, int cv, int j, double x, double y) {
+  if (j == 0) return fmax(fabs(x - cu), fabs(y - cv));
+  const bool in = j == 1 ? (x >= cu && y >= cv) : j == 2 ? (x >= cu && y < cv) : j == 3 ? (x < cv && y < cv) : (x < cv && y >= cv);
+  return in ? (x - cu) * (y - cv) : -HUGE_VAL;
+}
+// a thread's running best of the five slots over the features it visits in ascending index: the first best index is kept
+struct KeyBest { double v[5]; int i[5]; };
+SVO_DEV void key_best_init(KeyBest& b) {
+#pragma unroll
+  for (int j = 0; j < 5; ++j) { b.v[j] = j == 0 ? HUGE_VAL : -HUGE_VAL; b.i[j] = INT_MAX; }
+}
+SVO_DEV void key_best_offer(KeyBest& b, int cu, int cv, int idx, double x, double y) {
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const double v = key_slot_value(cu, cv, j, x, y);
+    const bool better = j == 0 ? v < b.v[j] : v > b.v[j];
+    if (better) { b.v[j] = v; b.i[j] = idx; }
+  }
+}
+// slot j over the nt threads' bests: best value, lowest feature index on ties; false: no contender (a feature outside the
+// quadrant is none)
+SVO_DEV bool key_best_reduce(int j, const double* s_val, const int* s_idx, int nt, double* bv_out, int* bi_out) {
+  double bv = j == 0 ? HUGE_VAL : -HUGE_VAL;
+  int bi = INT_MAX;
+  for (int q = 0; q < nt; ++q) {
+    const double v = s_val[q];
+    const int i = s_idx[q];
+    if (i == INT_MAX) continue;
+    const bool better = j == 0 ? v < bv : v > bv;
+    if (better || (v == bv && i < bi)) { bv = v; bi = i; }
+  }
+  *bv_out = bv; *bi_out = bi;
+  return bi != INT_MAX && (j == 0 || bv > -HUGE_VAL);
+}
+
 // ---- Frame::removeKeyPoint / setKeyPoints (S/frame.cpp:83-165) for the keyframes that lost a key feature to a point the
 // reprojector deleted in the previous frame (Map::safeDeletePoint, S/map.cpp:78-88): one workgroup per keyframe.
 // A keyframe none of whose key features lost its point keeps its key features untouched, as in the reference (they are
@@ -493,13 +532,6 @@ __global__ __launch_bounds__(256) void trk_rekey_kernel(TrkMap m, int* __restric
       if (m.obs_kf[o] == k) { *x = m.obs_px[2 * (size_t)o]; *y = m.obs_px[2 * (size_t)o + 1]; return true; }
     return false;
   };
-  // value of a feature for slot j (0: distance from the centre, smaller is better; 1..4: the quadrant products, larger is
-  // better, -inf outside the quadrant -- the two left quadrants test x against cv as the reference does, S/frame.cpp:133,142)
-  auto slot_value = [&](int j, double x, double y) {
-    if (j == 0) return fmax(fabs(x - cu), fabs(y - cv));
-    const bool in = j == 1 ? (x >= cu && y >= cv) : j == 2 ? (x >= cu && y < cv) : j == 3 ? (x < cv && y < cv) : (x < cv && y >= cv);
-    return in ? (x - cu) * (y - cv) : -HUGE_VAL;
-  };
   if (t == 0) s_found = 0;
   __syncthreads();
   if (t < 5) {
@@ -508,44 +540,193 @@ __global__ __launch_bounds__(256) void trk_rekey_kernel(TrkMap m, int* __restric
     double x = 0, y = 0;
     const bool has = p >= 0 && px_in_kf(p, &x, &y);
     s_inc[t] = has ? p : -1;
-    s_inc_val[t] = has ? slot_value(t, x, y) : 0.0;
+    s_inc_val[t] = has ? key_slot_value(cu, cv, t, x, y) : 0.0;
   }
   __syncthreads();
   if (!s_found) return;                                                        // block-uniform
-  double best[5];
-  int best_j[5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) { best[j] = j == 0 ? HUGE_VAL : -HUGE_VAL; best_j[j] = INT_MAX; }
+  KeyBest best;
+  key_best_init(best);
   const int f0 = m.kf_ftr_offset[k], f1 = m.kf_ftr_offset[k + 1];
   for (int i = f0 + t; i < f1; i += nt) {                                      // ascending per thread: the first best index is kept
     const int p = m.kf_ftr_point[i];
     if (p < 0 || m.pt_unlinked[p]) continue;                                   // ftr->point == NULL
     double x, y;
     if (!px_in_kf(p, &x, &y)) continue;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const double v = slot_value(j, x, y);
-      const bool better = j == 0 ? v < best[j] : v > best[j];
-      if (better) { best[j] = v; best_j[j] = i; }
-    }
+    key_best_offer(best, cu, cv, i, x, y);
   }
 #pragma unroll
-  for (int j = 0; j < 5; ++j) { s_best_val[j][t] = best[j]; s_best_idx[j][t] = best_j[j]; }
+  for (int j = 0; j < 5; ++j) { s_best_val[j][t] = best.v[j]; s_best_idx[j][t] = best.i[j]; }
   __syncthreads();
   if (t < 5) {
-    double bv = t == 0 ? HUGE_VAL : -HUGE_VAL;
-    int bi = INT_MAX;
-    for (int q = 0; q < nt; ++q) {                                             // best value, lowest feature index on ties
-      const double v = s_best_val[t][q];
-      const int i = s_best_idx[t][q];
-      if (i == INT_MAX) continue;
-      const bool better = t == 0 ? v < bv : v > bv;
-      if (better || (v == bv && i < bi)) { bv = v; bi = i; }
-    }
+    double bv;
+    int bi;
+    const bool challenger = key_best_reduce(t, s_best_val[t], s_best_idx[t], nt, &bv, &bi);
     int winner = s_inc[t];
-    const bool challenger = bi != INT_MAX && (t == 0 || bv > -HUGE_VAL);       // (a feature outside the quadrant is no contender)
     if (challenger && (winner < 0 || (t == 0 ? bv < s_inc_val[t] : bv > s_inc_val[t]))) winner = m.kf_ftr_point[bi];
     kf_key_point[5 * k + t] = winner;
+  }
+}
+
+// ---- the map grows in place.  New point candidates (DepthFilter::updateSeeds :310-331 + MapPointCandidates::newCandidatePoint,
+// S/map.cpp:226-231): n records from one staged block go to the tails of the point, observation and candidate tables; no
+// entry that existed before is written.
+struct TrkCandRec { double pos[3], px[2], f[3], grad[2]; int kf, level, edgelet, obs; };    // obs: where its observation goes
+__global__ void trk_add_candidates_kernel(int n, const TrkCandRec* __restrict__ rec, int n_points, int n_cand, double* __restrict__ pt_pos,
+                                          int* __restrict__ pt_type, int* __restrict__ pt_n_failed, int* __restrict__ pt_n_succeeded,
+                                          uint8_t* __restrict__ pt_unlinked, int* __restrict__ pt_obs_offset, int* __restrict__ obs_kf,
+                                          double* __restrict__ obs_px, double* __restrict__ obs_f, int* __restrict__ obs_level,
+                                          uint8_t* __restrict__ obs_edgelet, double* __restrict__ obs_grad, int* __restrict__ cand_point) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const TrkCandRec r = rec[i];
+  const size_t p = (size_t)n_points + i;
+  pt_pos[3 * p] = r.pos[0]; pt_pos[3 * p + 1] = r.pos[1]; pt_pos[3 * p + 2] = r.pos[2];
+  pt_type[p] = TYPE_CANDIDATE; pt_n_failed[p] = 0; pt_n_succeeded[p] = 0; pt_unlinked[p] = 0;
+  if (p == 0) pt_obs_offset[0] = 0;                                            // (a map without points has no offsets yet)
+  pt_obs_offset[p + 1] = r.obs + (r.kf >= 0 ? 1 : 0);
+  cand_point[n_cand + i] = (int)p;
+  if (r.kf >= 0) {
+    const size_t o = (size_t)r.obs;
+    obs_kf[o] = r.kf;
+    obs_px[2 * o] = r.px[0]; obs_px[2 * o + 1] = r.px[1];
+    obs_f[3 * o] = r.f[0]; obs_f[3 * o + 1] = r.f[1]; obs_f[3 * o + 2] = r.f[2];
+    obs_level[o] = r.level; obs_edgelet[o] = r.edgelet ? 1 : 0;
+    obs_grad[2 * o] = r.grad[0]; obs_grad[2 * o + 1] = r.grad[1];
+  }
+}
+
+// ---- the tracked frame becomes keyframe n_kf (FrameHandlerMono::processFrame :267-276, map_.addKeyframe :312).  The tables
+// whose entries move are rebuilt into a second set the tracker swaps to: the observation CSR (Point::addFrameRef pushes the new
+// observation to the FRONT of Point::obs_, S/point.cpp:61-65), the keyframes' feature rows (the new keyframe's row, and the seed
+// features MapPointCandidates::addCandidatePointToFrame adds to the END of their keyframes' rows, S/map.cpp:236-254) and the
+// candidate list (compacted, order kept).  One workgroup.
+struct TrkGrow {
+  int* pt_obs_offset; int* obs_kf; double* obs_px; double* obs_f; int* obs_level; uint8_t* obs_edgelet; double* obs_grad;
+  int* kf_ftr_offset; int* kf_ftr_point; int* cand_point;
+  int* cand_seed;                // [max_candidates] scratch: -2 stays, -1 promoted without a seed observation, else its seed keyframe
+  int* cand_scan;                // [max_candidates + 1] scratch
+  int* out;                      // [4]: promoted candidates, n_ftr, n_obs, n_candidates afterwards
+};
+constexpr int TRK_MAX_FRAME_FEATURES = 2816;   // trk_check_config
+__global__ __launch_bounds__(TRK_THREADS) void trk_promote_kernel(TrkMap m, TrkGrow g, double* __restrict__ T_kf_w, double* __restrict__ T_slot_w,
+                                                                  int* __restrict__ kf_slot, int* __restrict__ kf_key_point, int* __restrict__ mark,
+                                                                  TrkFeat ft, TrkLast last, int n_feat, int slot, Cam cam) {
+  __shared__ int s_part[TRK_THREADS];
+  __shared__ int s_fscan[TRK_MAX_FRAME_FEATURES + 1];
+  __shared__ int s_best_idx[5][256];
+  __shared__ double s_best_val[5][256];
+  __shared__ int s_n_promoted;
+  const int t = threadIdx.x, nt = blockDim.x;
+  const int k = m.n_kf;
+  if (t == 0) s_n_promoted = 0;
+  // ---- the frame's features that still have a point (mark[p] = the feature), their rank in creation order
+  for (int p = t; p < m.n_points; p += nt) mark[p] = INT_MAX;
+  for (int i = t; i < n_feat; i += nt) s_fscan[i] = last.point[i] >= 0 ? 1 : 0;
+  __syncthreads();
+  for (int i = t; i < n_feat; i += nt) {
+    const int p = last.point[i];
+    if (p >= 0) atomicMin(&mark[p], i);
+  }
+  __syncthreads();
+  // ---- observations: every point's old range behind its new observation
+  for (int p = t; p < m.n_points; p += nt) g.pt_obs_offset[p] = m.pt_obs_offset[p + 1] - m.pt_obs_offset[p] + (mark[p] != INT_MAX ? 1 : 0);
+  __syncthreads();
+  block_exclusive_scan(g.pt_obs_offset, m.n_points, s_part);
+  block_exclusive_scan(s_fscan, n_feat, s_part);
+  for (int p = t; p < m.n_points; p += nt) {
+    size_t d = (size_t)g.pt_obs_offset[p];
+    const int i = mark[p];
+    if (i != INT_MAX) {
+      g.obs_kf[d] = k;
+      g.obs_px[2 * d] = ft.px[2 * i]; g.obs_px[2 * d + 1] = ft.px[2 * i + 1];
+      g.obs_f[3 * d] = ft.f[3 * i]; g.obs_f[3 * d + 1] = ft.f[3 * i + 1]; g.obs_f[3 * d + 2] = ft.f[3 * i + 2];
+      g.obs_level[d] = ft.level[i]; g.obs_edgelet[d] = ft.edgelet[i];
+      g.obs_grad[2 * d] = ft.grad[2 * i]; g.obs_grad[2 * d + 1] = ft.grad[2 * i + 1];
+      ++d;
+    }
+    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o, ++d) {
+      g.obs_kf[d] = m.obs_kf[o];
+      g.obs_px[2 * d] = m.obs_px[2 * o]; g.obs_px[2 * d + 1] = m.obs_px[2 * o + 1];
+      g.obs_f[3 * d] = m.obs_f[3 * o]; g.obs_f[3 * d + 1] = m.obs_f[3 * o + 1]; g.obs_f[3 * d + 2] = m.obs_f[3 * o + 2];
+      g.obs_level[d] = m.obs_level[o]; g.obs_edgelet[d] = m.obs_edgelet[o];
+      g.obs_grad[2 * d] = m.obs_grad[2 * o]; g.obs_grad[2 * d + 1] = m.obs_grad[2 * o + 1];
+    }
+  }
+  // ---- MapPointCandidates::addCandidatePointToFrame: a candidate the frame observes becomes a map point
+  for (int c = t; c < m.n_candidates; c += nt) {
+    const int p = m.cand_point[c];
+    const bool promoted = p >= 0 && mark[p] != INT_MAX;
+    int seed = -2;
+    if (promoted) {
+      const int o0 = m.pt_obs_offset[p], o1 = m.pt_obs_offset[p + 1];
+      seed = o1 > o0 ? m.obs_kf[o1 - 1] : -1;                                  // it->second->frame (none: that keyframe left the map)
+      m.pt_type[p] = TYPE_UNKNOWN; m.pt_n_failed[p] = 0;
+      atomicAdd(&s_n_promoted, 1);
+    }
+    g.cand_seed[c] = seed;
+    g.cand_scan[c] = p >= 0 && !promoted ? 1 : 0;
+  }
+  __syncthreads();
+  block_exclusive_scan(g.cand_scan, m.n_candidates, s_part);
+  for (int c = t; c < m.n_candidates; c += nt) {
+    const int p = m.cand_point[c];
+    if (p >= 0 && g.cand_seed[c] == -2) g.cand_point[g.cand_scan[c]] = p;
+  }
+  // ---- the keyframes' feature rows: the old row, then the promoted seeds of that keyframe in list order; the new keyframe's row
+  for (int kk = t; kk <= k; kk += nt) {
+    int cnt = s_fscan[n_feat];
+    if (kk < k) {
+      cnt = m.kf_ftr_offset[kk + 1] - m.kf_ftr_offset[kk];
+      for (int c = 0; c < m.n_candidates; ++c) cnt += g.cand_seed[c] == kk ? 1 : 0;
+    }
+    g.kf_ftr_offset[kk] = cnt;
+  }
+  __syncthreads();
+  block_exclusive_scan(g.kf_ftr_offset, k + 1, s_part);
+  for (int kk = 0; kk < k; ++kk) {
+    const int src = m.kf_ftr_offset[kk], len = m.kf_ftr_offset[kk + 1] - src, dst = g.kf_ftr_offset[kk];
+    for (int j = t; j < len; j += nt) g.kf_ftr_point[dst + j] = m.kf_ftr_point[src + j];
+  }
+  for (int kk = t; kk < k; kk += nt) {
+    int at = g.kf_ftr_offset[kk] + m.kf_ftr_offset[kk + 1] - m.kf_ftr_offset[kk];
+    for (int c = 0; c < m.n_candidates; ++c)
+      if (g.cand_seed[c] == kk) g.kf_ftr_point[at++] = m.cand_point[c];
+  }
+  {
+    const int base = g.kf_ftr_offset[k];
+    for (int i = t; i < n_feat; i += nt) {
+      const int p = last.point[i];
+      if (p >= 0) g.kf_ftr_point[base + s_fscan[i]] = p;
+    }
+  }
+  // ---- Frame::setKeyPoints (S/frame.cpp:84-146) from five empty slots over the features with a point, in fts_ order
+  const int cu = cam.width / 2, cv = cam.height / 2;
+  if (t < 256) {
+    KeyBest best;
+    key_best_init(best);
+    for (int i = t; i < n_feat; i += 256)
+      if (last.point[i] >= 0) key_best_offer(best, cu, cv, i, ft.px[2 * i], ft.px[2 * i + 1]);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { s_best_val[j][t] = best.v[j]; s_best_idx[j][t] = best.i[j]; }
+  }
+  __syncthreads();
+  if (t < 5) {
+    double bv;
+    int bi;
+    const bool challenger = key_best_reduce(t, s_best_val[t], s_best_idx[t], 256, &bv, &bi);
+    kf_key_point[5 * k + t] = challenger ? last.point[bi] : -1;
+  }
+  if (t < 7) {                                                                  // the pose as the frame left it
+    const double v = last.T_f_w[t];
+    T_kf_w[7 * (size_t)k + t] = v;
+    T_slot_w[7 * (size_t)slot + t] = v;
+  }
+  if (t == 0) {
+    kf_slot[k] = slot;
+    g.out[0] = s_n_promoted;
+    g.out[1] = g.kf_ftr_offset[k + 1];
+    g.out[2] = g.pt_obs_offset[m.n_points];
+    g.out[3] = g.cand_scan[m.n_candidates];
   }
 }
 
@@ -769,6 +950,11 @@ struct svo_hip_tracker {
       *pt_n_succeeded = nullptr, *pt_obs_offset = nullptr, *obs_kf = nullptr, *obs_level = nullptr, *cand_point = nullptr;
   uint8_t *pt_unlinked = nullptr, *obs_edgelet = nullptr;
   int n_kf = 0, n_points = 0, n_candidates = 0;
+  int n_ftr = 0, n_obs = 0;                 // entries of kf_ftr_point / of the observation tables
+  std::vector<int> kf_slot_host;            // kf_slot as the device holds it (svo_hip_tracker_promote_last_frame checks against it)
+  int track_n_points = 0;                   // n_points when the last frame was tracked: the layout of the counters in the result block
+  TrkGrow grow{};                           // the second set of tables a promotion rebuilds into (allocated by the first one)
+  bool have_grow = false;
   bool have_map = false, have_last = false;
   bool rekey_pending = false;               // the last frame deleted points: keyframes that lost a key feature choose again before the next frame
   int last_n_host = 0;
@@ -1094,6 +1280,8 @@ int svo_hip_tracker_set_map(svo_hip_tracker* t, const svo_hip_tracker_map* mp) {
   if (e == hipSuccess && P) e = hipMemsetAsync(t->pt_unlinked, 0, P, ctx->stream);
   if (e != hipSuccess) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, "svo_hip_tracker_set_map", hipGetErrorString(e));
   t->n_kf = mp->n_kf; t->n_points = mp->n_points; t->n_candidates = mp->n_candidates;
+  t->n_ftr = n_ftr; t->n_obs = n_obs;
+  t->kf_slot_host.assign(mp->kf_slot, mp->kf_slot + mp->n_kf);
   t->any_edgelet = false;
   if (mp->obs_edgelet) for (int o = 0; o < n_obs && !t->any_edgelet; ++o) t->any_edgelet = mp->obs_edgelet[o] != 0;
   t->have_map = true; t->rekey_pending = false;
@@ -1212,7 +1400,7 @@ static void trk_copy_out(svo_hip_tracker* t, svo_hip_track_result* result, doubl
   if (feat_point) memcpy(feat_point, rh + t->o_point, nf * 4);
   if (feat_edgelet) memcpy(feat_edgelet, rh + t->o_edge, nf);
   if (feat_grad) memcpy(feat_grad, rh + t->o_grad, nf * 16);
-  const size_t np4 = (size_t)t->n_points * 4;
+  const size_t np4 = (size_t)t->track_n_points * 4;    // (the map may have gained points since: svo_hip_tracker_add_candidates)
   if (pt_type) memcpy(pt_type, rh + t->o_pt, np4);
   if (pt_n_failed) memcpy(pt_n_failed, rh + t->o_pt + np4, np4);
   if (pt_n_succeeded) memcpy(pt_n_succeeded, rh + t->o_pt + 2 * np4, np4);
@@ -1351,6 +1539,7 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
     svo_hip_tracker* t = sh->members[(size_t)k];
     const svo_hip_track_result* r = reinterpret_cast<const svo_hip_track_result*>(t->res_host);
     t->last_n_host = r->n_features;
+    t->track_n_points = t->n_points;
     t->last_from_track = true;
     t->need_gather = false;
     if (r->map_changed) t->rekey_pending = true;
@@ -1465,6 +1654,167 @@ int svo_hip_tracker_download_key_points(svo_hip_tracker* t, int32_t* kf_key_poin
     SVO_CHECK_HIP(ctx, hipMemcpyAsync(kf_key_point, t->kf_key_point, (size_t)t->n_kf * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
+  return SVO_HIP_OK;
+}
+
+// the pending re-selection of key points (the last frame deleted points), before anything reads or extends the feature rows
+static int trk_rekey_now(svo_hip_tracker* t) {
+  svo_hip_ctx* ctx = t->ctx;
+  if (t->rekey_pending && t->n_kf > 0) {
+    hipLaunchKernelGGL(trk_rekey_kernel, dim3(t->n_kf), dim3(256), 0, ctx->stream, make_map(t), t->kf_key_point, svo_make_cam(t->cam));
+    SVO_CHECK_HIP(ctx, hipGetLastError());
+  }
+  t->rekey_pending = false;
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_add_candidates(svo_hip_tracker* t, int n, const double* pos, const int32_t* kf_index, const double* px, const double* f,
+                                   const int32_t* level, const uint8_t* edgelet, const double* grad, int32_t* first_point) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  const svo_hip_tracker_config& c = t->cfg;
+  SVO_REQUIRE(ctx, n >= 0 && (n == 0 || (pos && kf_index && px && f && level)));
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_add_candidates", "no map has been set");
+  // every index and every capacity, before anything is enqueued
+  SVO_REQUIRE(ctx, n <= c.max_points - t->n_points && n <= c.max_candidates - t->n_candidates);
+  int n_new_obs = 0;
+  bool edge = false;
+  for (int i = 0; i < n; ++i) {
+    SVO_REQUIRE(ctx, kf_index[i] >= -1 && kf_index[i] < t->n_kf && level[i] >= 0 && level[i] < c.n_levels);
+    if (kf_index[i] >= 0) { ++n_new_obs; edge = edge || (edgelet && edgelet[i]); }
+  }
+  SVO_REQUIRE(ctx, n_new_obs <= c.max_obs - t->n_obs);
+  if (first_point) *first_point = t->n_points;
+  if (n == 0) return SVO_HIP_OK;
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)n * sizeof(TrkCandRec);
+  char* d = nullptr;
+  char* hs = nullptr;
+  int rc = svo_ctx_staging(ctx, bytes, &d);
+  if (rc == SVO_HIP_OK) rc = svo_ctx_host_staging(ctx, bytes, &hs);
+  if (rc != SVO_HIP_OK) return rc;
+  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the staging area may still feed an earlier transfer
+  TrkCandRec* rec = reinterpret_cast<TrkCandRec*>(hs);
+  int at = t->n_obs;
+  for (int i = 0; i < n; ++i) {
+    TrkCandRec r;
+    memset(&r, 0, sizeof(r));
+    memcpy(r.pos, pos + 3 * (size_t)i, 24); memcpy(r.px, px + 2 * (size_t)i, 16); memcpy(r.f, f + 3 * (size_t)i, 24);
+    if (grad) memcpy(r.grad, grad + 2 * (size_t)i, 16); else { r.grad[0] = 1.0; r.grad[1] = 0.0; }
+    r.kf = kf_index[i]; r.level = level[i]; r.edgelet = edgelet && edgelet[i] ? 1 : 0; r.obs = at;
+    if (r.kf >= 0) ++at;
+    rec[i] = r;
+  }
+  SVO_CHECK_HIP(ctx, hipMemcpyAsync(d, hs, bytes, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(trk_add_candidates_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, reinterpret_cast<const TrkCandRec*>(d),
+                     t->n_points, t->n_candidates, t->pt_pos, t->pt_type, t->pt_n_failed, t->pt_n_succeeded, t->pt_unlinked, t->pt_obs_offset,
+                     t->obs_kf, t->obs_px, t->obs_f, t->obs_level, t->obs_edgelet, t->obs_grad, t->cand_point);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  // existing indices keep their meaning: the last frame, the solver's copy of it and a pending re-selection stay as they are
+  t->n_points += n; t->n_candidates += n; t->n_obs = at;
+  t->any_edgelet = t->any_edgelet || edge;
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_promote_last_frame(svo_hip_tracker* t, int slot, int* kf_index, int* n_promoted_candidates) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  const svo_hip_tracker_config& c = t->cfg;
+  const char* who = "svo_hip_tracker_promote_last_frame";
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no map has been set");
+  // a frame from svo_hip_tracker_set_last_frame has no levels, edgelet flags or gradients
+  if (!t->have_last || !t->last_from_track) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "the last frame has to be a tracked one");
+  SVO_REQUIRE(ctx, slot >= 0 && slot < c.max_keyframes && t->n_kf < c.max_keyframes);
+  for (int k = 0; k < t->n_kf; ++k) SVO_REQUIRE(ctx, t->kf_slot_host[(size_t)k] != slot);
+  // the frame's features with a point, from the page-locked result block; every one is a new observation and a row entry of
+  // the new keyframe.  The promoted candidates add one row entry each at most, and each of them is one of those features:
+  // min(features with a point, candidates) bounds what the rows can gain beyond that.
+  const int n_feat = t->last_n_host;
+  const int32_t* fp = reinterpret_cast<const int32_t*>(t->res_host + t->o_point);
+  int n_with_point = 0;
+  for (int i = 0; i < n_feat; ++i) n_with_point += fp[i] >= 0 ? 1 : 0;
+  const int seeds_bound = n_with_point < t->n_candidates ? n_with_point : t->n_candidates;
+  SVO_REQUIRE(ctx, n_with_point <= c.max_obs - t->n_obs && n_with_point + seeds_bound <= c.max_kf_features - t->n_ftr);
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  if (!t->have_grow) {                      // the second set of tables, at the capacities of the first
+    TrkGrow g;
+    memset(&g, 0, sizeof(g));
+    int rc = SVO_HIP_OK;
+    std::vector<void*> got;
+    auto D = [&](auto** p, size_t count) {
+      if (rc != SVO_HIP_OK) return;
+      rc = trk_alloc(ctx, p, count);
+      if (rc == SVO_HIP_OK) got.push_back((void*)*p);
+    };
+    const size_t K = c.max_keyframes, P = c.max_points, O = c.max_obs, F = c.max_kf_features, CN = c.max_candidates > 0 ? c.max_candidates : 1;
+    D(&g.pt_obs_offset, P + 1); D(&g.obs_kf, O); D(&g.obs_px, O * 2); D(&g.obs_f, O * 3); D(&g.obs_level, O); D(&g.obs_edgelet, O);
+    D(&g.obs_grad, O * 2); D(&g.kf_ftr_offset, K + 2); D(&g.kf_ftr_point, F); D(&g.cand_point, CN); D(&g.cand_seed, CN); D(&g.cand_scan, CN + 1);
+    D(&g.out, 4);
+    if (rc != SVO_HIP_OK) { for (void* p : got) (void)hipFree(p); return rc; }
+    for (void* p : got) t->dev_allocs.push_back(p);
+    t->grow = g; t->have_grow = true;
+  }
+  int rc = trk_rekey_now(t);                // (the re-selection owed to the last frame's deletions sees the rows as they were)
+  if (rc != SVO_HIP_OK) return rc;
+  rc = svo_hip_tracker_keyframe_from_last_frame(t, slot);
+  if (rc != SVO_HIP_OK) return rc;
+  hipLaunchKernelGGL(trk_promote_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, make_map(t), t->grow, t->T_kf_w, t->T_slot_w, t->kf_slot,
+                     t->kf_key_point, t->pl.first_seq, t->ft, t->last, n_feat, slot, svo_make_cam(t->cam));
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  int out[4] = {0, 0, 0, 0};
+  SVO_CHECK_HIP(ctx, hipMemcpyAsync(out, t->grow.out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
+  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // the rebuilt tables are the map's from here on
+  TrkGrow& g = t->grow;
+  std::swap(t->pt_obs_offset, g.pt_obs_offset); std::swap(t->obs_kf, g.obs_kf); std::swap(t->obs_px, g.obs_px); std::swap(t->obs_f, g.obs_f);
+  std::swap(t->obs_level, g.obs_level); std::swap(t->obs_edgelet, g.obs_edgelet); std::swap(t->obs_grad, g.obs_grad);
+  std::swap(t->kf_ftr_offset, g.kf_ftr_offset); std::swap(t->kf_ftr_point, g.kf_ftr_point); std::swap(t->cand_point, g.cand_point);
+  if (kf_index) *kf_index = t->n_kf;
+  if (n_promoted_candidates) *n_promoted_candidates = out[0];
+  t->kf_slot_host.push_back(slot);
+  t->n_kf += 1; t->n_ftr = out[1]; t->n_obs = out[2]; t->n_candidates = out[3];
+  if (!t->any_edgelet) {                    // the new observations carry the frame's edgelet flags
+    const uint8_t* fe = reinterpret_cast<const uint8_t*>(t->res_host + t->o_edge);
+    for (int i = 0; i < n_feat && !t->any_edgelet; ++i) t->any_edgelet = fp[i] >= 0 && fe[i] != 0;
+  }
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_map_sizes(const svo_hip_tracker* t, int* n_kf, int* n_ftr, int* n_points, int* n_obs, int* n_candidates) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  if (!t->have_map) return svo_fail(t->ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_map_sizes", "no map has been set");
+  if (n_kf) *n_kf = t->n_kf;
+  if (n_ftr) *n_ftr = t->n_ftr;
+  if (n_points) *n_points = t->n_points;
+  if (n_obs) *n_obs = t->n_obs;
+  if (n_candidates) *n_candidates = t->n_candidates;
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_download_map(svo_hip_tracker* t, svo_hip_tracker_map_out* out) {
+  if (!t || !out) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_download_map", "no map has been set");
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  const int rc = trk_rekey_now(t);
+  if (rc != SVO_HIP_OK) return rc;
+  hipError_t e = hipSuccess;
+  auto get = [&](void* dst, const void* src, size_t bytes) {
+    if (dst && bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  };
+  const size_t K = (size_t)t->n_kf, P = (size_t)t->n_points, O = (size_t)t->n_obs;
+  out->n_kf = t->n_kf; out->n_points = t->n_points; out->n_candidates = t->n_candidates;
+  get(out->kf_slot, t->kf_slot, K * 4); get(out->T_kf_w, t->T_kf_w, K * 56); get(out->kf_key_point, t->kf_key_point, K * 20);
+  if (K) get(out->kf_ftr_offset, t->kf_ftr_offset, (K + 1) * 4);
+  get(out->kf_ftr_point, t->kf_ftr_point, (size_t)t->n_ftr * 4);
+  get(out->pt_pos, t->pt_pos, P * 24); get(out->pt_type, t->pt_type, P * 4); get(out->pt_n_failed, t->pt_n_failed, P * 4);
+  get(out->pt_n_succeeded, t->pt_n_succeeded, P * 4);
+  if (P) get(out->pt_obs_offset, t->pt_obs_offset, (P + 1) * 4);
+  get(out->obs_kf, t->obs_kf, O * 4); get(out->obs_px, t->obs_px, O * 16); get(out->obs_f, t->obs_f, O * 24); get(out->obs_level, t->obs_level, O * 4);
+  get(out->obs_edgelet, t->obs_edgelet, O); get(out->obs_grad, t->obs_grad, O * 16);
+  get(out->cand_point, t->cand_point, (size_t)t->n_candidates * 4);
+  if (e != hipSuccess) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, "svo_hip_tracker_download_map", hipGetErrorString(e));
+  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SVO_HIP_OK;
 }
 

@@ -908,6 +908,10 @@ class CTrackerMap(C.Structure):
                 ("n_candidates", C.c_int), ("cand_point", C.POINTER(C.c_int32))]
 
 
+class CTrackerMapOut(C.Structure):          # svo_hip_tracker_map_out: the same fields, buffers the library writes
+    _fields_ = CTrackerMap._fields_
+
+
 class CTrackResult(C.Structure):
     _fields_ = [("T_f_w", C.c_double * 7), ("T_f_w_sia", C.c_double * 7), ("sia_n_tracked", C.c_uint64),
                 ("sia_iters", C.c_int32 * MAX_LEVELS), ("sia_stop", C.c_int32), ("n_features", C.c_int32), ("n_matches", C.c_uint64),
@@ -992,6 +996,56 @@ class Tracker:
         self.ctx.sync()
         self.n_points = len(a["ty"])
 
+    def add_candidates(self, pos, kf_index, px, f, level, edgelet=None, grad=None) -> int:
+        """svo_hip_tracker_add_candidates: n converged seeds become point candidates at the tails of the device tables (no new
+        upload of the map, the last frame stays valid).  kf_index: the keyframe the seed's feature lies in, -1 = none left.
+        Returns the index of the first new point."""
+        I, D = C.c_int32, C.c_double
+        pp, kf, x, ff, lv = _f64(pos).reshape(-1, 3), np.ascontiguousarray(kf_index, dtype=np.int32), _f64(px).reshape(-1, 2), \
+            _f64(f).reshape(-1, 3), np.ascontiguousarray(level, dtype=np.int32)
+        n = len(kf)
+        assert len(pp) == len(x) == len(ff) == len(lv) == n
+        ed = None if edgelet is None else np.ascontiguousarray(edgelet, dtype=np.uint8)
+        gr = None if grad is None else _f64(grad).reshape(-1, 2)
+        assert (ed is None or len(ed) == n) and (gr is None or len(gr) == n)
+        first = C.c_int32(-1)
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_add_candidates(
+            self.h, n, _ptr(pp, D), _ptr(kf, I), _ptr(x, D), _ptr(ff, D), _ptr(lv, I), None if ed is None else _ptr(ed, C.c_uint8),
+            None if gr is None else _ptr(gr, D), C.byref(first)), "tracker_add_candidates")
+        self.n_points += n
+        return first.value
+
+    def promote_last_frame(self, slot: int):
+        """svo_hip_tracker_promote_last_frame: the last tracked frame becomes a keyframe of the device's map, pyramid in `slot`.
+        Returns (kf_index, n_promoted_candidates)."""
+        k, n = C.c_int(-1), C.c_int(-1)
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_promote_last_frame(self.h, int(slot), C.byref(k), C.byref(n)), "tracker_promote_last_frame")
+        return k.value, n.value
+
+    def map_sizes(self) -> dict:
+        """svo_hip_tracker_map_sizes: n_kf, n_ftr, n_points, n_obs, n_candidates of the tables the device holds"""
+        v = [C.c_int() for _ in range(5)]
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_map_sizes(self.h, *[C.byref(x) for x in v]), "tracker_map_sizes")
+        return dict(zip(("n_kf", "n_ftr", "n_points", "n_obs", "n_candidates"), (x.value for x in v)))
+
+    def download_map(self) -> dict:
+        """svo_hip_tracker_download_map: every table of the map as the device holds it now, in set_map's layout"""
+        z = self.map_sizes()
+        K, F, P, O, CN = z["n_kf"], z["n_ftr"], z["n_points"], z["n_obs"], z["n_candidates"]
+        i32, f64 = (lambda *sh: np.zeros(sh, np.int32)), (lambda *sh: np.zeros(sh, np.float64))
+        a = dict(kf_slot=i32(K), T_kf_w=f64(K, 7), kf_key_point=i32(K, 5), kf_ftr_offset=i32(K + 1), kf_ftr_point=i32(F), pt_pos=f64(P, 3),
+                 pt_type=i32(P), pt_n_failed=i32(P), pt_n_succeeded=i32(P), pt_obs_offset=i32(P + 1), obs_kf=i32(O), obs_px=f64(O, 2),
+                 obs_f=f64(O, 3), obs_level=i32(O), obs_edgelet=np.zeros(O, np.uint8), obs_grad=f64(O, 2), cand_point=i32(CN))
+        ptr = lambda k, t: _ptr(a[k], t) if a[k].size else None
+        I, D = C.c_int32, C.c_double
+        m = CTrackerMapOut(0, ptr("kf_slot", I), ptr("T_kf_w", D), ptr("kf_key_point", I), ptr("kf_ftr_offset", I), ptr("kf_ftr_point", I), 0,
+                           ptr("pt_pos", D), ptr("pt_type", I), ptr("pt_n_failed", I), ptr("pt_n_succeeded", I), ptr("pt_obs_offset", I),
+                           ptr("obs_kf", I), ptr("obs_px", D), ptr("obs_f", D), ptr("obs_level", I), ptr("obs_edgelet", C.c_uint8),
+                           ptr("obs_grad", D), 0, ptr("cand_point", I))
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_download_map(self.h, C.byref(m)), "tracker_download_map")
+        assert (m.n_kf, m.n_points, m.n_candidates) == (K, P, CN)
+        return dict(a, n_kf=K, n_points=P)
+
     def update_point_positions(self, point, pos):
         pt, pp = np.ascontiguousarray(point, dtype=np.int32), _f64(pos)
         self.ctx.check(self.ctx.lib.svo_hip_tracker_update_point_positions(self.h, len(pt), _ptr(pt, C.c_int32), _ptr(pp, C.c_double)),
@@ -1009,10 +1063,11 @@ class Tracker:
 
     def _outputs(self):
         nf = self.cfg.max_frame_features
-        if not hasattr(self, "_out") or len(self._out["pt_type"]) != max(self.n_points, 1):
+        npt = max(self.n_points, getattr(self, "_tracked_n_points", 0), 1)     # (last_result writes the tracked frame's count)
+        if not hasattr(self, "_out") or len(self._out["pt_type"]) != npt:
             self._out = dict(px=np.zeros((nf, 2)), f=np.zeros((nf, 3)), level=np.zeros(nf, np.int32), point=np.zeros(nf, np.int32),
-                             edgelet=np.zeros(nf, np.uint8), grad=np.zeros((nf, 2)), pt_type=np.zeros(max(self.n_points, 1), np.int32),
-                             pt_n_failed=np.zeros(max(self.n_points, 1), np.int32), pt_n_succeeded=np.zeros(max(self.n_points, 1), np.int32))
+                             edgelet=np.zeros(nf, np.uint8), grad=np.zeros((nf, 2)), pt_type=np.zeros(npt, np.int32),
+                             pt_n_failed=np.zeros(npt, np.int32), pt_n_succeeded=np.zeros(npt, np.int32))
         return self._out
 
     def track(self, img: np.ndarray, want_points: bool = True) -> dict:
@@ -1025,6 +1080,7 @@ class Tracker:
             self.h, _ptr(im, C.c_uint8), C.byref(res), _ptr(o["px"], D), _ptr(o["f"], D), _ptr(o["level"], I), _ptr(o["point"], I),
             _ptr(o["edgelet"], C.c_uint8), _ptr(o["grad"], D), _ptr(o["pt_type"], I) if want_points else None,
             _ptr(o["pt_n_failed"], I) if want_points else None, _ptr(o["pt_n_succeeded"], I) if want_points else None), "tracker_track")
+        self._tracked_n_points = self.n_points
         return self._as_dict(res, o)
 
     def last_result(self) -> dict:
@@ -1040,12 +1096,13 @@ class Tracker:
 
     def _as_dict(self, res, o) -> dict:
         n = res.n_features
+        npt = getattr(self, "_tracked_n_points", self.n_points)     # the counters cover the points the map had at track time
         return {"result": res, "T_f_w": np.array(res.T_f_w), "T_f_w_sia": np.array(res.T_f_w_sia), "n_matches": int(res.n_matches),
                 "n_trials": int(res.n_trials), "feat_px": o["px"][:n].copy(), "feat_f": o["f"][:n].copy(), "feat_level": o["level"][:n].copy(),
                 "feat_point": o["point"][:n].copy(), "feat_type": o["edgelet"][:n].astype(np.int32), "feat_grad": o["grad"][:n].copy(),
                 "overlap_kf": np.array(res.overlap_kf[:res.n_overlap]), "overlap_count": np.array(res.overlap_count[:res.n_overlap]),
-                "type": o["pt_type"][:self.n_points].copy(), "n_failed": o["pt_n_failed"][:self.n_points].copy(),
-                "n_succeeded": o["pt_n_succeeded"][:self.n_points].copy(), "map_changed": int(res.map_changed)}
+                "type": o["pt_type"][:npt].copy(), "n_failed": o["pt_n_failed"][:npt].copy(),
+                "n_succeeded": o["pt_n_succeeded"][:npt].copy(), "map_changed": int(res.map_changed)}
 
     def destroy(self):
         if self.h and not self._in_group:
@@ -1090,6 +1147,8 @@ class TrackerGroup:
             keep.append(im)
             self._ptrs[c] = im.ctypes.data_as(C.POINTER(C.c_uint8))
         self.ctx.check(self.ctx.lib.svo_hip_tracker_group_track(self.h, self._ptrs, self._res), "tracker_group_track")
+        for t in self.cameras:
+            t._tracked_n_points = t.n_points
         return [self._res[c] for c in range(self.n)]
 
     def destroy(self):

@@ -118,7 +118,10 @@ static svo_hip_tracker_config track_config(const std::vector<double>& m) {
   return cfg;
 }
 
-static int track_demo(const std::string& dir, const std::string& out, TrackerPort& port) {
+// incremental: FrameTracker::setIncrementalMap -- new candidates and a promoted keyframe reach the device in place, and the
+// promotion also runs MapPointCandidates::addCandidatePointToFrame (processFrame :276) on the objects.  times: the host-side
+// duration of every track() call in microseconds goes to times_track.bin.
+static int track_demo(const std::string& dir, const std::string& out, TrackerPort& port, bool incremental = false, bool times = false) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
   PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
   const int n_kf = (int)m[6], n_points = (int)m[7], n_obs = (int)m[8], n_cand = (int)m[10], n_frames = (int)m[11];
@@ -178,6 +181,8 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
 
   TrackerCamera& tracker = port.camera();
   if (!tracker.ok()) throw std::runtime_error("svo::FrameTracker: no device tracker");
+  tracker.setIncrementalMap(incremental);
+  std::vector<double> track_us;
 
   // the last frame: a keyframe of the map, or a frame of its own without features (SparseImgAlign::run then returns at once)
   const int last_kf = (int)m[17];
@@ -197,7 +202,9 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
     FramePtr cur = std::make_shared<Frame>(&cam, std::move(pyr));
     std::vector<std::pair<FramePtr, size_t>> overlap_kfs;
     FrameTracker::Outcome oc;
+    const auto t0 = std::chrono::steady_clock::now();
     if (!port.track(last, cur, map, overlap_kfs, oc)) throw std::runtime_error("svo::FrameTracker::track failed at frame " + std::to_string(k));
+    track_us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
     poses.insert(poses.end(), cur->T_f_w_.p, cur->T_f_w_.p + 7);
     stats.insert(stats.end(), {(double)cur->fts_.size(), (double)oc.repr_n_matches, (double)oc.repr_n_trials, (double)oc.img_align_n_tracked,
                                oc.pose_optimised ? 1.0 : 0.0, (double)oc.sfba_n_edges_final, oc.sfba_error_init, oc.sfba_error_final, (double)overlap_kfs.size()});
@@ -265,9 +272,11 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
       // keeps its pyramid; the tracker flattens the grown map before the next frame
       cur->setKeyframe();
       for (Feature* ftr : cur->fts_) if (ftr->point != nullptr) ftr->point->addFrameRef(ftr);
+      if (incremental) map.point_candidates_.addCandidatePointToFrame(cur);
       map.addKeyframe(cur);
       kfs.push_back(cur);
-      if (!tracker.lastFrameBecameKeyframe(*cur)) throw std::runtime_error("svo::FrameTracker::lastFrameBecameKeyframe failed");
+      if (!(incremental ? tracker.lastFrameBecameKeyframe(cur, map) : tracker.lastFrameBecameKeyframe(*cur)))
+        throw std::runtime_error("svo::FrameTracker::lastFrameBecameKeyframe failed");
     }
     last = cur;
   }
@@ -275,17 +284,18 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
   write_bin(out + "/track_stats.bin", stats);
   write_bin(out + "/track_uploads.bin", uploads);
   write_bin(out + "/track_overlap_first.bin", overlap);
+  if (times) write_bin(out + "/times_track.bin", track_us);
   if (port.lone) std::printf("svo_host_demo track OK\n");
   return 0;
 }
 
-static int track_lone(const std::string& dir, const std::string& out) {
+static int track_lone(const std::string& dir, const std::string& out, bool incremental, bool times) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
   PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
   FrameTracker tracker(cam, track_config(m));
   TrackerPort port;
   port.lone = &tracker;
-  return track_demo(dir, out, port);
+  return track_demo(dir, out, port, incremental, times);
 }
 
 // n copies of the world, one svo::FrameTrackerGroup: every world's outputs must equal the lone tracker's
@@ -413,7 +423,7 @@ static int churn_demo(const std::string& dir, const std::string& out) {
 }
 
 int main(int argc, char** argv) {
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track|churn]\n", argv[0]); return 2; }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times]|trackgroup n|churn]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {
@@ -433,7 +443,12 @@ int main(int argc, char** argv) {
   }
   if (argc > 3 && std::string(argv[3]) == "track") {
     try {
-      return track_lone(dir, out);
+      bool incremental = false, times = false;                                 // optional trailing arguments
+      for (int a = 4; a < argc; ++a) {
+        incremental = incremental || std::string(argv[a]) == "incremental";
+        times = times || std::string(argv[a]) == "times";
+      }
+      return track_lone(dir, out, incremental, times);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "svo_host_demo FAILED: %s\n", e.what());
       return 1;

@@ -216,6 +216,22 @@ struct MapPointCandidates {
   ~MapPointCandidates() {
     for (PointCandidate& c : candidates_) delete c.second;
   }
+  /// S/map.cpp:236-254: the candidates the new keyframe observes first become map points; their seed features join the
+  /// keyframes they were made in
+  template <class FramePtrT>
+  void addCandidatePointToFrame(const FramePtrT& frame) {
+    std::unique_lock<std::mutex> lock(mut_);
+    for (auto it = candidates_.begin(); it != candidates_.end();) {
+      if (!it->first->obs_.empty() && it->first->obs_.front()->frame == frame.get()) {
+        it->first->type_ = Point::TYPE_UNKNOWN;
+        it->first->n_failed_reproj_ = 0;
+        it->second->frame->addFeature(it->second);
+        it = candidates_.erase(it);
+      } else {
+        ++it;
+      }
+    }
+  }
   bool deleteCandidatePoint(Point* point) {                                      // S/map.cpp:256-269, :297-304
     std::unique_lock<std::mutex> lock(mut_);
     for (auto it = candidates_.begin(); it != candidates_.end(); ++it) {

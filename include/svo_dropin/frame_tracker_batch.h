@@ -81,6 +81,14 @@ class FrameTrackerT {
   bool ok() const { return trk_ != NULL; }
   /// how often the map has been flattened and uploaded (diagnostic)
   size_t mapUploads() const { return n_uploads_; }
+  /// Opt-in (default off): the two frame-rate changes of the map that otherwise flatten it again go to the device in place.
+  /// New point candidates (the depth filter's thread pushes them to the back of MapPointCandidates::candidates_) are appended
+  /// by prepare through svo_hip_tracker_add_candidates, and lastFrameBecameKeyframe(frame, map) promotes the tracked frame
+  /// with svo_hip_tracker_promote_last_frame.  Neither re-uploads the map or the last frame; when a device call refuses
+  /// (a capacity, a frame the tables do not hold) the bridge falls back to the full upload, so no frame is lost.  What still
+  /// needs mapChanged(): Map::safeDeleteFrame, MapPointCandidates::removeFrameCandidates, anything else that renumbers.
+  void setIncrementalMap(bool on) { incremental_ = on; }
+  bool incrementalMap() const { return incremental_; }
 
   /// page-locked buffer of one full-resolution image (svo_hip_tracker_image_buffer): a new frame whose level 0 lives there
   /// (cv::Mat(rows, cols, CV_8UC1, tracker.imageBuffer()) handed to the Frame constructor) is tracked without the copy of its
@@ -135,7 +143,8 @@ class FrameTrackerT {
       // the depth filter's thread adds candidates behind the tracker's back (its convergence callback is
       // MapPointCandidates::newCandidatePoint, frame_handler_mono.cpp:46-48): a list that has grown is flattened again
       std::unique_lock<std::mutex> lock(map.point_candidates_.mut_);
-      if (map.point_candidates_.candidates_.size() != n_candidates_) map_dirty_ = true;
+      const size_t n_now = map.point_candidates_.candidates_.size();
+      if (n_now != n_candidates_ && !(incremental_ && n_now > n_candidates_ && appendCandidates(map, n_now - n_candidates_))) map_dirty_ = true;
     }
     if (map_dirty_ && !uploadMap(map)) return false;
     if (!have_last_ && !uploadLastFrame(*last_frame)) return false;
@@ -248,6 +257,25 @@ class FrameTrackerT {
     map_dirty_ = true;
     return svo_hip_tracker_keyframe_from_last_frame(trk_, slot) == SVO_HIP_OK;
   }
+  /// The same with the map at hand: with setIncrementalMap(true) and a clean map the device promotes the frame itself
+  /// (svo_hip_tracker_promote_last_frame) and nothing is flattened.  Precondition: the caller has run processFrame :267-276
+  /// (setKeyframe, Point::addFrameRef for every feature with a point, addCandidatePointToFrame) and map_.addKeyframe on its
+  /// objects, and nothing else, since `frame` was tracked.  Otherwise, or when the device refuses, as lastFrameBecameKeyframe(frame).
+  bool lastFrameBecameKeyframe(const FramePtr& frame, Map& map) {
+    if (!trk_) return false;
+    if (!incremental_ || map_dirty_ || !have_last_) return lastFrameBecameKeyframe(*frame);
+    const int slot = freeSlot();
+    if (slot < 0) return false;
+    int kf_index = -1, n_promoted = 0;
+    if (svo_hip_tracker_promote_last_frame(trk_, slot, &kf_index, &n_promoted) != SVO_HIP_OK || kf_index != (int)keyframes_.size())
+      return lastFrameBecameKeyframe(*frame);                 // (a refused promotion changed nothing: the full upload follows)
+    slot_of_frame_[frame->id_] = slot;
+    index_of_frame_[frame->id_] = kf_index;
+    keyframes_.push_back(frame);
+    std::unique_lock<std::mutex> lock(map.point_candidates_.mut_);
+    n_candidates_ = map.point_candidates_.candidates_.size();
+    return true;
+  }
 
  private:
   /// lowest keyframe pyramid slot no known keyframe occupies, or -1
@@ -260,6 +288,40 @@ class FrameTrackerT {
   struct LastOptimLess {                                   // ptLastOptimComparator (frame_handler_base.cpp:181-184)
     bool operator()(const Point* a, const Point* b) const { return a->last_structure_optim_ < b->last_structure_optim_; }
   };
+  /// The last g entries of MapPointCandidates::candidates_ are new (only the depth filter's thread pushes back, and the
+  /// tracker's own deletions are counted already): their points and seed features go to the tails of the device tables.
+  /// The caller holds the list's lock.  false: nothing was sent, the map has to be flattened.
+  bool appendCandidates(Map& map, size_t g) {
+    typename Host::CandidateList& list = map.point_candidates_.candidates_;
+    typename Host::CandidateList::iterator it = list.end();
+    for (size_t i = 0; i < g; ++i) --it;
+    std::vector<double> pos, px, f, grad;
+    std::vector<int32_t> kf, level;
+    std::vector<uint8_t> edge;
+    std::vector<Point*> fresh;
+    for (; it != list.end(); ++it) {
+      Point* pt = it->first;
+      const Feature* ftr = it->second;
+      if (pt == NULL || ftr == NULL || index_of_point_.find(pt) != index_of_point_.end()) return false;
+      std::map<int, int>::const_iterator fi = index_of_frame_.find(ftr->frame->id_);
+      kf.push_back(fi == index_of_frame_.end() ? -1 : fi->second);       // -1: the seed's keyframe has left the map
+      pos.push_back(pt->pos_[0]); pos.push_back(pt->pos_[1]); pos.push_back(pt->pos_[2]);
+      px.push_back(ftr->px[0]); px.push_back(ftr->px[1]);
+      f.push_back(ftr->f[0]); f.push_back(ftr->f[1]); f.push_back(ftr->f[2]);
+      level.push_back(ftr->level);
+      edge.push_back(Host::isEdgelet(*ftr) ? 1 : 0);
+      grad.push_back(ftr->grad[0]); grad.push_back(ftr->grad[1]);
+      fresh.push_back(pt);
+    }
+    int32_t first = -1;
+    if (svo_hip_tracker_add_candidates(trk_, (int)fresh.size(), pos.data(), kf.data(), px.data(), f.data(), level.data(), edge.data(), grad.data(),
+                                       &first) != SVO_HIP_OK)
+      return false;
+    if (first != (int32_t)points_.size()) { map_dirty_ = true; return false; }   // (cannot happen: both sides count the same points)
+    for (size_t i = 0; i < fresh.size(); ++i) { index_of_point_[fresh[i]] = (int)points_.size(); points_.push_back(fresh[i]); }
+    n_candidates_ += g;
+    return true;
+  }
   bool uploadLastFrame(const Frame& last) {
     std::vector<double> px, f;
     std::vector<int32_t> pt;
@@ -296,7 +358,8 @@ class FrameTrackerT {
       slot_of_frame_.swap(live);
     }
     points_.clear(); index_of_point_.clear();
-    std::map<int, int> index_of_frame;
+    std::map<int, int>& index_of_frame = index_of_frame_;
+    index_of_frame.clear();
     std::vector<int32_t> kf_slot, key, ftr_off(1, 0), ftr_pt, ty, nf, ns, obs_off(1, 0), obs_kf, obs_level, cand;
     std::vector<double> T, pos, obs_px, obs_f, obs_grad;
     std::vector<uint8_t> obs_edge;
@@ -377,6 +440,8 @@ class FrameTrackerT {
   bool owns_trk_;
   svo_hip_tracker_config cfg_;
   bool map_dirty_, have_last_;
+  bool incremental_ = false;                                 // setIncrementalMap
+  std::map<int, int> index_of_frame_;                        // Frame::id_ -> keyframe index of the device tables
   size_t n_uploads_ = 0;
   size_t n_candidates_ = 0;                                  // MapPointCandidates::candidates_.size() as uploaded, minus our own deletions
   std::vector<FramePtr> keyframes_;

@@ -70,6 +70,8 @@ class FrameTracker : public FrameTrackerT<SvoTrackerHost> {
  public:
   explicit FrameTracker(vk::AbstractCamera* cam, int max_keyframes = 256)
       : FrameTrackerT<SvoTrackerHost>(toCamera(cam), SvoTrackerHost::config(max_keyframes)) {}
+  /// processFrame :330 with setIncrementalMap(true): the device promotes the tracked frame itself (the map is not flattened)
+  bool newKeyframe(const FramePtr& frame, Map& map) { return lastFrameBecameKeyframe(frame, map); }
 };
 
 /// Several FrameHandlerMono objects (cameras, or sequences replayed side by side) tracked together: one chain of launches per

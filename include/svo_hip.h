@@ -745,7 +745,8 @@ int svo_hip_tracker_set_sia_option(svo_hip_tracker* trk, int option, int value);
 /* One frame.  Outputs (host, any may be NULL except result): the new frame's features in creation order -- px[n][2],
  * f[n][3], level[n], point[n] (-1 where the pose refinement dropped the observation, pose_optimizer.cpp:154-157),
  * edgelet[n], grad[n][2], capacity max_frame_features -- and the point counters after the frame (capacity n_points of
- * the map).  Synchronises once. */
+ * the map).  The counter outputs cover the points the map had WHEN THE FRAME WAS TRACKED: svo_hip_tracker_last_result after
+ * svo_hip_tracker_add_candidates still returns that many.  Synchronises once. */
 int svo_hip_tracker_track(svo_hip_tracker* trk, const uint8_t* level0, svo_hip_track_result* result, double* feat_px,
                           double* feat_f, int32_t* feat_level, int32_t* feat_point, uint8_t* feat_edgelet, double* feat_grad,
                           int32_t* pt_type, int32_t* pt_n_failed, int32_t* pt_n_succeeded);
@@ -782,6 +783,70 @@ int svo_hip_tracker_group_track(svo_hip_tracker_group* group, const uint8_t* con
 int svo_hip_tracker_last_result(svo_hip_tracker* trk, svo_hip_track_result* result, double* feat_px, double* feat_f,
                                 int32_t* feat_level, int32_t* feat_point, uint8_t* feat_edgelet, double* feat_grad,
                                 int32_t* pt_type, int32_t* pt_n_failed, int32_t* pt_n_succeeded);
+
+/* ---- the map grows in place (opt-in; svo_hip_tracker_set_map keeps working as before).  Two things change the map at frame
+ * rate besides deletions and optimised positions: the depth filter converges seeds into point candidates, and the tracked
+ * frame becomes a keyframe.  Both extend the device tables without the host flattening its pointer graph again.  Point,
+ * keyframe and candidate indices that existed before keep their meaning, so the last frame stays valid across both calls.
+ * Both take a lone tracker's handle or a handle from svo_hip_tracker_group_camera.  What still needs svo_hip_tracker_set_map:
+ * Map::safeDeleteFrame, MapPointCandidates::removeFrameCandidates, anything else that renumbers keyframes or points.
+ *
+ * svo_hip_tracker_add_candidates: what DepthFilter::updateSeeds (depth_filter.cpp:310-331) and
+ * MapPointCandidates::newCandidatePoint (map.cpp:226-231) do for n converged seeds.  Host arrays: pos[n][3] the new points,
+ * kf_index[n] the keyframe INDEX the seed's feature lies in (-1: that keyframe has left the map -- the point gets no
+ * observation), px[n][2] / f[n][3] / level[n] / edgelet[n] (NULL: corners) / grad[n][2] (NULL: (1,0)) that feature.  The points
+ * get the indices n_points .. n_points + n - 1 (*first_point = the first, may be NULL), Point::TYPE_CANDIDATE, both counters
+ * 0; their observations go to the end of the observation tables and the points to the end of the candidate list, in argument
+ * order.  Every index and capacity (max_points, max_obs, max_candidates, level < n_levels, kf_index < n_kf) is checked on the
+ * host first: a refused call returns SVO_HIP_ERR_INVALID and changes nothing.  One packed transfer, one launch, no wait for
+ * the device beyond the re-use of the staging area. */
+int svo_hip_tracker_add_candidates(svo_hip_tracker* trk, int n, const double* pos, const int32_t* kf_index, const double* px,
+                                   const double* f, const int32_t* level, const uint8_t* edgelet, const double* grad,
+                                   int32_t* first_point);
+/* svo_hip_tracker_promote_last_frame: the last TRACKED frame becomes keyframe *kf_index = n_kf with its pyramid in `slot`
+ * (FrameHandlerMono::processFrame :267-276, map_.addKeyframe :312), from what the device holds of it:
+ *   - pose = the frame's T_f_w; pyramid kept as svo_hip_tracker_keyframe_from_last_frame keeps it;
+ *   - its features that still have a point form the keyframe's feature row in creation order, and each becomes an observation
+ *     at the FRONT of its point's list (Point::addFrameRef, point.cpp:61-65) with the feature's px, f, level, edgelet flag, grad;
+ *   - Frame::setKeyPoints (frame.cpp:84-146) over those features, from five empty slots;
+ *   - MapPointCandidates::addCandidatePointToFrame (map.cpp:236-254): every candidate the frame observes becomes TYPE_UNKNOWN
+ *     with n_failed_reproj_ = 0 and leaves the candidate list (compacted, order kept, entries that were -1 dropped); its seed
+ *     feature joins the END of its own keyframe's feature row, in list order (none when its kf_index was -1);
+ *     *n_promoted_candidates = how many.
+ * A re-selection of key points the last frame's deletions still owe is applied first, on the rows as they were.  Checked
+ * before anything is enqueued (SVO_HIP_ERR_INVALID, nothing changes): slot in range and held by no keyframe, n_kf <
+ * max_keyframes, room in max_obs for the features with a point and in max_kf_features for them plus min(them, n_candidates)
+ * seed features -- a worst-case bound, the real number is known only on the device.  SVO_HIP_ERR_STATE without a map or when
+ * the last frame was not tracked (one from svo_hip_tracker_set_last_frame has no levels).  Synchronises once. */
+int svo_hip_tracker_promote_last_frame(svo_hip_tracker* trk, int slot, int* kf_index, int* n_promoted_candidates);
+/* diagnostics and parity tests: the sizes of the tables the device holds, and the tables themselves in svo_hip_tracker_map's
+ * layout (the key points with the owed re-selections applied).  The caller's buffers hold at least the sizes
+ * svo_hip_tracker_map_sizes reports (kf_ftr_offset n_kf + 1, pt_obs_offset n_points + 1); a NULL pointer skips its table.
+ * n_kf / n_points / n_candidates are filled in.  svo_hip_tracker_download_map synchronises. */
+typedef struct {
+  int n_kf;
+  int32_t* kf_slot;
+  double* T_kf_w;
+  int32_t* kf_key_point;
+  int32_t* kf_ftr_offset;
+  int32_t* kf_ftr_point;
+  int n_points;
+  double* pt_pos;
+  int32_t* pt_type;
+  int32_t* pt_n_failed;
+  int32_t* pt_n_succeeded;
+  int32_t* pt_obs_offset;
+  int32_t* obs_kf;
+  double* obs_px;
+  double* obs_f;
+  int32_t* obs_level;
+  uint8_t* obs_edgelet;
+  double* obs_grad;
+  int n_candidates;
+  int32_t* cand_point;
+} svo_hip_tracker_map_out;
+int svo_hip_tracker_map_sizes(const svo_hip_tracker* trk, int* n_kf, int* n_ftr, int* n_points, int* n_obs, int* n_candidates);
+int svo_hip_tracker_download_map(svo_hip_tracker* trk, svo_hip_tracker_map_out* out);
 
 /* The 6x6 pivoted LDL^T solve both Gauss-Newton solvers use (x = H.ldlt().solve(b), Eigen 3.4 semantics incl. the
  * pseudo-inverse of D), n systems from host buffers: exposed so that the parity tests can show it is bit-identical
