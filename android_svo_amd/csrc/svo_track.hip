@@ -605,7 +605,9 @@ struct TrkGrow {
   int* kf_ftr_offset; int* kf_ftr_point; int* cand_point;
   int* cand_seed;                // [max_candidates] scratch: -2 stays, -1 promoted without a seed observation, else its seed keyframe
   int* cand_scan;                // [max_candidates + 1] scratch
-  int* out;                      // [4]: promoted candidates, n_ftr, n_obs, n_candidates afterwards
+  int* ftr_scan;                 // [max_kf_features + 1] scratch (trk_remove_kernel)
+  int* out;                      // [8]: promoted candidates (removal: deleted points), n_ftr, n_obs, n_candidates afterwards;
+                                 //      removal only: 4 deleted candidates
 };
 constexpr int TRK_MAX_FRAME_FEATURES = 2816;   // trk_check_config
 __global__ __launch_bounds__(TRK_THREADS) void trk_promote_kernel(TrkMap m, TrkGrow g, double* __restrict__ T_kf_w, double* __restrict__ T_slot_w,
@@ -727,6 +729,135 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_promote_kernel(TrkMap m, TrkG
     g.out[1] = g.kf_ftr_offset[k + 1];
     g.out[2] = g.pt_obs_offset[m.n_points];
     g.out[3] = g.cand_scan[m.n_candidates];
+  }
+}
+
+// rows first + 1 .. n_rows - 1 of an [n_rows][W] table move down by one row in place: every element is read, then -- behind
+// a barrier -- written.  A thread holds at most two (TRK_LDS_KF rows over TRK_THREADS threads).  Block-uniform call.
+template <typename T, int W>
+SVO_DEV void rows_move_down(T* a, int first, int n_rows) {
+  static_assert(TRK_LDS_KF * W <= 2 * TRK_THREADS, "two elements per thread cover the largest table");
+  const int t = threadIdx.x, nt = blockDim.x;
+  const int n = (n_rows - 1 - first) * W;
+  T* dst = a + (size_t)first * W;
+  T v0 = T(), v1 = T();
+  if (t < n) v0 = dst[t + W];
+  if (t + nt < n) v1 = dst[t + nt + W];
+  __syncthreads();
+  if (t < n) dst[t] = v0;
+  if (t + nt < n) dst[t + nt] = v1;
+}
+
+// ---- keyframe k leaves the map: Map::safeDeleteFrame (S/map.cpp:41-64) on the tables.  removePtFrameRef (:66-80) over the
+// keyframe's features that have a point: a point with at most two observations is deleted (safeDeletePoint :82-93, deletePoint
+// :95-99), any other loses its observation in k (Point::deleteFrameRef, S/point.cpp:75-86).  A point has one feature per keyframe
+// at most, so the decisions are independent.  removeFrameCandidates / deleteCandidate (:271-285, :297-304): the candidates whose
+// seed feature (the last observation of their range) lies in k are deleted.  The tables whose entries move are rebuilt into the
+// second set in the form a host flatten gives them: an unlinked point -- by this call or by an earlier frame -- has no
+// observations, is in no feature row and not in the candidate list; row order and observation order are kept, keyframes above k
+// move down by one.  The key points of the other keyframes are left to trk_rekey_kernel (the deleted points are unlinked).  A
+// feature of the last frame whose point was deleted here loses it (safeDeletePoint clears ftr->point of every observation).
+// One workgroup of TRK_THREADS; mark: per-point scratch.
+__global__ __launch_bounds__(TRK_THREADS) void trk_remove_kernel(TrkMap m, TrkGrow g, double* __restrict__ T_kf_w, int* __restrict__ kf_slot,
+                                                                 int* __restrict__ kf_key_point, int* __restrict__ mark, TrkLast last, int k, int n_ftr) {
+  __shared__ int s_part[TRK_THREADS];
+  __shared__ int s_del_points, s_del_cands;
+  const int t = threadIdx.x, nt = blockDim.x;
+  const int K = m.n_kf, P = m.n_points;
+  if (t == 0) { s_del_points = 0; s_del_cands = 0; }
+  for (int p = t; p < P; p += nt) mark[p] = 0;
+  __syncthreads();
+  // ---- the decisions: mark[p] = 1 deleted as a map point, 2 deleted as a candidate
+  const int r0 = m.kf_ftr_offset[k], r1 = m.kf_ftr_offset[k + 1];
+  for (int i = r0 + t; i < r1; i += nt) {
+    const int p = m.kf_ftr_point[i];
+    if (p < 0 || m.pt_unlinked[p]) continue;                                     // ftr->point == NULL
+    if (m.pt_obs_offset[p + 1] - m.pt_obs_offset[p] <= 2) mark[p] = 1;         // pt->obs_.size() <= 2
+  }
+  for (int c = t; c < m.n_candidates; c += nt) {
+    const int p = m.cand_point[c];
+    if (p < 0 || m.pt_unlinked[p]) continue;
+    const int o0 = m.pt_obs_offset[p], o1 = m.pt_obs_offset[p + 1];
+    if (o1 > o0 && m.obs_kf[o1 - 1] == k) mark[p] = 2;                           // it->second->frame == frame
+  }
+  __syncthreads();
+  // ---- the points: type and link, and what is left of every observation list
+  int n_dp = 0, n_dc = 0;
+  for (int p = t; p < P; p += nt) {
+    const int mk = mark[p];
+    bool gone = m.pt_unlinked[p] != 0;
+    if (mk) {
+      m.pt_type[p] = TYPE_DELETED; m.pt_unlinked[p] = 1;
+      gone = true;
+      if (mk == 1) ++n_dp; else ++n_dc;
+    }
+    int cnt = 0;
+    if (!gone)
+      for (int o = m.pt_obs_offset[p]; o < m.pt_obs_offset[p + 1]; ++o) cnt += m.obs_kf[o] != k ? 1 : 0;
+    g.pt_obs_offset[p] = cnt;
+  }
+  if (n_dp) atomicAdd(&s_del_points, n_dp);
+  if (n_dc) atomicAdd(&s_del_cands, n_dc);
+  __syncthreads();
+  block_exclusive_scan(g.pt_obs_offset, P, s_part);
+  for (int p = t; p < P; p += nt) {
+    if (m.pt_unlinked[p]) continue;
+    size_t d = (size_t)g.pt_obs_offset[p];
+    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o) {
+      const int kf = m.obs_kf[o];
+      if (kf == k) continue;
+      g.obs_kf[d] = kf > k ? kf - 1 : kf;
+      g.obs_px[2 * d] = m.obs_px[2 * o]; g.obs_px[2 * d + 1] = m.obs_px[2 * o + 1];
+      g.obs_f[3 * d] = m.obs_f[3 * o]; g.obs_f[3 * d + 1] = m.obs_f[3 * o + 1]; g.obs_f[3 * d + 2] = m.obs_f[3 * o + 2];
+      g.obs_level[d] = m.obs_level[o]; g.obs_edgelet[d] = m.obs_edgelet[o];
+      g.obs_grad[2 * d] = m.obs_grad[2 * o]; g.obs_grad[2 * d + 1] = m.obs_grad[2 * o + 1];
+      ++d;
+    }
+  }
+  // ---- the feature rows: row k goes, the others keep the entries that still have a point
+  for (int i = t; i < n_ftr; i += nt) {
+    const int p = m.kf_ftr_point[i];
+    g.ftr_scan[i] = (i < r0 || i >= r1) && p >= 0 && !m.pt_unlinked[p] ? 1 : 0;
+  }
+  __syncthreads();
+  block_exclusive_scan(g.ftr_scan, n_ftr, s_part);
+  for (int i = t; i < n_ftr; i += nt) {
+    const int p = m.kf_ftr_point[i];
+    if ((i < r0 || i >= r1) && p >= 0 && !m.pt_unlinked[p]) g.kf_ftr_point[g.ftr_scan[i]] = p;
+  }
+  for (int j = t; j < K; j += nt) g.kf_ftr_offset[j] = g.ftr_scan[m.kf_ftr_offset[j < k ? j : j + 1]];      // (K - 1 rows, K offsets)
+  // ---- the candidate list, compacted
+  for (int c = t; c < m.n_candidates; c += nt) {
+    const int p = m.cand_point[c];
+    g.cand_scan[c] = p >= 0 && !m.pt_unlinked[p] ? 1 : 0;
+  }
+  __syncthreads();
+  block_exclusive_scan(g.cand_scan, m.n_candidates, s_part);
+  for (int c = t; c < m.n_candidates; c += nt) {
+    const int p = m.cand_point[c];
+    if (p >= 0 && !m.pt_unlinked[p]) g.cand_point[g.cand_scan[c]] = p;
+  }
+  // ---- the keyframe tables
+  rows_move_down<double, 7>(T_kf_w, k, K);
+  rows_move_down<int, 5>(kf_key_point, k, K);
+  rows_move_down<int, 1>(kf_slot, k, K);
+  // ---- the last frame
+  const int n_last = *last.n;
+  for (int i = t; i < n_last; i += nt) {
+    const int p = last.point[i];
+    if (p < 0 || p >= P || !mark[p]) continue;
+    last.point[i] = -1;
+    if (i < last.sia_max_n) {                                                    // what the solver holds of a feature without a point
+      last.sia_has_point[i] = 0;
+      last.sia_pos[3 * i] = 0.0; last.sia_pos[3 * i + 1] = 0.0; last.sia_pos[3 * i + 2] = 1.0;
+    }
+  }
+  if (t == 0) {
+    g.out[0] = s_del_points;
+    g.out[1] = g.ftr_scan[n_ftr];
+    g.out[2] = g.pt_obs_offset[P];
+    g.out[3] = g.cand_scan[m.n_candidates];
+    g.out[4] = s_del_cands;
   }
 }
 
@@ -1716,6 +1847,38 @@ int svo_hip_tracker_add_candidates(svo_hip_tracker* t, int n, const double* pos,
   return SVO_HIP_OK;
 }
 
+// the second set of tables a promotion or a removal rebuilds into, at the capacities of the first: allocated by whichever runs first
+static int trk_grow_tables(svo_hip_tracker* t) {
+  if (t->have_grow) return SVO_HIP_OK;
+  svo_hip_ctx* ctx = t->ctx;
+  const svo_hip_tracker_config& c = t->cfg;
+  TrkGrow g;
+  memset(&g, 0, sizeof(g));
+  int rc = SVO_HIP_OK;
+  std::vector<void*> got;
+  auto D = [&](auto** p, size_t count) {
+    if (rc != SVO_HIP_OK) return;
+    rc = trk_alloc(ctx, p, count);
+    if (rc == SVO_HIP_OK) got.push_back((void*)*p);
+  };
+  const size_t K = c.max_keyframes, P = c.max_points, O = c.max_obs, F = c.max_kf_features, CN = c.max_candidates > 0 ? c.max_candidates : 1;
+  D(&g.pt_obs_offset, P + 1); D(&g.obs_kf, O); D(&g.obs_px, O * 2); D(&g.obs_f, O * 3); D(&g.obs_level, O); D(&g.obs_edgelet, O);
+  D(&g.obs_grad, O * 2); D(&g.kf_ftr_offset, K + 2); D(&g.kf_ftr_point, F); D(&g.cand_point, CN); D(&g.cand_seed, CN); D(&g.cand_scan, CN + 1);
+  D(&g.ftr_scan, F + 1); D(&g.out, 8);
+  if (rc != SVO_HIP_OK) { for (void* p : got) (void)hipFree(p); return rc; }
+  for (void* p : got) t->dev_allocs.push_back(p);
+  t->grow = g; t->have_grow = true;
+  return SVO_HIP_OK;
+}
+
+// the rebuilt tables are the map's from here on
+static void trk_swap_grown(svo_hip_tracker* t) {
+  TrkGrow& g = t->grow;
+  std::swap(t->pt_obs_offset, g.pt_obs_offset); std::swap(t->obs_kf, g.obs_kf); std::swap(t->obs_px, g.obs_px); std::swap(t->obs_f, g.obs_f);
+  std::swap(t->obs_level, g.obs_level); std::swap(t->obs_edgelet, g.obs_edgelet); std::swap(t->obs_grad, g.obs_grad);
+  std::swap(t->kf_ftr_offset, g.kf_ftr_offset); std::swap(t->kf_ftr_point, g.kf_ftr_point); std::swap(t->cand_point, g.cand_point);
+}
+
 int svo_hip_tracker_promote_last_frame(svo_hip_tracker* t, int slot, int* kf_index, int* n_promoted_candidates) {
   if (!t) return SVO_HIP_ERR_INVALID;
   svo_hip_ctx* ctx = t->ctx;
@@ -1736,25 +1899,9 @@ int svo_hip_tracker_promote_last_frame(svo_hip_tracker* t, int slot, int* kf_ind
   const int seeds_bound = n_with_point < t->n_candidates ? n_with_point : t->n_candidates;
   SVO_REQUIRE(ctx, n_with_point <= c.max_obs - t->n_obs && n_with_point + seeds_bound <= c.max_kf_features - t->n_ftr);
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  if (!t->have_grow) {                      // the second set of tables, at the capacities of the first
-    TrkGrow g;
-    memset(&g, 0, sizeof(g));
-    int rc = SVO_HIP_OK;
-    std::vector<void*> got;
-    auto D = [&](auto** p, size_t count) {
-      if (rc != SVO_HIP_OK) return;
-      rc = trk_alloc(ctx, p, count);
-      if (rc == SVO_HIP_OK) got.push_back((void*)*p);
-    };
-    const size_t K = c.max_keyframes, P = c.max_points, O = c.max_obs, F = c.max_kf_features, CN = c.max_candidates > 0 ? c.max_candidates : 1;
-    D(&g.pt_obs_offset, P + 1); D(&g.obs_kf, O); D(&g.obs_px, O * 2); D(&g.obs_f, O * 3); D(&g.obs_level, O); D(&g.obs_edgelet, O);
-    D(&g.obs_grad, O * 2); D(&g.kf_ftr_offset, K + 2); D(&g.kf_ftr_point, F); D(&g.cand_point, CN); D(&g.cand_seed, CN); D(&g.cand_scan, CN + 1);
-    D(&g.out, 4);
-    if (rc != SVO_HIP_OK) { for (void* p : got) (void)hipFree(p); return rc; }
-    for (void* p : got) t->dev_allocs.push_back(p);
-    t->grow = g; t->have_grow = true;
-  }
-  int rc = trk_rekey_now(t);                // (the re-selection owed to the last frame's deletions sees the rows as they were)
+  int rc = trk_grow_tables(t);
+  if (rc != SVO_HIP_OK) return rc;
+  rc = trk_rekey_now(t);                    // (the re-selection owed to the last frame's deletions sees the rows as they were)
   if (rc != SVO_HIP_OK) return rc;
   rc = svo_hip_tracker_keyframe_from_last_frame(t, slot);
   if (rc != SVO_HIP_OK) return rc;
@@ -1764,11 +1911,7 @@ int svo_hip_tracker_promote_last_frame(svo_hip_tracker* t, int slot, int* kf_ind
   int out[4] = {0, 0, 0, 0};
   SVO_CHECK_HIP(ctx, hipMemcpyAsync(out, t->grow.out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
   SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  // the rebuilt tables are the map's from here on
-  TrkGrow& g = t->grow;
-  std::swap(t->pt_obs_offset, g.pt_obs_offset); std::swap(t->obs_kf, g.obs_kf); std::swap(t->obs_px, g.obs_px); std::swap(t->obs_f, g.obs_f);
-  std::swap(t->obs_level, g.obs_level); std::swap(t->obs_edgelet, g.obs_edgelet); std::swap(t->obs_grad, g.obs_grad);
-  std::swap(t->kf_ftr_offset, g.kf_ftr_offset); std::swap(t->kf_ftr_point, g.kf_ftr_point); std::swap(t->cand_point, g.cand_point);
+  trk_swap_grown(t);
   if (kf_index) *kf_index = t->n_kf;
   if (n_promoted_candidates) *n_promoted_candidates = out[0];
   t->kf_slot_host.push_back(slot);
@@ -1777,6 +1920,35 @@ int svo_hip_tracker_promote_last_frame(svo_hip_tracker* t, int slot, int* kf_ind
     const uint8_t* fe = reinterpret_cast<const uint8_t*>(t->res_host + t->o_edge);
     for (int i = 0; i < n_feat && !t->any_edgelet; ++i) t->any_edgelet = fp[i] >= 0 && fe[i] != 0;
   }
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_remove_keyframe(svo_hip_tracker* t, int kf_index, int* slot_freed, int* n_deleted_points, int* n_deleted_candidates) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_remove_keyframe", "no map has been set");
+  // (the reference removes a keyframe only when Config::maxNKfs() > 2: the map never loses its only one)
+  SVO_REQUIRE(ctx, kf_index >= 0 && kf_index < t->n_kf && t->n_kf > 1);
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = trk_grow_tables(t);
+  if (rc != SVO_HIP_OK) return rc;
+  rc = trk_rekey_now(t);                    // (the re-selection owed to the last frame's deletions sees the rows as they were)
+  if (rc != SVO_HIP_OK) return rc;
+  hipLaunchKernelGGL(trk_remove_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, make_map(t), t->grow, t->T_kf_w, t->kf_slot, t->kf_key_point,
+                     t->pl.first_seq, t->last, kf_index, t->n_ftr);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  int out[5] = {0, 0, 0, 0, 0};
+  SVO_CHECK_HIP(ctx, hipMemcpyAsync(out, t->grow.out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
+  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  trk_swap_grown(t);
+  if (slot_freed) *slot_freed = t->kf_slot_host[(size_t)kf_index];
+  if (n_deleted_points) *n_deleted_points = out[0];
+  if (n_deleted_candidates) *n_deleted_candidates = out[4];
+  t->kf_slot_host.erase(t->kf_slot_host.begin() + kf_index);
+  t->n_kf -= 1; t->n_ftr = out[1]; t->n_obs = out[2]; t->n_candidates = out[3];
+  // the keyframes that lost a key feature to a point deleted here choose again (Frame::removeKeyPoint), on the new rows,
+  // before anything reads the key points
+  if (out[0] > 0) t->rekey_pending = true;
   return SVO_HIP_OK;
 }
 

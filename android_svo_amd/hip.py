@@ -1022,6 +1022,15 @@ class Tracker:
         self.ctx.check(self.ctx.lib.svo_hip_tracker_promote_last_frame(self.h, int(slot), C.byref(k), C.byref(n)), "tracker_promote_last_frame")
         return k.value, n.value
 
+    def remove_keyframe(self, kf_index: int) -> dict:
+        """svo_hip_tracker_remove_keyframe: keyframe kf_index leaves the device's map in place (Map::safeDeleteFrame on the
+        tables; later keyframes move down by one).  Returns dict(slot = the pyramid slot it held, n_deleted_points,
+        n_deleted_candidates)."""
+        s, p, c = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_remove_keyframe(self.h, int(kf_index), C.byref(s), C.byref(p), C.byref(c)),
+                       "tracker_remove_keyframe")
+        return dict(slot=s.value, n_deleted_points=p.value, n_deleted_candidates=c.value)
+
     def map_sizes(self) -> dict:
         """svo_hip_tracker_map_sizes: n_kf, n_ftr, n_points, n_obs, n_candidates of the tables the device holds"""
         v = [C.c_int() for _ in range(5)]

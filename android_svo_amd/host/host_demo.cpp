@@ -109,10 +109,11 @@ struct TrackerPort {
   }
 };
 
-static svo_hip_tracker_config track_config(const std::vector<double>& m) {
+static svo_hip_tracker_config track_config(const std::vector<double>& m, int max_kfs = 0) {
   svo_hip_tracker_config cfg;
   svo_hip_tracker_default_config(&cfg);
   cfg.max_keyframes = (int)m[6] + 2;                                          // room for a frame that becomes a keyframe
+  if (cfg.max_keyframes < max_kfs + 1) cfg.max_keyframes = max_kfs + 1;      // (the new keyframe joins before the furthest one leaves)
   cfg.grid_size = (int)m[12]; cfg.max_fts = (int)m[13]; cfg.quality_min_fts = (int)m[14];
   cfg.klt_min_level = (int)m[15]; cfg.max_frame_features = (int)m[16];
   return cfg;
@@ -120,8 +121,14 @@ static svo_hip_tracker_config track_config(const std::vector<double>& m) {
 
 // incremental: FrameTracker::setIncrementalMap -- new candidates and a promoted keyframe reach the device in place, and the
 // promotion also runs MapPointCandidates::addCandidatePointToFrame (processFrame :276) on the objects.  times: the host-side
-// duration of every track() call in microseconds goes to times_track.bin.
-static int track_demo(const std::string& dir, const std::string& out, TrackerPort& port, bool incremental = false, bool times = false) {
+// duration of every track() call in microseconds goes to times_track.bin.  kf_every E: not only the manifest's frame
+// keyframe_at becomes a keyframe but every E-th frame from it on.  max_kfs N (Config::maxNKfs(), > 2): once the map holds N
+// keyframes the one furthest from the new keyframe leaves first (processFrame :303-308: getFurthestKeyframe, safeDeleteFrame),
+// which reaches the device through FrameTracker::keyframeRemoved; full_remove: through mapChanged() instead (a full upload, the
+// yardstick).  A frame whose pose is NaN (tracking was lost) has no furthest keyframe, and the reference would let the map grow:
+// the demo stops there.  track_removed.bin: per frame, which keyframe left (in order of creation), or -1; track_map_size.bin: the map at the end.
+static int track_demo(const std::string& dir, const std::string& out, TrackerPort& port, bool incremental = false, bool times = false,
+                      int max_kfs = 0, bool full_remove = false, int kf_every = 0) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
   PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
   const int n_kf = (int)m[6], n_points = (int)m[7], n_obs = (int)m[8], n_cand = (int)m[10], n_frames = (int)m[11];
@@ -195,7 +202,8 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
     last = std::make_shared<Frame>(&cam, std::move(pyr));
     last->T_f_w_ = SE3(read_bin<double>(dir + "/last_pose.bin").data());
   }
-  std::vector<double> poses, stats, overlap, uploads;
+  std::vector<double> poses, stats, overlap, uploads, removed;
+  const int keyframe_at = m.size() > 19 ? (int)m[19] : -1;
   for (int k = 0; k < n_frames; ++k) {
     std::vector<std::vector<uint8_t>> pyr;
     pyr.push_back(read_bin<uint8_t>(dir + "/trk_frame_" + std::to_string(k) + ".bin"));
@@ -266,36 +274,57 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
       std::unique_lock<std::mutex> lock(map.point_candidates_.mut_);
       map.point_candidates_.candidates_.push_back(MapPointCandidates::PointCandidate(np_, nf));
     }
-    if (m.size() > 19 && (int)m[19] == k) {
+    removed.push_back(-1.0);
+    if (keyframe_at >= 0 && (k == keyframe_at || (kf_every > 0 && k > keyframe_at && (k - keyframe_at) % kf_every == 0))) {
       // FrameHandlerMono::processFrame :284-330: the tracked frame becomes a keyframe -- setKeyframe (key points), every feature
       // with a point becomes an observation of it (Point::addFrameRef: front of obs_), the map takes the frame, the device
       // keeps its pyramid; the tracker flattens the grown map before the next frame
       cur->setKeyframe();
       for (Feature* ftr : cur->fts_) if (ftr->point != nullptr) ftr->point->addFrameRef(ftr);
       if (incremental) map.point_candidates_.addCandidatePointToFrame(cur);
+      // a map that is full loses the keyframe furthest from the new one: chosen before the new one joins, as the reference does
+      FramePtr furthest;
+      if (max_kfs > 2 && (int)map.size() >= max_kfs) {
+        furthest = map.getFurthestKeyframe(cur->pos());
+        if (!furthest) throw std::runtime_error("no furthest keyframe at frame " + std::to_string(k) + ": the frame's pose is not a number, tracking was lost");
+      }
       map.addKeyframe(cur);
       kfs.push_back(cur);
       if (!(incremental ? tracker.lastFrameBecameKeyframe(cur, map) : tracker.lastFrameBecameKeyframe(*cur)))
         throw std::runtime_error("svo::FrameTracker::lastFrameBecameKeyframe failed");
+      if (furthest) {
+        for (size_t j = 0; j < kfs.size(); ++j) if (kfs[j] == furthest) removed.back() = (double)j;
+        map.safeDeleteFrame(furthest);
+        if (full_remove || !incremental) tracker.mapChanged();
+        else if (!tracker.keyframeRemoved(furthest, map)) throw std::runtime_error("svo::FrameTracker::keyframeRemoved failed");
+      }
     }
     last = cur;
   }
   write_bin(out + "/track_poses.bin", poses);
   write_bin(out + "/track_stats.bin", stats);
   write_bin(out + "/track_uploads.bin", uploads);
+  if (max_kfs > 0) {
+    write_bin(out + "/track_removed.bin", removed);
+    std::set<const Point*> seen;                                               // the map at the end: keyframes, features with a point, points, candidates
+    double n_ftr = 0;
+    for (const FramePtr& kf : map.keyframes_)
+      for (const Feature* ftr : kf->fts_) if (ftr->point) { ++n_ftr; seen.insert(ftr->point); }
+    write_bin(out + "/track_map_size.bin", std::vector<double>{(double)map.size(), n_ftr, (double)seen.size(), (double)map.point_candidates_.candidates_.size()});
+  }
   write_bin(out + "/track_overlap_first.bin", overlap);
   if (times) write_bin(out + "/times_track.bin", track_us);
   if (port.lone) std::printf("svo_host_demo track OK\n");
   return 0;
 }
 
-static int track_lone(const std::string& dir, const std::string& out, bool incremental, bool times) {
+static int track_lone(const std::string& dir, const std::string& out, bool incremental, bool times, int max_kfs, bool full_remove, int kf_every) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
   PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
-  FrameTracker tracker(cam, track_config(m));
+  FrameTracker tracker(cam, track_config(m, max_kfs));
   TrackerPort port;
   port.lone = &tracker;
-  return track_demo(dir, out, port, incremental, times);
+  return track_demo(dir, out, port, incremental, times, max_kfs, full_remove, kf_every);
 }
 
 // n copies of the world, one svo::FrameTrackerGroup: every world's outputs must equal the lone tracker's
@@ -423,7 +452,7 @@ static int churn_demo(const std::string& dir, const std::string& out) {
 }
 
 int main(int argc, char** argv) {
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times]|trackgroup n|churn]\n", argv[0]); return 2; }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove]|trackgroup n|churn]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {
@@ -443,12 +472,16 @@ int main(int argc, char** argv) {
   }
   if (argc > 3 && std::string(argv[3]) == "track") {
     try {
-      bool incremental = false, times = false;                                 // optional trailing arguments
+      bool incremental = false, times = false, full_remove = false;            // optional trailing arguments
+      int max_kfs = 0, kf_every = 0;
       for (int a = 4; a < argc; ++a) {
         incremental = incremental || std::string(argv[a]) == "incremental";
         times = times || std::string(argv[a]) == "times";
+        full_remove = full_remove || std::string(argv[a]) == "full_remove";
+        if (std::string(argv[a]) == "max_kfs" && a + 1 < argc) max_kfs = std::atoi(argv[++a]);
+        else if (std::string(argv[a]) == "kf_every" && a + 1 < argc) kf_every = std::atoi(argv[++a]);
       }
-      return track_lone(dir, out, incremental, times);
+      return track_lone(dir, out, incremental, times, max_kfs, full_remove, kf_every);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "svo_host_demo FAILED: %s\n", e.what());
       return 1;

@@ -87,6 +87,7 @@ struct PinholeCamera {            // vk::PinholeCamera: pinhole + optional 5-coe
 };
 
 struct Feature;
+struct Frame;
 struct Point {                                      // I/point.h: position + the features that observe it
   enum PointType { TYPE_DELETED, TYPE_CANDIDATE, TYPE_UNKNOWN, TYPE_GOOD };      // I/point.h:33-38
   Vector3d pos_;
@@ -97,8 +98,8 @@ struct Point {                                      // I/point.h: position + the
   explicit Point(const Vector3d& p) : pos_(p) {}
   Point(const Vector3d& p, Feature* ftr) : pos_(p) { obs_.push_front(ftr); }     // S/point.cpp:39-48
   void addFrameRef(Feature* ftr) { obs_.push_front(ftr); }                       // S/point.cpp:52-55
+  bool deleteFrameRef(const Frame* frame);                                       // S/point.cpp:75-86
 };
-struct Frame;
 struct Feature {
   enum FeatureType { CORNER, EDGELET };                                          // I/feature.h:26-29
   FeatureType type = CORNER;
@@ -106,6 +107,12 @@ struct Feature {
   Vector2d grad{{1.0, 0.0}};                                                     // edgelets: direction of the gradient, normalised
   Feature(Frame* fr, const Vector2d& px_, const Vector3d& f_, int lvl) : frame(fr), px(px_), f(f_), level(lvl), point(nullptr) {}
 };
+/// the point's observation made in `frame` leaves the list (false: it had none there)
+inline bool Point::deleteFrameRef(const Frame* frame) {
+  for (auto it = obs_.begin(); it != obs_.end(); ++it)
+    if ((*it)->frame == frame) { obs_.erase(it); return true; }
+  return false;
+}
 
 struct Frame {
   static int frame_counter_;
@@ -120,6 +127,7 @@ struct Frame {
   Frame(const PinholeCamera* cam, std::vector<std::vector<uint8_t>> pyr) : id_(frame_counter_++), cam_(cam), img_pyr_(std::move(pyr)) {}
   ~Frame() { for (Feature* f : fts_) delete f; }
   bool isKeyframe() const { return is_keyframe_; }
+  Vector3d pos() const { const SE3 T_w_f = T_f_w_.inverse(); return Vector3d{{T_w_f.p[0], T_w_f.p[1], T_w_f.p[2]}}; }   // I/frame.h: the camera centre
   void setKeyframe() { is_keyframe_ = true; setKeyPoints(); }                    // S/frame.cpp:67-71
   void addFeature(Feature* ftr) { fts_.push_back(ftr); }                         // :75-78
 
@@ -244,6 +252,18 @@ struct MapPointCandidates {
     }
     return false;
   }
+  /// S/map.cpp:271-285, :297-304: the candidates whose seed feature was made in `frame` go with it
+  template <class FramePtrT>
+  void removeFrameCandidates(const FramePtrT& frame) {
+    std::unique_lock<std::mutex> lock(mut_);
+    for (auto it = candidates_.begin(); it != candidates_.end();) {
+      if (it->second->frame != frame.get()) { ++it; continue; }
+      delete it->second;
+      it->first->type_ = Point::TYPE_DELETED;
+      trash_points_.push_back(it->first);
+      it = candidates_.erase(it);
+    }
+  }
 };
 
 /// I/map.h:69-130: keyframes + the candidates; points are owned through the features that refer to them
@@ -258,6 +278,42 @@ struct Map {
     for (Feature* ftr : pt->obs_) { ftr->point = nullptr; ftr->frame->removeKeyPoint(ftr); }
     pt->obs_.clear();
     deletePoint(pt);
+  }
+  size_t size() const { return keyframes_.size(); }
+  /// :66-80: a feature of a keyframe that leaves lets go of its point; a point that two features saw at most goes with it,
+  /// any other forgets the keyframe
+  void removePtFrameRef(Frame* frame, Feature* ftr) {
+    Point* pt = ftr->point;
+    if (pt == nullptr) return;                     // (gone with an earlier deletion)
+    ftr->point = nullptr;
+    if (pt->obs_.size() <= 2) { safeDeletePoint(pt); return; }
+    pt->deleteFrameRef(frame);
+    frame->removeKeyPoint(ftr);
+  }
+  /// :41-64: the keyframe leaves the map, its candidates with it (false: the map did not hold it)
+  bool safeDeleteFrame(FramePtr frame) {
+    bool found = false;
+    for (auto it = keyframes_.begin(); it != keyframes_.end(); ++it) {
+      if (*it != frame) continue;
+      for (Feature* ftr : frame->fts_) removePtFrameRef(frame.get(), ftr);
+      keyframes_.erase(it);
+      found = true;
+      break;
+    }
+    point_candidates_.removeFrameCandidates(frame);
+    return found;
+  }
+  /// :156-169: the keyframe whose camera centre is furthest from pos (none: no keyframe lies away from it)
+  FramePtr getFurthestKeyframe(const Vector3d& pos) const {
+    FramePtr furthest;
+    double maxdist = 0.0;
+    for (const FramePtr& kf : keyframes_) {
+      const Vector3d c = kf->pos();
+      const double d[3] = {c[0] - pos[0], c[1] - pos[1], c[2] - pos[2]};
+      const double dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+      if (dist > maxdist) { maxdist = dist; furthest = kf; }
+    }
+    return furthest;
   }
 };
 

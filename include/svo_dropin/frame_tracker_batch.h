@@ -81,12 +81,13 @@ class FrameTrackerT {
   bool ok() const { return trk_ != NULL; }
   /// how often the map has been flattened and uploaded (diagnostic)
   size_t mapUploads() const { return n_uploads_; }
-  /// Opt-in (default off): the two frame-rate changes of the map that otherwise flatten it again go to the device in place.
+  /// Opt-in (default off): the frame-rate changes of the map that otherwise flatten it again go to the device in place.
   /// New point candidates (the depth filter's thread pushes them to the back of MapPointCandidates::candidates_) are appended
-  /// by prepare through svo_hip_tracker_add_candidates, and lastFrameBecameKeyframe(frame, map) promotes the tracked frame
-  /// with svo_hip_tracker_promote_last_frame.  Neither re-uploads the map or the last frame; when a device call refuses
-  /// (a capacity, a frame the tables do not hold) the bridge falls back to the full upload, so no frame is lost.  What still
-  /// needs mapChanged(): Map::safeDeleteFrame, MapPointCandidates::removeFrameCandidates, anything else that renumbers.
+  /// by prepare through svo_hip_tracker_add_candidates, lastFrameBecameKeyframe(frame, map) promotes the tracked frame
+  /// with svo_hip_tracker_promote_last_frame, and keyframeRemoved(frame, map) follows Map::safeDeleteFrame with
+  /// svo_hip_tracker_remove_keyframe.  None re-uploads the map or the last frame; when a device call refuses (a capacity, a
+  /// frame the tables do not hold) the bridge falls back to the full upload, so no frame is lost.  What still needs
+  /// mapChanged(): anything else that renumbers keyframes or points.
   void setIncrementalMap(bool on) { incremental_ = on; }
   bool incrementalMap() const { return incremental_; }
 
@@ -274,6 +275,45 @@ class FrameTrackerT {
     keyframes_.push_back(frame);
     std::unique_lock<std::mutex> lock(map.point_candidates_.mut_);
     n_candidates_ = map.point_candidates_.candidates_.size();
+    return true;
+  }
+
+  /// Map::safeDeleteFrame(frame) has taken a keyframe out of the map (FrameHandlerMono::processFrame :303-308).  Precondition:
+  /// the caller has run it on its objects, and nothing else since the last device call.  With setIncrementalMap(true), a clean
+  /// map and a keyframe the tables hold, the device removes it in place (svo_hip_tracker_remove_keyframe): the keyframes behind
+  /// it move down by one, its pyramid slot is free again, the points and candidates the host's call deleted are forgotten here
+  /// as apply() forgets them.  Otherwise, when the device refuses, or when it deleted another number of points or candidates
+  /// than the host did, as mapChanged(): the map is flattened again before the next frame.  false: no tracker.
+  bool keyframeRemoved(const FramePtr& frame, Map& map) {
+    if (!trk_) return false;
+    std::map<int, int>::iterator fi = index_of_frame_.find(frame->id_);
+    std::map<int, int>::iterator si = slot_of_frame_.find(frame->id_);
+    if (!incremental_ || map_dirty_ || fi == index_of_frame_.end() || si == slot_of_frame_.end()) { mapChanged(); return true; }
+    const int k = fi->second;
+    int slot = -1, n_points = 0, n_cands = 0;
+    if (svo_hip_tracker_remove_keyframe(trk_, k, &slot, &n_points, &n_cands) != SVO_HIP_OK) { mapChanged(); return true; }
+    // what the host's call deleted: the points of the tables that are TYPE_DELETED now, the entries its candidate list lost
+    size_t n_deleted = 0, n_list = 0;
+    for (size_t p = 0; p < points_.size(); ++p) n_deleted += points_[p] != NULL && points_[p]->type_ == Point::TYPE_DELETED ? 1 : 0;
+    {
+      std::unique_lock<std::mutex> lock(map.point_candidates_.mut_);
+      n_list = map.point_candidates_.candidates_.size();
+    }
+    if (slot != si->second || n_list > n_candidates_ || (size_t)n_cands != n_candidates_ - n_list || (size_t)(n_points + n_cands) != n_deleted) {
+      mapChanged();                                            // (the two sides disagree: the full upload puts the device right)
+      return true;
+    }
+    keyframes_.erase(keyframes_.begin() + k);
+    slot_of_frame_.erase(si);
+    index_of_frame_.erase(fi);
+    for (std::map<int, int>::iterator it = index_of_frame_.begin(); it != index_of_frame_.end(); ++it) if (it->second > k) --it->second;
+    for (size_t p = 0; p < points_.size(); ++p) {
+      Point* pt = points_[p];
+      if (pt == NULL || pt->type_ != Point::TYPE_DELETED) continue;
+      index_of_point_.erase(pt);                               // (the map's trash owns the object; the index stays taken)
+      points_[p] = NULL;
+    }
+    n_candidates_ = n_list;
     return true;
   }
 

@@ -72,6 +72,8 @@ class FrameTracker : public FrameTrackerT<SvoTrackerHost> {
       : FrameTrackerT<SvoTrackerHost>(toCamera(cam), SvoTrackerHost::config(max_keyframes)) {}
   /// processFrame :330 with setIncrementalMap(true): the device promotes the tracked frame itself (the map is not flattened)
   bool newKeyframe(const FramePtr& frame, Map& map) { return lastFrameBecameKeyframe(frame, map); }
+  /// processFrame :307 with setIncrementalMap(true): map_.safeDeleteFrame(frame) has run, the device removes the keyframe in place
+  bool keyframeLeft(const FramePtr& frame, Map& map) { return keyframeRemoved(frame, map); }
 };
 
 /// Several FrameHandlerMono objects (cameras, or sequences replayed side by side) tracked together: one chain of launches per

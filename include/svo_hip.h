@@ -788,8 +788,11 @@ int svo_hip_tracker_last_result(svo_hip_tracker* trk, svo_hip_track_result* resu
  * rate besides deletions and optimised positions: the depth filter converges seeds into point candidates, and the tracked
  * frame becomes a keyframe.  Both extend the device tables without the host flattening its pointer graph again.  Point,
  * keyframe and candidate indices that existed before keep their meaning, so the last frame stays valid across both calls.
- * Both take a lone tracker's handle or a handle from svo_hip_tracker_group_camera.  What still needs svo_hip_tracker_set_map:
- * Map::safeDeleteFrame, MapPointCandidates::removeFrameCandidates, anything else that renumbers keyframes or points.
+ * Both take a lone tracker's handle or a handle from svo_hip_tracker_group_camera.  A keyframe leaves the map in place too
+ * (svo_hip_tracker_remove_keyframe below).  Nothing renumbers POINTS in place: a deleted point keeps its index and its rows of the
+ * pt_* tables, so n_points only grows; when svo_hip_tracker_add_candidates is refused for max_points, a svo_hip_tracker_set_map
+ * of the flattened map compacts them.  What still needs svo_hip_tracker_set_map: anything that renumbers points, or
+ * keyframes in another way than that removal.
  *
  * svo_hip_tracker_add_candidates: what DepthFilter::updateSeeds (depth_filter.cpp:310-331) and
  * MapPointCandidates::newCandidatePoint (map.cpp:226-231) do for n converged seeds.  Host arrays: pos[n][3] the new points,
@@ -819,6 +822,35 @@ int svo_hip_tracker_add_candidates(svo_hip_tracker* trk, int n, const double* po
  * seed features -- a worst-case bound, the real number is known only on the device.  SVO_HIP_ERR_STATE without a map or when
  * the last frame was not tracked (one from svo_hip_tracker_set_last_frame has no levels).  Synchronises once. */
 int svo_hip_tracker_promote_last_frame(svo_hip_tracker* trk, int slot, int* kf_index, int* n_promoted_candidates);
+/* svo_hip_tracker_remove_keyframe: keyframe kf_index leaves the device's map in place -- what Map::safeDeleteFrame
+ * (map.cpp:41-64) does to the objects, with removePtFrameRef (:66-80), safeDeletePoint (:82-93), deletePoint (:95-99),
+ * Point::deleteFrameRef (point.cpp:75-86) and MapPointCandidates::removeFrameCandidates / deleteCandidate (map.cpp:271-285,
+ * :297-304).  FrameHandlerMono::processFrame (:303-308) makes this call after every new keyframe once the map holds
+ * Config::maxNKfs() of them.  Takes a lone tracker's handle or a handle from svo_hip_tracker_group_camera.
+ *   - A feature of the keyframe "has a point" when its point is not unlinked.  Such a point with at most two observations (all
+ *     keyframes counted, this one included) is deleted: TYPE_DELETED, unlinked, no observations; *n_deleted_points = how
+ *     many.  Any other loses its observation in the keyframe; the order of the rest, its counters and type stay.
+ *   - A candidate whose seed feature (the last observation of its range) lies in the keyframe becomes TYPE_DELETED and
+ *     unlinked and leaves the candidate list; *n_deleted_candidates = how many.  Candidates without an observation stay.
+ *   - Row kf_index of kf_slot, T_kf_w, kf_key_point and of the feature rows disappears, later keyframes move down by one,
+ *     every obs_kf above kf_index is decremented.  *slot_freed = the pyramid slot the keyframe held: free for the next
+ *     promotion or upload.
+ *   - The tables are left in the form a host flatten under the same point numbering writes: an unlinked point -- by this call
+ *     or by an earlier frame -- has an empty observation range, is in no feature row and not in the candidate list (-1
+ *     entries are dropped); row order and per-point observation order are kept.  n_ftr, n_obs and n_candidates of
+ *     svo_hip_tracker_map_sizes are exact afterwards.
+ *   - Key points: a re-selection the last frame's deletions still owe is applied first, on the rows as they were.  A keyframe
+ *     that lost a key feature to a point deleted here chooses again before anything reads its key points, once, with
+ *     Frame::removeKeyPoint's rule (the reference chooses again at every deletion: the outcomes differ only on exact ties
+ *     of slot values); every other keyframe keeps its incumbents.
+ *   - A feature of the device's last frame whose point was deleted here loses it (point -1; the solver skips it), as
+ *     safeDeletePoint clears ftr->point of every observation.  The page-locked result block of the last tracked frame is not
+ *     rewritten: svo_hip_tracker_last_result keeps returning the frame as it was tracked.
+ * No table grows, so there is no capacity check.  Refused before anything is enqueued, nothing changes: SVO_HIP_ERR_STATE
+ * without a map; SVO_HIP_ERR_INVALID for kf_index outside [0, n_kf) or a map of one keyframe (the reference removes only when
+ * Config::maxNKfs() > 2).  Outputs may be NULL.  One launch, synchronises once. */
+int svo_hip_tracker_remove_keyframe(svo_hip_tracker* trk, int kf_index, int* slot_freed, int* n_deleted_points,
+                                    int* n_deleted_candidates);
 /* diagnostics and parity tests: the sizes of the tables the device holds, and the tables themselves in svo_hip_tracker_map's
  * layout (the key points with the owed re-selections applied).  The caller's buffers hold at least the sizes
  * svo_hip_tracker_map_sizes reports (kf_ftr_offset n_kf + 1, pt_obs_offset n_points + 1); a NULL pointer skips its table.
