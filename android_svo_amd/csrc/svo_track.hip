@@ -861,6 +861,131 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_remove_kernel(TrkMap m, TrkGr
   }
 }
 
+// ---- the points are renumbered in place: the unlinked ones (pt_unlinked: deleted by a tracked frame or by a removal) leave
+// the tables, the others keep their order -- a living point's new index is the number of living points below it.  The tables
+// end in the form a host flatten under the new numbering writes, the one trk_remove_kernel leaves: no row, no observation, no
+// feature-row entry and no candidate entry of a dead point, -1 entries dropped, every order kept.
+// What holds a point index, and what becomes of it here:
+//   kf_key_point, kf_ftr_point, cand_point        rewritten (the pending re-selection of key points has run before the launch)
+//   TrkLast::point (the last frame's features)    rewritten; a feature whose point is dead gets -1 and the solver's copy of
+//                                                 it is cleared as trk_remove_kernel does (none after a tracked frame)
+//   the solver's slot (sia_pos, sia_has_point)    holds positions and flags by feature, no index
+//   the pt_* rows, pt_unlinked, pt_obs_offset     the rows of the living points move down, the offsets are rebuilt
+//   TrkPlan::first_seq / item_point / cand_point, TrkFeat::point, TrkStructSel: scratch of one call, rebuilt by the next
+//   svo_hip_tracker::last_max_point               host side: set from out[4] (svo_hip_tracker_compact_points)
+//   svo_hip_tracker::track_n_points and the page-locked result block: NOT rewritten -- svo_hip_tracker_last_result keeps
+//                                                 returning the frame under the numbering it was tracked with
+// mark[p] (per-point scratch) receives old_to_new: the new index, -1 for a dead point; the host copies it out.
+// The observation CSR, the feature rows and the candidate list are rebuilt into the second set.  The pt_* rows have no second
+// set: they move down in place by an ascending walk in chunks of one block -- every thread reads the row of its point of the
+// chunk into registers, a barrier, then writes it to its new index.  A new index is never above the old one, so the writes of a
+// chunk land on rows of this chunk (read before the barrier) or of earlier chunks (read in earlier rounds), never on a row a
+// later chunk has yet to read: one barrier a chunk is enough.  One workgroup of TRK_THREADS.
+__global__ __launch_bounds__(TRK_THREADS) void trk_compact_kernel(TrkMap m, TrkGrow g, double* __restrict__ pt_pos, int* __restrict__ kf_key_point,
+                                                                  int* __restrict__ mark, TrkLast last, int n_ftr) {
+  __shared__ int s_part[TRK_THREADS];
+  __shared__ int s_last_max;
+  const int t = threadIdx.x, nt = blockDim.x;
+  const int K = m.n_kf, P = m.n_points;
+  if (t == 0) s_last_max = -1;
+  // ---- the new indices: an exclusive scan over "living" (in the second set's offsets: P + 1 entries)
+  for (int p = t; p < P; p += nt) g.pt_obs_offset[p] = m.pt_unlinked[p] ? 0 : 1;
+  __syncthreads();
+  block_exclusive_scan(g.pt_obs_offset, P, s_part);
+  const int N = g.pt_obs_offset[P];
+  for (int p = t; p < P; p += nt) mark[p] = m.pt_unlinked[p] ? -1 : g.pt_obs_offset[p];
+  __syncthreads();                                                               // (every thread holds N; the offsets are free again)
+  // ---- the observations of the living points, by new index
+  for (int p = t; p < P; p += nt) {
+    const int q = mark[p];
+    if (q >= 0) g.pt_obs_offset[q] = m.pt_obs_offset[p + 1] - m.pt_obs_offset[p];
+  }
+  __syncthreads();
+  block_exclusive_scan(g.pt_obs_offset, N, s_part);
+  for (int p = t; p < P; p += nt) {
+    const int q = mark[p];
+    if (q < 0) continue;
+    size_t d = (size_t)g.pt_obs_offset[q];
+    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o, ++d) {
+      g.obs_kf[d] = m.obs_kf[o];
+      g.obs_px[2 * d] = m.obs_px[2 * o]; g.obs_px[2 * d + 1] = m.obs_px[2 * o + 1];
+      g.obs_f[3 * d] = m.obs_f[3 * o]; g.obs_f[3 * d + 1] = m.obs_f[3 * o + 1]; g.obs_f[3 * d + 2] = m.obs_f[3 * o + 2];
+      g.obs_level[d] = m.obs_level[o]; g.obs_edgelet[d] = m.obs_edgelet[o];
+      g.obs_grad[2 * d] = m.obs_grad[2 * o]; g.obs_grad[2 * d + 1] = m.obs_grad[2 * o + 1];
+    }
+  }
+  // ---- the feature rows keep the entries that still have a point
+  for (int i = t; i < n_ftr; i += nt) {
+    const int p = m.kf_ftr_point[i];
+    g.ftr_scan[i] = p >= 0 && mark[p] >= 0 ? 1 : 0;
+  }
+  __syncthreads();
+  block_exclusive_scan(g.ftr_scan, n_ftr, s_part);
+  for (int i = t; i < n_ftr; i += nt) {
+    const int p = m.kf_ftr_point[i];
+    if (p >= 0 && mark[p] >= 0) g.kf_ftr_point[g.ftr_scan[i]] = mark[p];
+  }
+  if (K > 0)                                                                     // (a map without keyframes has no offsets)
+    for (int j = t; j <= K; j += nt) g.kf_ftr_offset[j] = g.ftr_scan[m.kf_ftr_offset[j]];
+  // ---- the candidate list
+  for (int c = t; c < m.n_candidates; c += nt) {
+    const int p = m.cand_point[c];
+    g.cand_scan[c] = p >= 0 && mark[p] >= 0 ? 1 : 0;
+  }
+  __syncthreads();
+  block_exclusive_scan(g.cand_scan, m.n_candidates, s_part);
+  for (int c = t; c < m.n_candidates; c += nt) {
+    const int p = m.cand_point[c];
+    if (p >= 0 && mark[p] >= 0) g.cand_point[g.cand_scan[c]] = mark[p];
+  }
+  // ---- the key points (none is dead after the re-selection; one that were would become -1)
+  for (int j = t; j < 5 * K; j += nt) {
+    const int p = kf_key_point[j];
+    if (p >= 0) kf_key_point[j] = mark[p];
+  }
+  // ---- the last frame
+  const int n_last = *last.n;
+  int last_max = -1;
+  for (int i = t; i < n_last; i += nt) {
+    const int p = last.point[i];
+    if (p < 0 || p >= P) continue;
+    const int q = mark[p];
+    last.point[i] = q;
+    if (q > last_max) last_max = q;
+    if (q < 0 && i < last.sia_max_n) {                                           // what the solver holds of a feature without a point
+      last.sia_has_point[i] = 0;
+      last.sia_pos[3 * i] = 0.0; last.sia_pos[3 * i + 1] = 0.0; last.sia_pos[3 * i + 2] = 1.0;
+    }
+  }
+  if (last_max >= 0) atomicMax(&s_last_max, last_max);
+  // ---- the rows of the points move down in place (see above: read, barrier, write, chunk by chunk upwards).  From here on
+  // nothing reads pt_unlinked.
+  for (int base = 0; base < P; base += nt) {                                     // block-uniform
+    const int p = base + t;
+    const int q = p < P ? mark[p] : -1;
+    double x = 0.0, y = 0.0, z = 0.0;
+    int ty = 0, nf = 0, ns = 0;
+    if (q >= 0) {
+      x = pt_pos[3 * (size_t)p]; y = pt_pos[3 * (size_t)p + 1]; z = pt_pos[3 * (size_t)p + 2];
+      ty = m.pt_type[p]; nf = m.pt_n_failed[p]; ns = m.pt_n_succeeded[p];
+    }
+    __syncthreads();
+    if (q >= 0) {
+      pt_pos[3 * (size_t)q] = x; pt_pos[3 * (size_t)q + 1] = y; pt_pos[3 * (size_t)q + 2] = z;
+      m.pt_type[q] = ty; m.pt_n_failed[q] = nf; m.pt_n_succeeded[q] = ns;
+      m.pt_unlinked[q] = 0;
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    g.out[0] = N;
+    g.out[1] = g.ftr_scan[n_ftr];
+    g.out[2] = g.pt_obs_offset[N];
+    g.out[3] = g.cand_scan[m.n_candidates];
+    g.out[4] = s_last_max;
+  }
+}
+
 // ---- FrameHandlerBase::optimizeStructure (S/frame_handler_base.cpp:190-210) on the points the host selected: Point::optimize
 // of each of them over its observations as the map tables hold them (keyframe pose + bearing, Point::obs_ order), the new
 // positions written into the point table, into the solver's copy of the last frame's points (the next SparseImgAlign::run reads
@@ -1091,6 +1216,7 @@ struct svo_hip_tracker {
   int last_n_host = 0;
   int last_max_point = -1;                  // largest map point index the last frame's features refer to (set_last_frame input)
   bool last_from_track = false;             // ... or: the last frame is the previous call's new frame, its features are in the result block
+  bool last_renumbered = false;             // ... whose point indices a compaction has outdated since: last_max_point holds the bound again
   // plan / replay scratch
   TrkPlan pl{};
   TrkFeat ft{};
@@ -1355,7 +1481,7 @@ int svo_hip_tracker_set_map(svo_hip_tracker* t, const svo_hip_tracker_map* mp) {
     // the last frame's features keep referring to map points by index: a map with fewer points than the largest of them
     // needs svo_hip_tracker_set_last_frame again (the result block still holds the features of a tracked frame)
     int max_point = t->last_max_point;
-    if (t->last_from_track) {
+    if (t->last_from_track && !t->last_renumbered) {
       const int32_t* fp = reinterpret_cast<const int32_t*>(t->res_host + t->o_point);
       max_point = -1;
       for (int i = 0; i < t->last_n_host; ++i) if (fp[i] > max_point) max_point = fp[i];
@@ -1512,6 +1638,7 @@ int svo_hip_tracker_set_last_frame(svo_hip_tracker* t, const uint8_t* level0, in
   t->last_n_host = n;
   t->last_max_point = max_point;
   t->last_from_track = false;
+  t->last_renumbered = false;
   t->have_last = true;
   t->need_gather = true;
   return SVO_HIP_OK;
@@ -1672,6 +1799,7 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
     t->last_n_host = r->n_features;
     t->track_n_points = t->n_points;
     t->last_from_track = true;
+    t->last_renumbered = false;
     t->need_gather = false;
     if (r->map_changed) t->rekey_pending = true;
   }
@@ -1949,6 +2077,34 @@ int svo_hip_tracker_remove_keyframe(svo_hip_tracker* t, int kf_index, int* slot_
   // the keyframes that lost a key feature to a point deleted here choose again (Frame::removeKeyPoint), on the new rows,
   // before anything reads the key points
   if (out[0] > 0) t->rekey_pending = true;
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_compact_points(svo_hip_tracker* t, int* n_points_after, int32_t* old_to_new) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_compact_points", "no map has been set");
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = trk_grow_tables(t);
+  if (rc != SVO_HIP_OK) return rc;
+  rc = trk_rekey_now(t);                    // (the re-selection owed to the last frame's deletions sees the rows as they were)
+  if (rc != SVO_HIP_OK) return rc;
+  const int n_before = t->n_points;
+  hipLaunchKernelGGL(trk_compact_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, make_map(t), t->grow, t->pt_pos, t->kf_key_point,
+                     t->pl.first_seq, t->last, t->n_ftr);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  int out[5] = {0, 0, 0, 0, -1};
+  SVO_CHECK_HIP(ctx, hipMemcpyAsync(out, t->grow.out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
+  if (old_to_new && n_before > 0)
+    SVO_CHECK_HIP(ctx, hipMemcpyAsync(old_to_new, t->pl.first_seq, (size_t)n_before * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  trk_swap_grown(t);
+  t->n_points = out[0]; t->n_ftr = out[1]; t->n_obs = out[2]; t->n_candidates = out[3];
+  // the last frame's features refer to the new numbering on the device; the result block (and track_n_points, its layout)
+  // stays the tracked frame's under the old one
+  t->last_max_point = out[4];
+  t->last_renumbered = t->last_from_track;
+  if (n_points_after) *n_points_after = t->n_points;
   return SVO_HIP_OK;
 }
 

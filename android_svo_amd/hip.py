@@ -1031,6 +1031,18 @@ class Tracker:
                        "tracker_remove_keyframe")
         return dict(slot=s.value, n_deleted_points=p.value, n_deleted_candidates=c.value)
 
+    def compact_points(self) -> dict:
+        """svo_hip_tracker_compact_points: the points the device holds as unlinked leave its tables in place, the living ones
+        are renumbered in order.  Returns dict(n_points = the number of living points, old_to_new = int32[n_points before]:
+        the new index of every point, -1 for a dead one).  last_result() keeps the old numbering and the old point count."""
+        nb = C.c_int(0)
+        before = nb.value if self.ctx.lib.svo_hip_tracker_map_sizes(self.h, None, None, C.byref(nb), None, None) == 0 else 0
+        n = C.c_int(-1)
+        o2n = np.full(max(before, 1), -1, np.int32)
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_compact_points(self.h, C.byref(n), _ptr(o2n, C.c_int32)), "tracker_compact_points")
+        self.n_points = n.value
+        return dict(n_points=n.value, old_to_new=o2n[:before])
+
     def map_sizes(self) -> dict:
         """svo_hip_tracker_map_sizes: n_kf, n_ftr, n_points, n_obs, n_candidates of the tables the device holds"""
         v = [C.c_int() for _ in range(5)]

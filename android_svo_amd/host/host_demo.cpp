@@ -109,13 +109,14 @@ struct TrackerPort {
   }
 };
 
-static svo_hip_tracker_config track_config(const std::vector<double>& m, int max_kfs = 0) {
+static svo_hip_tracker_config track_config(const std::vector<double>& m, int max_kfs = 0, int max_points = 0) {
   svo_hip_tracker_config cfg;
   svo_hip_tracker_default_config(&cfg);
   cfg.max_keyframes = (int)m[6] + 2;                                          // room for a frame that becomes a keyframe
   if (cfg.max_keyframes < max_kfs + 1) cfg.max_keyframes = max_kfs + 1;      // (the new keyframe joins before the furthest one leaves)
   cfg.grid_size = (int)m[12]; cfg.max_fts = (int)m[13]; cfg.quality_min_fts = (int)m[14];
   cfg.klt_min_level = (int)m[15]; cfg.max_frame_features = (int)m[16];
+  if (max_points > 0) cfg.max_points = max_points;
   return cfg;
 }
 
@@ -127,8 +128,15 @@ static svo_hip_tracker_config track_config(const std::vector<double>& m, int max
 // which reaches the device through FrameTracker::keyframeRemoved; full_remove: through mapChanged() instead (a full upload, the
 // yardstick).  A frame whose pose is NaN (tracking was lost) has no furthest keyframe, and the reference would let the map grow:
 // the demo stops there.  track_removed.bin: per frame, which keyframe left (in order of creation), or -1; track_map_size.bin: the map at the end.
+// new_seeds S: every frame that becomes a keyframe seeds S point candidates behind the tracker's back, as the depth filter's thread
+// does when seeds of that keyframe converge: twins of the first S of its features that have a point, a tenth of a millimetre
+// off.  They reach the device with the next frame; those that are not matched and promoted go with their keyframe, so with max_kfs
+// the living points stay bounded while the rows of the device's point tables grow.  max_points N: svo_hip_tracker_config::max_points.
+// compact: FrameTracker::setPointCompaction.  map_compactions.bin: per frame, the compactions so far (beside track_uploads.bin);
+// map_points_room.bin: the largest (living points + candidates waiting to be appended) at the end of a frame, and the rows of
+// the device's point tables at the end.
 static int track_demo(const std::string& dir, const std::string& out, TrackerPort& port, bool incremental = false, bool times = false,
-                      int max_kfs = 0, bool full_remove = false, int kf_every = 0) {
+                      int max_kfs = 0, bool full_remove = false, int kf_every = 0, bool compact = false, int new_seeds = 0) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
   PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
   const int n_kf = (int)m[6], n_points = (int)m[7], n_obs = (int)m[8], n_cand = (int)m[10], n_frames = (int)m[11];
@@ -189,6 +197,7 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
   TrackerCamera& tracker = port.camera();
   if (!tracker.ok()) throw std::runtime_error("svo::FrameTracker: no device tracker");
   tracker.setIncrementalMap(incremental);
+  if (compact) tracker.setPointCompaction(true);
   std::vector<double> track_us;
 
   // the last frame: a keyframe of the map, or a frame of its own without features (SparseImgAlign::run then returns at once)
@@ -202,7 +211,8 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
     last = std::make_shared<Frame>(&cam, std::move(pyr));
     last->T_f_w_ = SE3(read_bin<double>(dir + "/last_pose.bin").data());
   }
-  std::vector<double> poses, stats, overlap, uploads, removed;
+  std::vector<double> poses, stats, overlap, uploads, removed, compactions;
+  size_t room_needed = 0;
   const int keyframe_at = m.size() > 19 ? (int)m[19] : -1;
   for (int k = 0; k < n_frames; ++k) {
     std::vector<std::vector<uint8_t>> pyr;
@@ -260,6 +270,7 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
       write_bin(out + "/track_obs_linked_after_first.bin", linked);
     }
     uploads.push_back((double)tracker.mapUploads());
+    compactions.push_back((double)tracker.pointCompactions());
     if (m.size() > 20 && (int)m[20] == k && !map.point_candidates_.candidates_.empty()) {
       // what the depth filter's thread does when a seed converges (MapPointCandidates::newCandidatePoint): a new candidate
       // appears in the list behind the tracker's back -- here a twin of the list's first one
@@ -299,9 +310,30 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
         else if (!tracker.keyframeRemoved(furthest, map)) throw std::runtime_error("svo::FrameTracker::keyframeRemoved failed");
       }
     }
+    size_t n_seeded = 0;
+    if (new_seeds > 0 && cur->is_keyframe_) {
+      // the depth filter's thread: seeds of the new keyframe converge (DepthFilter::updateSeeds :310-331, newCandidatePoint)
+      std::unique_lock<std::mutex> lock(map.point_candidates_.mut_);
+      for (const Feature* ftr : cur->fts_) {
+        if ((int)n_seeded == new_seeds) break;
+        if (ftr->point == nullptr) continue;
+        points.emplace_back(new Point(Vector3d{{ftr->point->pos_[0] + 1e-4, ftr->point->pos_[1] + 1e-4, ftr->point->pos_[2] + 1e-4}}));
+        Point* np_ = points.back().get();
+        np_->type_ = Point::TYPE_CANDIDATE;
+        Feature* nf = new Feature(cur.get(), ftr->px, ftr->f, ftr->level);
+        nf->point = np_;
+        np_->obs_.push_front(nf);
+        index_of_point[np_] = (int)points.size() - 1;
+        map.point_candidates_.candidates_.push_back(MapPointCandidates::PointCandidate(np_, nf));
+        ++n_seeded;
+      }
+    }
+    room_needed = std::max(room_needed, tracker.livingPoints() + n_seeded);
     last = cur;
   }
   write_bin(out + "/track_poses.bin", poses);
+  write_bin(out + "/map_compactions.bin", compactions);
+  write_bin(out + "/map_points_room.bin", std::vector<double>{(double)room_needed, (double)tracker.tablePoints()});
   write_bin(out + "/track_stats.bin", stats);
   write_bin(out + "/track_uploads.bin", uploads);
   if (max_kfs > 0) {
@@ -318,13 +350,14 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
   return 0;
 }
 
-static int track_lone(const std::string& dir, const std::string& out, bool incremental, bool times, int max_kfs, bool full_remove, int kf_every) {
+static int track_lone(const std::string& dir, const std::string& out, bool incremental, bool times, int max_kfs, bool full_remove, int kf_every,
+                      int max_points, bool compact, int new_seeds) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
   PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
-  FrameTracker tracker(cam, track_config(m, max_kfs));
+  FrameTracker tracker(cam, track_config(m, max_kfs, max_points));
   TrackerPort port;
   port.lone = &tracker;
-  return track_demo(dir, out, port, incremental, times, max_kfs, full_remove, kf_every);
+  return track_demo(dir, out, port, incremental, times, max_kfs, full_remove, kf_every, compact, new_seeds);
 }
 
 // n copies of the world, one svo::FrameTrackerGroup: every world's outputs must equal the lone tracker's
@@ -452,7 +485,7 @@ static int churn_demo(const std::string& dir, const std::string& out) {
 }
 
 int main(int argc, char** argv) {
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove]|trackgroup n|churn]\n", argv[0]); return 2; }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact]|trackgroup n|churn]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {
@@ -472,16 +505,19 @@ int main(int argc, char** argv) {
   }
   if (argc > 3 && std::string(argv[3]) == "track") {
     try {
-      bool incremental = false, times = false, full_remove = false;            // optional trailing arguments
-      int max_kfs = 0, kf_every = 0;
+      bool incremental = false, times = false, full_remove = false, compact = false;     // optional trailing arguments
+      int max_kfs = 0, kf_every = 0, max_points = 0, new_seeds = 0;
       for (int a = 4; a < argc; ++a) {
         incremental = incremental || std::string(argv[a]) == "incremental";
         times = times || std::string(argv[a]) == "times";
         full_remove = full_remove || std::string(argv[a]) == "full_remove";
         if (std::string(argv[a]) == "max_kfs" && a + 1 < argc) max_kfs = std::atoi(argv[++a]);
         else if (std::string(argv[a]) == "kf_every" && a + 1 < argc) kf_every = std::atoi(argv[++a]);
+        else if (std::string(argv[a]) == "max_points" && a + 1 < argc) max_points = std::atoi(argv[++a]);
+        else if (std::string(argv[a]) == "new_seeds" && a + 1 < argc) new_seeds = std::atoi(argv[++a]);
+        else if (std::string(argv[a]) == "compact") compact = true;
       }
-      return track_lone(dir, out, incremental, times, max_kfs, full_remove, kf_every);
+      return track_lone(dir, out, incremental, times, max_kfs, full_remove, kf_every, max_points, compact, new_seeds);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "svo_host_demo FAILED: %s\n", e.what());
       return 1;

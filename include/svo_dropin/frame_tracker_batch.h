@@ -90,6 +90,23 @@ class FrameTrackerT {
   /// mapChanged(): anything else that renumbers keyframes or points.
   void setIncrementalMap(bool on) { incremental_ = on; }
   bool incrementalMap() const { return incremental_; }
+  /// Opt-in (default off; takes effect only with setIncrementalMap(true)): when svo_hip_tracker_add_candidates or
+  /// svo_hip_tracker_promote_last_frame refuses -- deleted points keep their rows, so a bounded map reaches max_points, max_obs or
+  /// max_kf_features all the same -- the bridge renumbers the points in place (svo_hip_tracker_compact_points), drops the
+  /// deleted ones from its own tables and repeats the call once.  A second refusal falls back to the full upload.  With the
+  /// option off every path is what it was.  (The C-ABI function is reached through a pointer set here, so that code which
+  /// never turns the option on does not refer to it.)
+  void setPointCompaction(bool on) { compact_fn_ = on ? &svo_hip_tracker_compact_points : (CompactFn)NULL; }
+  bool pointCompaction() const { return compact_fn_ != NULL; }
+  /// how often the points have been renumbered in place (diagnostic)
+  size_t pointCompactions() const { return n_compactions_; }
+  /// rows of the device's point tables, and how many of them are points this side still holds (diagnostic)
+  size_t tablePoints() const { return points_.size(); }
+  size_t livingPoints() const {
+    size_t n = 0;
+    for (size_t p = 0; p < points_.size(); ++p) n += points_[p] != NULL ? 1 : 0;
+    return n;
+  }
 
   /// page-locked buffer of one full-resolution image (svo_hip_tracker_image_buffer): a new frame whose level 0 lives there
   /// (cv::Mat(rows, cols, CV_8UC1, tracker.imageBuffer()) handed to the Frame constructor) is tracked without the copy of its
@@ -268,7 +285,9 @@ class FrameTrackerT {
     const int slot = freeSlot();
     if (slot < 0) return false;
     int kf_index = -1, n_promoted = 0;
-    if (svo_hip_tracker_promote_last_frame(trk_, slot, &kf_index, &n_promoted) != SVO_HIP_OK || kf_index != (int)keyframes_.size())
+    int rc = svo_hip_tracker_promote_last_frame(trk_, slot, &kf_index, &n_promoted);
+    if (rc != SVO_HIP_OK && compactPoints()) rc = svo_hip_tracker_promote_last_frame(trk_, slot, &kf_index, &n_promoted);   // once
+    if (rc != SVO_HIP_OK || kf_index != (int)keyframes_.size())
       return lastFrameBecameKeyframe(*frame);                 // (a refused promotion changed nothing: the full upload follows)
     slot_of_frame_[frame->id_] = slot;
     index_of_frame_[frame->id_] = kf_index;
@@ -354,12 +373,41 @@ class FrameTrackerT {
       fresh.push_back(pt);
     }
     int32_t first = -1;
-    if (svo_hip_tracker_add_candidates(trk_, (int)fresh.size(), pos.data(), kf.data(), px.data(), f.data(), level.data(), edge.data(), grad.data(),
-                                       &first) != SVO_HIP_OK)
-      return false;
+    int rc = svo_hip_tracker_add_candidates(trk_, (int)fresh.size(), pos.data(), kf.data(), px.data(), f.data(), level.data(), edge.data(),
+                                            grad.data(), &first);
+    if (rc != SVO_HIP_OK && compactPoints())                  // (keyframe indices are not touched by it: the arrays stay valid); once
+      rc = svo_hip_tracker_add_candidates(trk_, (int)fresh.size(), pos.data(), kf.data(), px.data(), f.data(), level.data(), edge.data(),
+                                          grad.data(), &first);
+    if (rc != SVO_HIP_OK) return false;
     if (first != (int32_t)points_.size()) { map_dirty_ = true; return false; }   // (cannot happen: both sides count the same points)
     for (size_t i = 0; i < fresh.size(); ++i) { index_of_point_[fresh[i]] = (int)points_.size(); points_.push_back(fresh[i]); }
     n_candidates_ += g;
+    return true;
+  }
+  /// A device call was refused: with setPointCompaction the points the tracker and the removals deleted (NULL in points_) leave
+  /// the device tables in place, and points_ / index_of_point_ follow old_to_new.  Cross-checked as keyframeRemoved does: the
+  /// device must have kept exactly the points this side still holds; otherwise mapChanged().  true: renumbered, the refused
+  /// call is worth repeating.
+  bool compactPoints() {
+    if (compact_fn_ == NULL || !incremental_ || map_dirty_) return false;
+    std::vector<int32_t> old_to_new(points_.size() + 1, -1);
+    int n_after = -1;
+    if (compact_fn_(trk_, &n_after, old_to_new.data()) != SVO_HIP_OK) return false;
+    ++n_compactions_;
+    int n_live = 0;
+    bool agree = true;
+    for (size_t p = 0; p < points_.size(); ++p) {
+      if (points_[p] == NULL) agree = agree && old_to_new[p] == -1;
+      else agree = agree && old_to_new[p] == n_live++;
+    }
+    if (!agree || n_after != n_live) { mapChanged(); return false; }     // (the two sides disagree: the full upload puts the device right)
+    std::vector<Point*> kept((size_t)n_live, (Point*)NULL);
+    for (size_t p = 0; p < points_.size(); ++p) {
+      if (points_[p] == NULL) continue;
+      kept[(size_t)old_to_new[p]] = points_[p];
+      index_of_point_[points_[p]] = old_to_new[p];
+    }
+    points_.swap(kept);                                       // (the p_* buffers follow points_.size() in prepare)
     return true;
   }
   bool uploadLastFrame(const Frame& last) {
@@ -481,6 +529,9 @@ class FrameTrackerT {
   svo_hip_tracker_config cfg_;
   bool map_dirty_, have_last_;
   bool incremental_ = false;                                 // setIncrementalMap
+  typedef int (*CompactFn)(svo_hip_tracker*, int*, int32_t*);
+  CompactFn compact_fn_ = NULL;                              // setPointCompaction: svo_hip_tracker_compact_points, or NULL
+  size_t n_compactions_ = 0;
   std::map<int, int> index_of_frame_;                        // Frame::id_ -> keyframe index of the device tables
   size_t n_uploads_ = 0;
   size_t n_candidates_ = 0;                                  // MapPointCandidates::candidates_.size() as uploaded, minus our own deletions

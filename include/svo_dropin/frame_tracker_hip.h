@@ -74,6 +74,9 @@ class FrameTracker : public FrameTrackerT<SvoTrackerHost> {
   bool newKeyframe(const FramePtr& frame, Map& map) { return lastFrameBecameKeyframe(frame, map); }
   /// processFrame :307 with setIncrementalMap(true): map_.safeDeleteFrame(frame) has run, the device removes the keyframe in place
   bool keyframeLeft(const FramePtr& frame, Map& map) { return keyframeRemoved(frame, map); }
+  /// a bounded map (Config::maxNKfs() > 0) on one upload for good: setIncrementalMap with setPointCompaction, so that the rows of
+  /// deleted points are given back in place when a table is full
+  void keepMapOnDevice(bool on) { setIncrementalMap(on); setPointCompaction(on); }
 };
 
 /// Several FrameHandlerMono objects (cameras, or sequences replayed side by side) tracked together: one chain of launches per

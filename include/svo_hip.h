@@ -789,10 +789,10 @@ int svo_hip_tracker_last_result(svo_hip_tracker* trk, svo_hip_track_result* resu
  * frame becomes a keyframe.  Both extend the device tables without the host flattening its pointer graph again.  Point,
  * keyframe and candidate indices that existed before keep their meaning, so the last frame stays valid across both calls.
  * Both take a lone tracker's handle or a handle from svo_hip_tracker_group_camera.  A keyframe leaves the map in place too
- * (svo_hip_tracker_remove_keyframe below).  Nothing renumbers POINTS in place: a deleted point keeps its index and its rows of the
- * pt_* tables, so n_points only grows; when svo_hip_tracker_add_candidates is refused for max_points, a svo_hip_tracker_set_map
- * of the flattened map compacts them.  What still needs svo_hip_tracker_set_map: anything that renumbers points, or
- * keyframes in another way than that removal.
+ * (svo_hip_tracker_remove_keyframe below).  None of the three renumbers POINTS: a deleted point keeps its index and its rows of
+ * the pt_* tables, so n_points only grows with them; when svo_hip_tracker_add_candidates is refused for max_points,
+ * svo_hip_tracker_compact_points (below) renumbers the living points in place and frees the room the dead ones held.  What
+ * still needs svo_hip_tracker_set_map: anything that renumbers points or keyframes in another way than those two calls.
  *
  * svo_hip_tracker_add_candidates: what DepthFilter::updateSeeds (depth_filter.cpp:310-331) and
  * MapPointCandidates::newCandidatePoint (map.cpp:226-231) do for n converged seeds.  Host arrays: pos[n][3] the new points,
@@ -851,6 +851,28 @@ int svo_hip_tracker_promote_last_frame(svo_hip_tracker* trk, int slot, int* kf_i
  * Config::maxNKfs() > 2).  Outputs may be NULL.  One launch, synchronises once. */
 int svo_hip_tracker_remove_keyframe(svo_hip_tracker* trk, int kf_index, int* slot_freed, int* n_deleted_points,
                                     int* n_deleted_candidates);
+/* svo_hip_tracker_compact_points: the dead points leave the device's tables in place and the living ones are renumbered.  Takes
+ * a lone tracker's handle or a handle from svo_hip_tracker_group_camera.
+ *   - A point is dead exactly when the device holds it as unlinked: deleted by a tracked frame (the reprojector's
+ *     thresholds) or by svo_hip_tracker_remove_keyframe.  svo_hip_tracker_set_map unlinks nothing: a point uploaded as
+ *     TYPE_DELETED is a living row until one of those deletes it.
+ *   - Living points keep their relative order: the new index of a living point is the number of living points below it.
+ *     old_to_new[n_points before the call] (may be NULL) receives that index, -1 for a dead point; *n_points_after (may be
+ *     NULL) the number of living points.
+ *   - A re-selection of key points the last frame's deletions still owe is applied first, on the rows as they were.
+ *   - The tables end in the form a host flatten under the NEW numbering writes, the form the removal leaves: no row of a dead
+ *     point in pt_pos, pt_type, pt_n_failed, pt_n_succeeded and pt_obs_offset, no observation of one, no feature-row entry
+ *     and no candidate entry that points to one, -1 entries dropped; row order, per-point observation order and candidate
+ *     order are kept.  svo_hip_tracker_map_sizes is exact afterwards, so the call also frees room in max_obs and
+ *     max_kf_features.  Without a dead point every table keeps its bytes and old_to_new is the identity.
+ *   - Every point index the device holds is rewritten: key points, feature rows, the candidate list and the features of the
+ *     device's last frame (one whose point is dead gets -1 and the solver skips it; after a tracked frame there is none).
+ *   - The page-locked result block of the last tracked frame is NOT rewritten: svo_hip_tracker_last_result keeps returning
+ *     that frame as it was tracked, feat_point under the OLD numbering and the point counters for the OLD number of points.
+ *     old_to_new is what translates it.  Results of frames tracked afterwards use the new numbering.
+ * No table grows, so there is no capacity check; n_points == 0 is valid.  SVO_HIP_ERR_STATE without a map (nothing changes).
+ * One launch, synchronises once. */
+int svo_hip_tracker_compact_points(svo_hip_tracker* trk, int* n_points_after, int32_t* old_to_new);
 /* diagnostics and parity tests: the sizes of the tables the device holds, and the tables themselves in svo_hip_tracker_map's
  * layout (the key points with the owed re-selections applied).  The caller's buffers hold at least the sizes
  * svo_hip_tracker_map_sizes reports (kf_ftr_offset n_kf + 1, pt_obs_offset n_points + 1); a NULL pointer skips its table.
