@@ -71,6 +71,25 @@ struct TrkMap {
   const int* cand_point;
 };
 
+// The tables whose entries move when the map is rebuilt in place (a keyframe joins or leaves, the points are renumbered): the
+// observation CSR, the keyframes' feature rows and the candidate list.  A tracker holds two such sets, each at the capacities of
+// its configuration; a rebuild reads the current one (through TrkMap) and writes the other, which is the current one afterwards.
+struct TrkTables {
+  int* pt_obs_offset;            // [max_points + 1]
+  int* obs_kf; double* obs_px; double* obs_f; int* obs_level; uint8_t* obs_edgelet; double* obs_grad;   // [max_obs] rows, as in TrkMap
+  int* kf_ftr_offset;            // [max_keyframes + 1]
+  int* kf_ftr_point;             // [max_kf_features]
+  int* cand_point;               // [max_candidates]
+};
+
+// scratch of the rebuild kernels (one workgroup each), and what they report to the host
+struct TrkScratch {
+  int* cand_seed;                // [max_candidates] trk_promote_kernel: -2 stays, -1 promoted without a seed observation, else its seed keyframe
+  int* cand_scan;                // [max_candidates + 1]
+  int* ftr_scan;                 // [max_kf_features + 1]
+  int* out;                      // [8]: 0 the call's own count, 1 n_ftr, 2 n_obs, 3 n_candidates afterwards (trk_rebuild_end), 4 the call's own
+};
+
 // scratch and outputs of the planning kernel; cap = capacity of the candidate arrays
 struct TrkPlan {
   int cap, n_cells, grid_cols, grid_size, max_n_kfs;
@@ -187,6 +206,20 @@ SVO_DEV void block_exclusive_scan(int* v, int n, int* s_part) {
   if (t == nt - 1) v[n] = before + incl;
   __syncthreads();
   (void)n_waves;
+}
+
+// ordered compaction by one workgroup: the elements i of [0, n) with keep(i) get the ranks 0, 1, ... in ascending i, and
+// put(rank, i) is called once for each of them, by the thread that owns i.  scan: n + 1 ints of scratch; scan[n] = how many
+// were kept.  keep is evaluated twice, before and after the scan.  Block-uniform call with three barriers inside (one behind
+// the flags, two in the scan; the last one is behind scan[n], not behind the calls of put).
+template <typename Keep, typename Put>
+SVO_DEV void block_compact(int n, int* scan, int* s_part, Keep keep, Put put) {
+  const int t = threadIdx.x, nt = blockDim.x;
+  for (int i = t; i < n; i += nt) scan[i] = keep(i) ? 1 : 0;
+  __syncthreads();
+  block_exclusive_scan(scan, n, s_part);
+  for (int i = t; i < n; i += nt)
+    if (keep(i)) put(scan[i], i);
 }
 
 // ---- Reprojector::reprojectMap up to the cell loop (S/reprojector.cpp:72-146) + the per-candidate choice of the reference
@@ -498,20 +531,31 @@ SVO_DEV void key_best_offer(KeyBest& b, int cu, int cv, int idx, double x, doubl
     if (better) { b.v[j] = v; b.i[j] = idx; }
   }
 }
-// slot j over the nt threads' bests: best value, lowest feature index on ties; false: no contender (a feature outside the
-// quadrant is none)
-SVO_DEV bool key_best_reduce(int j, const double* s_val, const int* s_idx, int nt, double* bv_out, int* bi_out) {
-  double bv = j == 0 ? HUGE_VAL : -HUGE_VAL;
+// The five slots over the bests of the workgroup's first KEY_THREADS threads: thread j < 5 gets slot j's best value and, on
+// ties, the lowest feature index; false: no contender (a feature outside the quadrant is none) or not one of the five threads.
+// Block-uniform call with a barrier inside (between the threads' stores to LDS and the five threads' reads).
+constexpr int KEY_THREADS = 256;
+SVO_DEV bool key_best_select(const KeyBest& best, double* bv_out, int* bi_out) {
+  __shared__ int s_idx[5][KEY_THREADS];
+  __shared__ double s_val[5][KEY_THREADS];
+  const int t = threadIdx.x;
+  if (t < KEY_THREADS) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { s_val[j][t] = best.v[j]; s_idx[j][t] = best.i[j]; }
+  }
+  __syncthreads();
+  if (t >= 5) return false;
+  double bv = t == 0 ? HUGE_VAL : -HUGE_VAL;
   int bi = INT_MAX;
-  for (int q = 0; q < nt; ++q) {
-    const double v = s_val[q];
-    const int i = s_idx[q];
+  for (int q = 0; q < KEY_THREADS; ++q) {
+    const double v = s_val[t][q];
+    const int i = s_idx[t][q];
     if (i == INT_MAX) continue;
-    const bool better = j == 0 ? v < bv : v > bv;
+    const bool better = t == 0 ? v < bv : v > bv;
     if (better || (v == bv && i < bi)) { bv = v; bi = i; }
   }
   *bv_out = bv; *bi_out = bi;
-  return bi != INT_MAX && (j == 0 || bv > -HUGE_VAL);
+  return bi != INT_MAX && (t == 0 || bv > -HUGE_VAL);
 }
 
 // ---- Frame::removeKeyPoint / setKeyPoints (S/frame.cpp:83-165) for the keyframes that lost a key feature to a point the
@@ -521,10 +565,10 @@ SVO_DEV bool key_best_reduce(int j, const double* s_val, const int* s_idx, int n
 // every slot is contested again by every feature that still has a point, in fts_ order with strict improvement: the
 // incumbent stays on a tie, otherwise the first feature that reaches the best value wins.  A feature's pixel is the
 // observation of its point in this keyframe.
-__global__ __launch_bounds__(256) void trk_rekey_kernel(TrkMap m, int* __restrict__ kf_key_point, Cam cam) {
-  const int k = blockIdx.x, t = threadIdx.x, nt = blockDim.x;
-  __shared__ int s_found, s_inc[5], s_best_idx[5][256];
-  __shared__ double s_inc_val[5], s_best_val[5][256];
+__global__ __launch_bounds__(KEY_THREADS) void trk_rekey_kernel(TrkMap m, int* __restrict__ kf_key_point, Cam cam) {
+  const int k = blockIdx.x, t = threadIdx.x, nt = blockDim.x;        // (nt = KEY_THREADS)
+  __shared__ int s_found, s_inc[5];
+  __shared__ double s_inc_val[5];
   const int cu = cam.width / 2, cv = cam.height / 2;
   // pixel of point p's observation in keyframe k (false: none)
   auto px_in_kf = [&](int p, double* x, double* y) {
@@ -554,69 +598,72 @@ __global__ __launch_bounds__(256) void trk_rekey_kernel(TrkMap m, int* __restric
     if (!px_in_kf(p, &x, &y)) continue;
     key_best_offer(best, cu, cv, i, x, y);
   }
-#pragma unroll
-  for (int j = 0; j < 5; ++j) { s_best_val[j][t] = best.v[j]; s_best_idx[j][t] = best.i[j]; }
-  __syncthreads();
+  double bv;
+  int bi;
+  const bool challenger = key_best_select(best, &bv, &bi);
   if (t < 5) {
-    double bv;
-    int bi;
-    const bool challenger = key_best_reduce(t, s_best_val[t], s_best_idx[t], nt, &bv, &bi);
     int winner = s_inc[t];
     if (challenger && (winner < 0 || (t == 0 ? bv < s_inc_val[t] : bv > s_inc_val[t]))) winner = m.kf_ftr_point[bi];
     kf_key_point[5 * k + t] = winner;
   }
 }
 
-// ---- the map grows in place.  New point candidates (DepthFilter::updateSeeds :310-331 + MapPointCandidates::newCandidatePoint,
-// S/map.cpp:226-231): n records from one staged block go to the tails of the point, observation and candidate tables; no
-// entry that existed before is written.
+// ---- one observation (a keyframe's feature that refers to a point) as a value.  The field list of an observation is written
+// here, once for reading and once for writing, and once each for the two things a new observation is made from.
 struct TrkCandRec { double pos[3], px[2], f[3], grad[2]; int kf, level, edgelet, obs; };    // obs: where its observation goes
+struct ObsRow { int kf; double px[2], f[3]; int level; uint8_t edgelet; double grad[2]; };
+SVO_DEV ObsRow obs_load(const TrkMap& m, size_t o) {
+  return {m.obs_kf[o], {m.obs_px[2 * o], m.obs_px[2 * o + 1]}, {m.obs_f[3 * o], m.obs_f[3 * o + 1], m.obs_f[3 * o + 2]},
+          m.obs_level[o], m.obs_edgelet[o], {m.obs_grad[2 * o], m.obs_grad[2 * o + 1]}};
+}
+SVO_DEV void obs_store(const TrkTables& g, size_t d, const ObsRow& r) {
+  g.obs_kf[d] = r.kf;
+  g.obs_px[2 * d] = r.px[0]; g.obs_px[2 * d + 1] = r.px[1];
+  g.obs_f[3 * d] = r.f[0]; g.obs_f[3 * d + 1] = r.f[1]; g.obs_f[3 * d + 2] = r.f[2];
+  g.obs_level[d] = r.level; g.obs_edgelet[d] = r.edgelet;
+  g.obs_grad[2 * d] = r.grad[0]; g.obs_grad[2 * d + 1] = r.grad[1];
+}
+// feature i of the tracked frame, seen from keyframe k
+SVO_DEV ObsRow obs_of_feature(const TrkFeat& ft, int i, int k) {
+  return {k, {ft.px[2 * i], ft.px[2 * i + 1]}, {ft.f[3 * i], ft.f[3 * i + 1], ft.f[3 * i + 2]}, ft.level[i], ft.edgelet[i],
+          {ft.grad[2 * i], ft.grad[2 * i + 1]}};
+}
+SVO_DEV ObsRow obs_of_record(const TrkCandRec& r) {
+  return {r.kf, {r.px[0], r.px[1]}, {r.f[0], r.f[1], r.f[2]}, r.level, (uint8_t)(r.edgelet ? 1 : 0), {r.grad[0], r.grad[1]}};
+}
+
+// ---- the map grows in place.  New point candidates (DepthFilter::updateSeeds :310-331 + MapPointCandidates::newCandidatePoint,
+// S/map.cpp:226-231): n records from one staged block go to the tails of the point tables and of the current table set (tb);
+// no entry that existed before is written.
 __global__ void trk_add_candidates_kernel(int n, const TrkCandRec* __restrict__ rec, int n_points, int n_cand, double* __restrict__ pt_pos,
                                           int* __restrict__ pt_type, int* __restrict__ pt_n_failed, int* __restrict__ pt_n_succeeded,
-                                          uint8_t* __restrict__ pt_unlinked, int* __restrict__ pt_obs_offset, int* __restrict__ obs_kf,
-                                          double* __restrict__ obs_px, double* __restrict__ obs_f, int* __restrict__ obs_level,
-                                          uint8_t* __restrict__ obs_edgelet, double* __restrict__ obs_grad, int* __restrict__ cand_point) {
+                                          uint8_t* __restrict__ pt_unlinked, TrkTables tb) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const TrkCandRec r = rec[i];
   const size_t p = (size_t)n_points + i;
   pt_pos[3 * p] = r.pos[0]; pt_pos[3 * p + 1] = r.pos[1]; pt_pos[3 * p + 2] = r.pos[2];
   pt_type[p] = TYPE_CANDIDATE; pt_n_failed[p] = 0; pt_n_succeeded[p] = 0; pt_unlinked[p] = 0;
-  if (p == 0) pt_obs_offset[0] = 0;                                            // (a map without points has no offsets yet)
-  pt_obs_offset[p + 1] = r.obs + (r.kf >= 0 ? 1 : 0);
-  cand_point[n_cand + i] = (int)p;
-  if (r.kf >= 0) {
-    const size_t o = (size_t)r.obs;
-    obs_kf[o] = r.kf;
-    obs_px[2 * o] = r.px[0]; obs_px[2 * o + 1] = r.px[1];
-    obs_f[3 * o] = r.f[0]; obs_f[3 * o + 1] = r.f[1]; obs_f[3 * o + 2] = r.f[2];
-    obs_level[o] = r.level; obs_edgelet[o] = r.edgelet ? 1 : 0;
-    obs_grad[2 * o] = r.grad[0]; obs_grad[2 * o + 1] = r.grad[1];
-  }
+  if (p == 0) tb.pt_obs_offset[0] = 0;                                         // (a map without points has no offsets yet)
+  tb.pt_obs_offset[p + 1] = r.obs + (r.kf >= 0 ? 1 : 0);
+  tb.cand_point[n_cand + i] = (int)p;
+  if (r.kf >= 0) obs_store(tb, (size_t)r.obs, obs_of_record(r));
 }
 
-// ---- the tracked frame becomes keyframe n_kf (FrameHandlerMono::processFrame :267-276, map_.addKeyframe :312).  The tables
-// whose entries move are rebuilt into a second set the tracker swaps to: the observation CSR (Point::addFrameRef pushes the new
-// observation to the FRONT of Point::obs_, S/point.cpp:61-65), the keyframes' feature rows (the new keyframe's row, and the seed
-// features MapPointCandidates::addCandidatePointToFrame adds to the END of their keyframes' rows, S/map.cpp:236-254) and the
-// candidate list (compacted, order kept).  One workgroup.
-struct TrkGrow {
-  int* pt_obs_offset; int* obs_kf; double* obs_px; double* obs_f; int* obs_level; uint8_t* obs_edgelet; double* obs_grad;
-  int* kf_ftr_offset; int* kf_ftr_point; int* cand_point;
-  int* cand_seed;                // [max_candidates] scratch: -2 stays, -1 promoted without a seed observation, else its seed keyframe
-  int* cand_scan;                // [max_candidates + 1] scratch
-  int* ftr_scan;                 // [max_kf_features + 1] scratch (trk_remove_kernel)
-  int* out;                      // [8]: promoted candidates (removal: deleted points), n_ftr, n_obs, n_candidates afterwards;
-                                 //      removal only: 4 deleted candidates
-};
+// ---- the rebuild kernels: a promotion, a removal, a renumbering.  Each is one workgroup of TRK_THREADS that reads the current
+// table set through m and writes the other set g (the pt_* rows, the keyframe tables and the last frame are edited where they
+// lie), with sc and the per-point array mark as scratch, and leaves its counts in sc.out (trk_rebuild_end).
+// The tracked frame becomes keyframe n_kf (FrameHandlerMono::processFrame :267-276, map_.addKeyframe :312): the observation CSR
+// (Point::addFrameRef pushes the new observation to the FRONT of Point::obs_, S/point.cpp:61-65), the keyframes' feature rows
+// (the new keyframe's row, and the seed features MapPointCandidates::addCandidatePointToFrame adds to the END of their
+// keyframes' rows, S/map.cpp:236-254) and the candidate list (compacted, order kept).  out[0]: promoted candidates.
 constexpr int TRK_MAX_FRAME_FEATURES = 2816;   // trk_check_config
-__global__ __launch_bounds__(TRK_THREADS) void trk_promote_kernel(TrkMap m, TrkGrow g, double* __restrict__ T_kf_w, double* __restrict__ T_slot_w,
-                                                                  int* __restrict__ kf_slot, int* __restrict__ kf_key_point, int* __restrict__ mark,
-                                                                  TrkFeat ft, TrkLast last, int n_feat, int slot, Cam cam) {
+__global__ __launch_bounds__(TRK_THREADS) void trk_promote_kernel(TrkMap m, TrkTables g, TrkScratch sc, double* __restrict__ T_kf_w,
+                                                                  double* __restrict__ T_slot_w, int* __restrict__ kf_slot,
+                                                                  int* __restrict__ kf_key_point, int* __restrict__ mark, TrkFeat ft, TrkLast last,
+                                                                  int n_feat, int slot, Cam cam) {
   __shared__ int s_part[TRK_THREADS];
   __shared__ int s_fscan[TRK_MAX_FRAME_FEATURES + 1];
-  __shared__ int s_best_idx[5][256];
-  __shared__ double s_best_val[5][256];
   __shared__ int s_n_promoted;
   const int t = threadIdx.x, nt = blockDim.x;
   const int k = m.n_kf;
@@ -638,48 +685,29 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_promote_kernel(TrkMap m, TrkG
   for (int p = t; p < m.n_points; p += nt) {
     size_t d = (size_t)g.pt_obs_offset[p];
     const int i = mark[p];
-    if (i != INT_MAX) {
-      g.obs_kf[d] = k;
-      g.obs_px[2 * d] = ft.px[2 * i]; g.obs_px[2 * d + 1] = ft.px[2 * i + 1];
-      g.obs_f[3 * d] = ft.f[3 * i]; g.obs_f[3 * d + 1] = ft.f[3 * i + 1]; g.obs_f[3 * d + 2] = ft.f[3 * i + 2];
-      g.obs_level[d] = ft.level[i]; g.obs_edgelet[d] = ft.edgelet[i];
-      g.obs_grad[2 * d] = ft.grad[2 * i]; g.obs_grad[2 * d + 1] = ft.grad[2 * i + 1];
-      ++d;
-    }
-    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o, ++d) {
-      g.obs_kf[d] = m.obs_kf[o];
-      g.obs_px[2 * d] = m.obs_px[2 * o]; g.obs_px[2 * d + 1] = m.obs_px[2 * o + 1];
-      g.obs_f[3 * d] = m.obs_f[3 * o]; g.obs_f[3 * d + 1] = m.obs_f[3 * o + 1]; g.obs_f[3 * d + 2] = m.obs_f[3 * o + 2];
-      g.obs_level[d] = m.obs_level[o]; g.obs_edgelet[d] = m.obs_edgelet[o];
-      g.obs_grad[2 * d] = m.obs_grad[2 * o]; g.obs_grad[2 * d + 1] = m.obs_grad[2 * o + 1];
-    }
+    if (i != INT_MAX) obs_store(g, d++, obs_of_feature(ft, i, k));
+    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o) obs_store(g, d++, obs_load(m, o));
   }
-  // ---- MapPointCandidates::addCandidatePointToFrame: a candidate the frame observes becomes a map point
+  // ---- MapPointCandidates::addCandidatePointToFrame: a candidate the frame observes becomes a map point; the others stay
   for (int c = t; c < m.n_candidates; c += nt) {
     const int p = m.cand_point[c];
-    const bool promoted = p >= 0 && mark[p] != INT_MAX;
     int seed = -2;
-    if (promoted) {
+    if (p >= 0 && mark[p] != INT_MAX) {
       const int o0 = m.pt_obs_offset[p], o1 = m.pt_obs_offset[p + 1];
       seed = o1 > o0 ? m.obs_kf[o1 - 1] : -1;                                  // it->second->frame (none: that keyframe left the map)
       m.pt_type[p] = TYPE_UNKNOWN; m.pt_n_failed[p] = 0;
       atomicAdd(&s_n_promoted, 1);
     }
-    g.cand_seed[c] = seed;
-    g.cand_scan[c] = p >= 0 && !promoted ? 1 : 0;
+    sc.cand_seed[c] = seed;                                                    // (read back by this thread in the compaction, by all behind its barriers)
   }
-  __syncthreads();
-  block_exclusive_scan(g.cand_scan, m.n_candidates, s_part);
-  for (int c = t; c < m.n_candidates; c += nt) {
-    const int p = m.cand_point[c];
-    if (p >= 0 && g.cand_seed[c] == -2) g.cand_point[g.cand_scan[c]] = p;
-  }
+  block_compact(m.n_candidates, sc.cand_scan, s_part, [&](int c) { return m.cand_point[c] >= 0 && sc.cand_seed[c] == -2; },
+                [&](int r, int c) { g.cand_point[r] = m.cand_point[c]; });
   // ---- the keyframes' feature rows: the old row, then the promoted seeds of that keyframe in list order; the new keyframe's row
   for (int kk = t; kk <= k; kk += nt) {
     int cnt = s_fscan[n_feat];
     if (kk < k) {
       cnt = m.kf_ftr_offset[kk + 1] - m.kf_ftr_offset[kk];
-      for (int c = 0; c < m.n_candidates; ++c) cnt += g.cand_seed[c] == kk ? 1 : 0;
+      for (int c = 0; c < m.n_candidates; ++c) cnt += sc.cand_seed[c] == kk ? 1 : 0;
     }
     g.kf_ftr_offset[kk] = cnt;
   }
@@ -692,32 +720,24 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_promote_kernel(TrkMap m, TrkG
   for (int kk = t; kk < k; kk += nt) {
     int at = g.kf_ftr_offset[kk] + m.kf_ftr_offset[kk + 1] - m.kf_ftr_offset[kk];
     for (int c = 0; c < m.n_candidates; ++c)
-      if (g.cand_seed[c] == kk) g.kf_ftr_point[at++] = m.cand_point[c];
+      if (sc.cand_seed[c] == kk) g.kf_ftr_point[at++] = m.cand_point[c];
   }
-  {
-    const int base = g.kf_ftr_offset[k];
-    for (int i = t; i < n_feat; i += nt) {
-      const int p = last.point[i];
-      if (p >= 0) g.kf_ftr_point[base + s_fscan[i]] = p;
-    }
+  const int row_k = g.kf_ftr_offset[k];
+  for (int i = t; i < n_feat; i += nt) {
+    const int p = last.point[i];
+    if (p >= 0) g.kf_ftr_point[row_k + s_fscan[i]] = p;
   }
   // ---- Frame::setKeyPoints (S/frame.cpp:84-146) from five empty slots over the features with a point, in fts_ order
   const int cu = cam.width / 2, cv = cam.height / 2;
-  if (t < 256) {
-    KeyBest best;
-    key_best_init(best);
-    for (int i = t; i < n_feat; i += 256)
+  KeyBest best;
+  key_best_init(best);
+  if (t < KEY_THREADS)
+    for (int i = t; i < n_feat; i += KEY_THREADS)
       if (last.point[i] >= 0) key_best_offer(best, cu, cv, i, ft.px[2 * i], ft.px[2 * i + 1]);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) { s_best_val[j][t] = best.v[j]; s_best_idx[j][t] = best.i[j]; }
-  }
-  __syncthreads();
-  if (t < 5) {
-    double bv;
-    int bi;
-    const bool challenger = key_best_reduce(t, s_best_val[t], s_best_idx[t], 256, &bv, &bi);
-    kf_key_point[5 * k + t] = challenger ? last.point[bi] : -1;
-  }
+  double bv;
+  int bi;
+  const bool challenger = key_best_select(best, &bv, &bi);
+  if (t < 5) kf_key_point[5 * k + t] = challenger ? last.point[bi] : -1;
   if (t < 7) {                                                                  // the pose as the frame left it
     const double v = last.T_f_w[t];
     T_kf_w[7 * (size_t)k + t] = v;
@@ -725,10 +745,10 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_promote_kernel(TrkMap m, TrkG
   }
   if (t == 0) {
     kf_slot[k] = slot;
-    g.out[0] = s_n_promoted;
-    g.out[1] = g.kf_ftr_offset[k + 1];
-    g.out[2] = g.pt_obs_offset[m.n_points];
-    g.out[3] = g.cand_scan[m.n_candidates];
+    sc.out[0] = s_n_promoted;
+    sc.out[1] = g.kf_ftr_offset[k + 1];
+    sc.out[2] = g.pt_obs_offset[m.n_points];
+    sc.out[3] = sc.cand_scan[m.n_candidates];
   }
 }
 
@@ -748,18 +768,28 @@ SVO_DEV void rows_move_down(T* a, int first, int n_rows) {
   if (t + nt < n) dst[t + nt] = v1;
 }
 
+// feature i of the last frame loses its point (Map::safeDeletePoint clears ftr->point of every observation), and the solver
+// its copy of it: what it holds of a feature without a point
+SVO_DEV void last_feature_loses_point(const TrkLast& last, int i) {
+  last.point[i] = -1;
+  if (i < last.sia_max_n) {
+    last.sia_has_point[i] = 0;
+    last.sia_pos[3 * i] = 0.0; last.sia_pos[3 * i + 1] = 0.0; last.sia_pos[3 * i + 2] = 1.0;
+  }
+}
+
 // ---- keyframe k leaves the map: Map::safeDeleteFrame (S/map.cpp:41-64) on the tables.  removePtFrameRef (:66-80) over the
 // keyframe's features that have a point: a point with at most two observations is deleted (safeDeletePoint :82-93, deletePoint
 // :95-99), any other loses its observation in k (Point::deleteFrameRef, S/point.cpp:75-86).  A point has one feature per keyframe
 // at most, so the decisions are independent.  removeFrameCandidates / deleteCandidate (:271-285, :297-304): the candidates whose
-// seed feature (the last observation of their range) lies in k are deleted.  The tables whose entries move are rebuilt into the
-// second set in the form a host flatten gives them: an unlinked point -- by this call or by an earlier frame -- has no
-// observations, is in no feature row and not in the candidate list; row order and observation order are kept, keyframes above k
-// move down by one.  The key points of the other keyframes are left to trk_rekey_kernel (the deleted points are unlinked).  A
-// feature of the last frame whose point was deleted here loses it (safeDeletePoint clears ftr->point of every observation).
-// One workgroup of TRK_THREADS; mark: per-point scratch.
-__global__ __launch_bounds__(TRK_THREADS) void trk_remove_kernel(TrkMap m, TrkGrow g, double* __restrict__ T_kf_w, int* __restrict__ kf_slot,
-                                                                 int* __restrict__ kf_key_point, int* __restrict__ mark, TrkLast last, int k, int n_ftr) {
+// seed feature (the last observation of their range) lies in k are deleted.  The second set receives the tables in the form a
+// host flatten gives them: an unlinked point -- by this call or by an earlier frame -- has no observations, is in no feature
+// row and not in the candidate list; row order and observation order are kept, keyframes above k move down by one.  The key
+// points of the other keyframes are left to trk_rekey_kernel (the deleted points are unlinked).  A feature of the last frame
+// whose point was deleted here loses it.  out[0]: deleted points, out[4]: deleted candidates.
+__global__ __launch_bounds__(TRK_THREADS) void trk_remove_kernel(TrkMap m, TrkTables g, TrkScratch sc, double* __restrict__ T_kf_w,
+                                                                 int* __restrict__ kf_slot, int* __restrict__ kf_key_point, int* __restrict__ mark,
+                                                                 TrkLast last, int k, int n_ftr) {
   __shared__ int s_part[TRK_THREADS];
   __shared__ int s_del_points, s_del_cands;
   const int t = threadIdx.x, nt = blockDim.x;
@@ -769,14 +799,14 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_remove_kernel(TrkMap m, TrkGr
   __syncthreads();
   // ---- the decisions: mark[p] = 1 deleted as a map point, 2 deleted as a candidate
   const int r0 = m.kf_ftr_offset[k], r1 = m.kf_ftr_offset[k + 1];
+  auto linked = [&](int p) { return p >= 0 && !m.pt_unlinked[p]; };             // ftr->point != NULL
   for (int i = r0 + t; i < r1; i += nt) {
     const int p = m.kf_ftr_point[i];
-    if (p < 0 || m.pt_unlinked[p]) continue;                                     // ftr->point == NULL
-    if (m.pt_obs_offset[p + 1] - m.pt_obs_offset[p] <= 2) mark[p] = 1;         // pt->obs_.size() <= 2
+    if (linked(p) && m.pt_obs_offset[p + 1] - m.pt_obs_offset[p] <= 2) mark[p] = 1;      // pt->obs_.size() <= 2
   }
   for (int c = t; c < m.n_candidates; c += nt) {
     const int p = m.cand_point[c];
-    if (p < 0 || m.pt_unlinked[p]) continue;
+    if (!linked(p)) continue;
     const int o0 = m.pt_obs_offset[p], o1 = m.pt_obs_offset[p + 1];
     if (o1 > o0 && m.obs_kf[o1 - 1] == k) mark[p] = 2;                           // it->second->frame == frame
   }
@@ -804,39 +834,19 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_remove_kernel(TrkMap m, TrkGr
     if (m.pt_unlinked[p]) continue;
     size_t d = (size_t)g.pt_obs_offset[p];
     for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o) {
-      const int kf = m.obs_kf[o];
-      if (kf == k) continue;
-      g.obs_kf[d] = kf > k ? kf - 1 : kf;
-      g.obs_px[2 * d] = m.obs_px[2 * o]; g.obs_px[2 * d + 1] = m.obs_px[2 * o + 1];
-      g.obs_f[3 * d] = m.obs_f[3 * o]; g.obs_f[3 * d + 1] = m.obs_f[3 * o + 1]; g.obs_f[3 * d + 2] = m.obs_f[3 * o + 2];
-      g.obs_level[d] = m.obs_level[o]; g.obs_edgelet[d] = m.obs_edgelet[o];
-      g.obs_grad[2 * d] = m.obs_grad[2 * o]; g.obs_grad[2 * d + 1] = m.obs_grad[2 * o + 1];
-      ++d;
+      ObsRow r = obs_load(m, o);
+      if (r.kf == k) continue;
+      if (r.kf > k) --r.kf;
+      obs_store(g, d++, r);
     }
   }
   // ---- the feature rows: row k goes, the others keep the entries that still have a point
-  for (int i = t; i < n_ftr; i += nt) {
-    const int p = m.kf_ftr_point[i];
-    g.ftr_scan[i] = (i < r0 || i >= r1) && p >= 0 && !m.pt_unlinked[p] ? 1 : 0;
-  }
-  __syncthreads();
-  block_exclusive_scan(g.ftr_scan, n_ftr, s_part);
-  for (int i = t; i < n_ftr; i += nt) {
-    const int p = m.kf_ftr_point[i];
-    if ((i < r0 || i >= r1) && p >= 0 && !m.pt_unlinked[p]) g.kf_ftr_point[g.ftr_scan[i]] = p;
-  }
-  for (int j = t; j < K; j += nt) g.kf_ftr_offset[j] = g.ftr_scan[m.kf_ftr_offset[j < k ? j : j + 1]];      // (K - 1 rows, K offsets)
+  block_compact(n_ftr, sc.ftr_scan, s_part, [&](int i) { return (i < r0 || i >= r1) && linked(m.kf_ftr_point[i]); },
+                [&](int r, int i) { g.kf_ftr_point[r] = m.kf_ftr_point[i]; });
+  for (int j = t; j < K; j += nt) g.kf_ftr_offset[j] = sc.ftr_scan[m.kf_ftr_offset[j < k ? j : j + 1]];    // (K - 1 rows, K offsets)
   // ---- the candidate list, compacted
-  for (int c = t; c < m.n_candidates; c += nt) {
-    const int p = m.cand_point[c];
-    g.cand_scan[c] = p >= 0 && !m.pt_unlinked[p] ? 1 : 0;
-  }
-  __syncthreads();
-  block_exclusive_scan(g.cand_scan, m.n_candidates, s_part);
-  for (int c = t; c < m.n_candidates; c += nt) {
-    const int p = m.cand_point[c];
-    if (p >= 0 && !m.pt_unlinked[p]) g.cand_point[g.cand_scan[c]] = p;
-  }
+  block_compact(m.n_candidates, sc.cand_scan, s_part, [&](int c) { return linked(m.cand_point[c]); },
+                [&](int r, int c) { g.cand_point[r] = m.cand_point[c]; });
   // ---- the keyframe tables
   rows_move_down<double, 7>(T_kf_w, k, K);
   rows_move_down<int, 5>(kf_key_point, k, K);
@@ -845,19 +855,14 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_remove_kernel(TrkMap m, TrkGr
   const int n_last = *last.n;
   for (int i = t; i < n_last; i += nt) {
     const int p = last.point[i];
-    if (p < 0 || p >= P || !mark[p]) continue;
-    last.point[i] = -1;
-    if (i < last.sia_max_n) {                                                    // what the solver holds of a feature without a point
-      last.sia_has_point[i] = 0;
-      last.sia_pos[3 * i] = 0.0; last.sia_pos[3 * i + 1] = 0.0; last.sia_pos[3 * i + 2] = 1.0;
-    }
+    if (p >= 0 && p < P && mark[p]) last_feature_loses_point(last, i);
   }
   if (t == 0) {
-    g.out[0] = s_del_points;
-    g.out[1] = g.ftr_scan[n_ftr];
-    g.out[2] = g.pt_obs_offset[P];
-    g.out[3] = g.cand_scan[m.n_candidates];
-    g.out[4] = s_del_cands;
+    sc.out[0] = s_del_points;
+    sc.out[1] = sc.ftr_scan[n_ftr];
+    sc.out[2] = g.pt_obs_offset[P];
+    sc.out[3] = sc.cand_scan[m.n_candidates];
+    sc.out[4] = s_del_cands;
   }
 }
 
@@ -867,22 +872,22 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_remove_kernel(TrkMap m, TrkGr
 // feature-row entry and no candidate entry of a dead point, -1 entries dropped, every order kept.
 // What holds a point index, and what becomes of it here:
 //   kf_key_point, kf_ftr_point, cand_point        rewritten (the pending re-selection of key points has run before the launch)
-//   TrkLast::point (the last frame's features)    rewritten; a feature whose point is dead gets -1 and the solver's copy of
-//                                                 it is cleared as trk_remove_kernel does (none after a tracked frame)
+//   TrkLast::point (the last frame's features)    rewritten; a feature whose point is dead loses it as in trk_remove_kernel
+//                                                 (none after a tracked frame)
 //   the solver's slot (sia_pos, sia_has_point)    holds positions and flags by feature, no index
 //   the pt_* rows, pt_unlinked, pt_obs_offset     the rows of the living points move down, the offsets are rebuilt
 //   TrkPlan::first_seq / item_point / cand_point, TrkFeat::point, TrkStructSel: scratch of one call, rebuilt by the next
 //   svo_hip_tracker::last_max_point               host side: set from out[4] (svo_hip_tracker_compact_points)
 //   svo_hip_tracker::track_n_points and the page-locked result block: NOT rewritten -- svo_hip_tracker_last_result keeps
 //                                                 returning the frame under the numbering it was tracked with
-// mark[p] (per-point scratch) receives old_to_new: the new index, -1 for a dead point; the host copies it out.
-// The observation CSR, the feature rows and the candidate list are rebuilt into the second set.  The pt_* rows have no second
-// set: they move down in place by an ascending walk in chunks of one block -- every thread reads the row of its point of the
-// chunk into registers, a barrier, then writes it to its new index.  A new index is never above the old one, so the writes of a
-// chunk land on rows of this chunk (read before the barrier) or of earlier chunks (read in earlier rounds), never on a row a
-// later chunk has yet to read: one barrier a chunk is enough.  One workgroup of TRK_THREADS.
-__global__ __launch_bounds__(TRK_THREADS) void trk_compact_kernel(TrkMap m, TrkGrow g, double* __restrict__ pt_pos, int* __restrict__ kf_key_point,
-                                                                  int* __restrict__ mark, TrkLast last, int n_ftr) {
+// mark[p] receives old_to_new: the new index, -1 for a dead point; the host copies it out.  out[0]: the points afterwards.
+// The observation CSR, the feature rows and the candidate list go to the second set.  The pt_* rows have no second set: they
+// move down in place by an ascending walk in chunks of one block -- every thread reads the row of its point of the chunk into
+// registers, a barrier, then writes it to its new index.  A new index is never above the old one, so the writes of a chunk land
+// on rows of this chunk (read before the barrier) or of earlier chunks (read in earlier rounds), never on a row a later chunk
+// has yet to read: one barrier a chunk is enough.
+__global__ __launch_bounds__(TRK_THREADS) void trk_compact_kernel(TrkMap m, TrkTables g, TrkScratch sc, double* __restrict__ pt_pos,
+                                                                  int* __restrict__ kf_key_point, int* __restrict__ mark, TrkLast last, int n_ftr) {
   __shared__ int s_part[TRK_THREADS];
   __shared__ int s_last_max;
   const int t = threadIdx.x, nt = blockDim.x;
@@ -906,38 +911,16 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_compact_kernel(TrkMap m, TrkG
     const int q = mark[p];
     if (q < 0) continue;
     size_t d = (size_t)g.pt_obs_offset[q];
-    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o, ++d) {
-      g.obs_kf[d] = m.obs_kf[o];
-      g.obs_px[2 * d] = m.obs_px[2 * o]; g.obs_px[2 * d + 1] = m.obs_px[2 * o + 1];
-      g.obs_f[3 * d] = m.obs_f[3 * o]; g.obs_f[3 * d + 1] = m.obs_f[3 * o + 1]; g.obs_f[3 * d + 2] = m.obs_f[3 * o + 2];
-      g.obs_level[d] = m.obs_level[o]; g.obs_edgelet[d] = m.obs_edgelet[o];
-      g.obs_grad[2 * d] = m.obs_grad[2 * o]; g.obs_grad[2 * d + 1] = m.obs_grad[2 * o + 1];
-    }
+    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o) obs_store(g, d++, obs_load(m, o));
   }
-  // ---- the feature rows keep the entries that still have a point
-  for (int i = t; i < n_ftr; i += nt) {
-    const int p = m.kf_ftr_point[i];
-    g.ftr_scan[i] = p >= 0 && mark[p] >= 0 ? 1 : 0;
-  }
-  __syncthreads();
-  block_exclusive_scan(g.ftr_scan, n_ftr, s_part);
-  for (int i = t; i < n_ftr; i += nt) {
-    const int p = m.kf_ftr_point[i];
-    if (p >= 0 && mark[p] >= 0) g.kf_ftr_point[g.ftr_scan[i]] = mark[p];
-  }
+  // ---- the feature rows and the candidate list keep the entries that still have a point, under its new index
+  auto living = [&](int p) { return p >= 0 && mark[p] >= 0; };
+  block_compact(n_ftr, sc.ftr_scan, s_part, [&](int i) { return living(m.kf_ftr_point[i]); },
+                [&](int r, int i) { g.kf_ftr_point[r] = mark[m.kf_ftr_point[i]]; });
   if (K > 0)                                                                     // (a map without keyframes has no offsets)
-    for (int j = t; j <= K; j += nt) g.kf_ftr_offset[j] = g.ftr_scan[m.kf_ftr_offset[j]];
-  // ---- the candidate list
-  for (int c = t; c < m.n_candidates; c += nt) {
-    const int p = m.cand_point[c];
-    g.cand_scan[c] = p >= 0 && mark[p] >= 0 ? 1 : 0;
-  }
-  __syncthreads();
-  block_exclusive_scan(g.cand_scan, m.n_candidates, s_part);
-  for (int c = t; c < m.n_candidates; c += nt) {
-    const int p = m.cand_point[c];
-    if (p >= 0 && mark[p] >= 0) g.cand_point[g.cand_scan[c]] = mark[p];
-  }
+    for (int j = t; j <= K; j += nt) g.kf_ftr_offset[j] = sc.ftr_scan[m.kf_ftr_offset[j]];
+  block_compact(m.n_candidates, sc.cand_scan, s_part, [&](int c) { return living(m.cand_point[c]); },
+                [&](int r, int c) { g.cand_point[r] = mark[m.cand_point[c]]; });
   // ---- the key points (none is dead after the re-selection; one that were would become -1)
   for (int j = t; j < 5 * K; j += nt) {
     const int p = kf_key_point[j];
@@ -950,12 +933,9 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_compact_kernel(TrkMap m, TrkG
     const int p = last.point[i];
     if (p < 0 || p >= P) continue;
     const int q = mark[p];
+    if (q < 0) { last_feature_loses_point(last, i); continue; }
     last.point[i] = q;
     if (q > last_max) last_max = q;
-    if (q < 0 && i < last.sia_max_n) {                                           // what the solver holds of a feature without a point
-      last.sia_has_point[i] = 0;
-      last.sia_pos[3 * i] = 0.0; last.sia_pos[3 * i + 1] = 0.0; last.sia_pos[3 * i + 2] = 1.0;
-    }
   }
   if (last_max >= 0) atomicMax(&s_last_max, last_max);
   // ---- the rows of the points move down in place (see above: read, barrier, write, chunk by chunk upwards).  From here on
@@ -978,11 +958,11 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_compact_kernel(TrkMap m, TrkG
   }
   __syncthreads();
   if (t == 0) {
-    g.out[0] = N;
-    g.out[1] = g.ftr_scan[n_ftr];
-    g.out[2] = g.pt_obs_offset[N];
-    g.out[3] = g.cand_scan[m.n_candidates];
-    g.out[4] = s_last_max;
+    sc.out[0] = N;
+    sc.out[1] = sc.ftr_scan[n_ftr];
+    sc.out[2] = g.pt_obs_offset[N];
+    sc.out[3] = sc.cand_scan[m.n_candidates];
+    sc.out[4] = s_last_max;
   }
 }
 
@@ -1152,12 +1132,14 @@ __global__ void trk_scatter_positions_kernel(int n, const int* __restrict__ idx,
   pt_pos[3 * p] = pos[3 * i]; pt_pos[3 * p + 1] = pos[3 * i + 1]; pt_pos[3 * p + 2] = pos[3 * i + 2];
 }
 
+// device memory for count elements, recorded in got (whose owner frees it); a no-op once *rc holds an error
 template <typename T>
-int trk_alloc(svo_hip_ctx* ctx, T** p, size_t count) {
+void trk_alloc(svo_hip_ctx* ctx, std::vector<void*>* got, int* rc, T** p, size_t count) {
+  if (*rc != SVO_HIP_OK) return;
   void* d = nullptr;
-  const int rc = svo_hip_malloc(ctx, &d, (count ? count : 1) * sizeof(T));
+  *rc = svo_hip_malloc(ctx, &d, (count ? count : 1) * sizeof(T));
   *p = (T*)d;
-  return rc;
+  if (*rc == SVO_HIP_OK) got->push_back(d);
 }
 
 }  // namespace
@@ -1200,17 +1182,20 @@ struct svo_hip_tracker {
   svo_hip_tracker_shared* sh = nullptr;     // owned by the tracker itself (a lone tracker) or by its group
   bool owns_shared = false;
   int cam_index = 0;                        // this camera's slot in the shared solver / frame pyramids / per-camera arrays
-  // map tables
-  double *T_kf_w = nullptr, *T_slot_w = nullptr, *pt_pos = nullptr, *obs_px = nullptr, *obs_f = nullptr, *obs_grad = nullptr;
-  int *kf_slot = nullptr, *kf_key_point = nullptr, *kf_ftr_offset = nullptr, *kf_ftr_point = nullptr, *pt_type = nullptr, *pt_n_failed = nullptr,
-      *pt_n_succeeded = nullptr, *pt_obs_offset = nullptr, *obs_kf = nullptr, *obs_level = nullptr, *cand_point = nullptr;
-  uint8_t *pt_unlinked = nullptr, *obs_edgelet = nullptr;
+  // map tables: the ones that are edited where they lie ...
+  double *T_kf_w = nullptr, *T_slot_w = nullptr, *pt_pos = nullptr;
+  int *kf_slot = nullptr, *kf_key_point = nullptr, *pt_type = nullptr, *pt_n_failed = nullptr, *pt_n_succeeded = nullptr;
+  uint8_t* pt_unlinked = nullptr;
+  // ... and the ones a rebuild (promotion, removal, renumbering) writes anew: tables[cur] is the map's set, the other one and
+  // the kernels' scratch are allocated by whichever rebuild runs first (trk_rebuild_begin)
+  TrkTables tables[2]{};
+  int cur = 0;
+  TrkScratch scratch{};
+  bool have_second = false;
   int n_kf = 0, n_points = 0, n_candidates = 0;
   int n_ftr = 0, n_obs = 0;                 // entries of kf_ftr_point / of the observation tables
   std::vector<int> kf_slot_host;            // kf_slot as the device holds it (svo_hip_tracker_promote_last_frame checks against it)
   int track_n_points = 0;                   // n_points when the last frame was tracked: the layout of the counters in the result block
-  TrkGrow grow{};                           // the second set of tables a promotion rebuilds into (allocated by the first one)
-  bool have_grow = false;
   bool have_map = false, have_last = false;
   bool rekey_pending = false;               // the last frame deleted points: keyframes that lost a key feature choose again before the next frame
   int last_n_host = 0;
@@ -1247,12 +1232,72 @@ TrkMap make_map(const svo_hip_tracker* t) {
   TrkMap m;
   memset(&m, 0, sizeof(m));                 // (no stray padding bytes: trk_track_all compares argument tables byte by byte)
   m.n_kf = t->n_kf; m.n_points = t->n_points; m.n_candidates = t->n_candidates;
-  m.T_kf_w = t->T_kf_w; m.kf_slot = t->kf_slot; m.kf_key_point = t->kf_key_point; m.kf_ftr_offset = t->kf_ftr_offset;
-  m.kf_ftr_point = t->kf_ftr_point; m.pt_pos = t->pt_pos; m.pt_type = t->pt_type; m.pt_n_failed = t->pt_n_failed;
-  m.pt_n_succeeded = t->pt_n_succeeded; m.pt_unlinked = t->pt_unlinked; m.pt_obs_offset = t->pt_obs_offset; m.obs_kf = t->obs_kf;
-  m.obs_px = t->obs_px; m.obs_f = t->obs_f; m.obs_level = t->obs_level; m.obs_edgelet = t->obs_edgelet; m.obs_grad = t->obs_grad;
-  m.cand_point = t->cand_point;
+  m.T_kf_w = t->T_kf_w; m.kf_slot = t->kf_slot; m.kf_key_point = t->kf_key_point; m.pt_pos = t->pt_pos; m.pt_type = t->pt_type;
+  m.pt_n_failed = t->pt_n_failed; m.pt_n_succeeded = t->pt_n_succeeded; m.pt_unlinked = t->pt_unlinked;
+  const TrkTables& tb = t->tables[t->cur];
+  m.kf_ftr_offset = tb.kf_ftr_offset; m.kf_ftr_point = tb.kf_ftr_point; m.pt_obs_offset = tb.pt_obs_offset; m.obs_kf = tb.obs_kf;
+  m.obs_px = tb.obs_px; m.obs_f = tb.obs_f; m.obs_level = tb.obs_level; m.obs_edgelet = tb.obs_edgelet; m.obs_grad = tb.obs_grad;
+  m.cand_point = tb.cand_point;
   return m;
+}
+
+// a set of tables at the capacities of the configuration (the one place that states them); what was allocated is appended to
+// got, also when a later allocation fails.  kf_ftr_offset: max_keyframes + 1 entries hold the largest index a kernel writes --
+// the total of trk_promote_kernel's scan over n_kf + 1 <= max_keyframes rows, trk_compact_kernel's entry n_kf.
+int trk_tables_alloc(svo_hip_ctx* ctx, const svo_hip_tracker_config& c, TrkTables* tb, std::vector<void*>* got) {
+  int rc = SVO_HIP_OK;
+  auto D = [&](auto** p, size_t count) { trk_alloc(ctx, got, &rc, p, count); };
+  const size_t K = c.max_keyframes, P = c.max_points, O = c.max_obs, F = c.max_kf_features, CN = c.max_candidates > 0 ? c.max_candidates : 1;
+  D(&tb->pt_obs_offset, P + 1); D(&tb->obs_kf, O); D(&tb->obs_px, O * 2); D(&tb->obs_f, O * 3); D(&tb->obs_level, O); D(&tb->obs_edgelet, O);
+  D(&tb->obs_grad, O * 2); D(&tb->kf_ftr_offset, K + 1); D(&tb->kf_ftr_point, F); D(&tb->cand_point, CN);
+  return rc;
+}
+
+// the pending re-selection of key points (the last frame deleted points), before anything reads or extends the feature rows
+int trk_rekey_now(svo_hip_tracker* t) {
+  svo_hip_ctx* ctx = t->ctx;
+  if (t->rekey_pending && t->n_kf > 0) {
+    hipLaunchKernelGGL(trk_rekey_kernel, dim3(t->n_kf), dim3(KEY_THREADS), 0, ctx->stream, make_map(t), t->kf_key_point, svo_make_cam(t->cam));
+    SVO_CHECK_HIP(ctx, hipGetLastError());
+  }
+  t->rekey_pending = false;
+  return SVO_HIP_OK;
+}
+
+// What a promotion, a removal and a renumbering have in common around their launch.  Before it: the map has to be there, then
+// the caller's own checks (a refused call changes nothing and enqueues nothing); the second table set and the scratch exist
+// from the first rebuild on; the re-selection owed to the last frame's deletions sees the rows as they were.
+template <typename Checks>
+int trk_rebuild_begin(svo_hip_tracker* t, const char* who, Checks own_checks) {
+  svo_hip_ctx* ctx = t->ctx;
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no map has been set");
+  int rc = own_checks();
+  if (rc != SVO_HIP_OK) return rc;
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  if (!t->have_second) {
+    const size_t F = t->cfg.max_kf_features, CN = t->cfg.max_candidates > 0 ? t->cfg.max_candidates : 1;
+    TrkTables tb{};
+    TrkScratch sc{};
+    std::vector<void*> got;
+    rc = trk_tables_alloc(ctx, t->cfg, &tb, &got);
+    auto D = [&](int** p, size_t count) { trk_alloc(ctx, &got, &rc, p, count); };
+    D(&sc.cand_seed, CN); D(&sc.cand_scan, CN + 1); D(&sc.ftr_scan, F + 1); D(&sc.out, 8);
+    if (rc != SVO_HIP_OK) { for (void* p : got) (void)hipFree(p); return rc; }
+    t->dev_allocs.insert(t->dev_allocs.end(), got.begin(), got.end());
+    t->tables[1 - t->cur] = tb; t->scratch = sc; t->have_second = true;
+  }
+  return trk_rekey_now(t);
+}
+
+// After it: the first n_out counts of the kernel come back (out[1..3]: the entries of the feature rows, of the observation
+// tables and of the candidate list), and the set the kernel wrote is the map's from here on.
+int trk_rebuild_end(svo_hip_tracker* t, int* out, int n_out) {
+  svo_hip_ctx* ctx = t->ctx;
+  SVO_CHECK_HIP(ctx, hipMemcpyAsync(out, t->scratch.out, (size_t)n_out * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  t->cur = 1 - t->cur;
+  t->n_ftr = out[1]; t->n_obs = out[2]; t->n_candidates = out[3];
+  return SVO_HIP_OK;
 }
 
 }  // namespace
@@ -1326,11 +1371,7 @@ static int trk_shared_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const 
   sh->ctx = ctx; sh->n_cams = n_cams;
   int rc = SVO_HIP_OK;
   auto A = [&](int r) { if (rc == SVO_HIP_OK) rc = r; };
-  auto D = [&](auto** p, size_t count) {
-    if (rc != SVO_HIP_OK) return;
-    rc = trk_alloc(ctx, p, count);
-    if (rc == SVO_HIP_OK) sh->dev_allocs.push_back((void*)*p);
-  };
+  auto D = [&](auto** p, size_t count) { trk_alloc(ctx, &sh->dev_allocs, &rc, p, count); };
   A(svo_hip_pyramid_create(ctx, cam->width, cam->height, cfg->n_levels, n_cams * cfg->max_keyframes, &sh->kf_pyr));
   for (int i = 0; i < 2; ++i) A(svo_hip_pyramid_create(ctx, cam->width, cam->height, cfg->n_levels, n_cams, &sh->frame_pyr[i]));
   A(svo_hip_sia_create(ctx, n_cams, cfg->max_frame_features, &sh->sia));
@@ -1362,15 +1403,11 @@ static int trk_member_create(svo_hip_tracker_shared* sh, int index, const svo_hi
   t->grid_rows = (cam->height + cfg->grid_size - 1) / cfg->grid_size;
   t->n_cells = t->grid_cols * t->grid_rows;
   int rc = SVO_HIP_OK;
-  auto D = [&](auto** p, size_t count) {
-    if (rc != SVO_HIP_OK) return;
-    rc = trk_alloc(ctx, p, count);
-    if (rc == SVO_HIP_OK) t->dev_allocs.push_back((void*)*p);
-  };
+  auto D = [&](auto** p, size_t count) { trk_alloc(ctx, &t->dev_allocs, &rc, p, count); };
   const size_t K = cfg->max_keyframes, P = cfg->max_points, O = cfg->max_obs, F = cfg->max_kf_features, CN = cfg->max_candidates > 0 ? cfg->max_candidates : 1;
-  D(&t->T_kf_w, K * 7); D(&t->T_slot_w, K * 7); D(&t->kf_slot, K); D(&t->kf_key_point, K * 5); D(&t->kf_ftr_offset, K + 1); D(&t->kf_ftr_point, F);
-  D(&t->pt_pos, P * 3); D(&t->pt_type, P); D(&t->pt_n_failed, P); D(&t->pt_n_succeeded, P); D(&t->pt_unlinked, P); D(&t->pt_obs_offset, P + 1);
-  D(&t->obs_kf, O); D(&t->obs_px, O * 2); D(&t->obs_f, O * 3); D(&t->obs_level, O); D(&t->obs_edgelet, O); D(&t->obs_grad, O * 2); D(&t->cand_point, CN);
+  D(&t->T_kf_w, K * 7); D(&t->T_slot_w, K * 7); D(&t->kf_slot, K); D(&t->kf_key_point, K * 5);
+  D(&t->pt_pos, P * 3); D(&t->pt_type, P); D(&t->pt_n_failed, P); D(&t->pt_n_succeeded, P); D(&t->pt_unlinked, P);
+  if (rc == SVO_HIP_OK) rc = trk_tables_alloc(ctx, *cfg, &t->tables[0], &t->dev_allocs);
   TrkPlan& pl = t->pl;
   const size_t C = cfg->max_items, NC = t->n_cells;
   pl.cap = cfg->max_items; pl.n_cells = t->n_cells; pl.grid_cols = t->grid_cols; pl.grid_size = cfg->grid_size; pl.max_n_kfs = cfg->reproj_max_n_kfs;
@@ -1502,15 +1539,16 @@ int svo_hip_tracker_set_map(svo_hip_tracker* t, const svo_hip_tracker_map* mp) {
     off += bytes;
   };
   const size_t K = mp->n_kf, P = mp->n_points;
+  const TrkTables& tb = t->tables[t->cur];
   put(t->T_kf_w, mp->T_kf_w, K * 56); put(t->kf_slot, mp->kf_slot, K * 4); put(t->kf_key_point, mp->kf_key_point, K * 20);
-  if (K) put(t->kf_ftr_offset, mp->kf_ftr_offset, (K + 1) * 4);
-  put(t->kf_ftr_point, mp->kf_ftr_point, (size_t)n_ftr * 4);
+  if (K) put(tb.kf_ftr_offset, mp->kf_ftr_offset, (K + 1) * 4);
+  put(tb.kf_ftr_point, mp->kf_ftr_point, (size_t)n_ftr * 4);
   put(t->pt_pos, mp->pt_pos, P * 24); put(t->pt_type, mp->pt_type, P * 4); put(t->pt_n_failed, mp->pt_n_failed, P * 4);
   put(t->pt_n_succeeded, mp->pt_n_succeeded, P * 4);
-  if (P) put(t->pt_obs_offset, mp->pt_obs_offset, (P + 1) * 4);
-  put(t->obs_kf, mp->obs_kf, (size_t)n_obs * 4); put(t->obs_px, mp->obs_px, (size_t)n_obs * 16); put(t->obs_f, mp->obs_f, (size_t)n_obs * 24);
-  put(t->obs_level, mp->obs_level, (size_t)n_obs * 4);
-  put(t->cand_point, mp->cand_point, (size_t)mp->n_candidates * 4);
+  if (P) put(tb.pt_obs_offset, mp->pt_obs_offset, (P + 1) * 4);
+  put(tb.obs_kf, mp->obs_kf, (size_t)n_obs * 4); put(tb.obs_px, mp->obs_px, (size_t)n_obs * 16); put(tb.obs_f, mp->obs_f, (size_t)n_obs * 24);
+  put(tb.obs_level, mp->obs_level, (size_t)n_obs * 4);
+  put(tb.cand_point, mp->cand_point, (size_t)mp->n_candidates * 4);
   // T_slot_w: the keyframe poses indexed by pyramid slot (what the matcher's batch indexes)
   {
     off = (off + 15) & ~(size_t)15;
@@ -1525,13 +1563,13 @@ int svo_hip_tracker_set_map(svo_hip_tracker* t, const svo_hip_tracker_map* mp) {
     off = (off + 15) & ~(size_t)15;
     uint8_t* ed = reinterpret_cast<uint8_t*>(hs + off);
     if (mp->obs_edgelet) memcpy(ed, mp->obs_edgelet, (size_t)n_obs); else memset(ed, 0, (size_t)n_obs);
-    if (e == hipSuccess) e = hipMemcpyAsync(t->obs_edgelet, ed, (size_t)n_obs, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tb.obs_edgelet, ed, (size_t)n_obs, hipMemcpyHostToDevice, ctx->stream);
     off += (size_t)n_obs;
     off = (off + 15) & ~(size_t)15;
     double* gr = reinterpret_cast<double*>(hs + off);
     if (mp->obs_grad) memcpy(gr, mp->obs_grad, (size_t)n_obs * 16);
     else for (int o = 0; o < n_obs; ++o) { gr[2 * o] = 1.0; gr[2 * o + 1] = 0.0; }
-    if (e == hipSuccess) e = hipMemcpyAsync(t->obs_grad, gr, (size_t)n_obs * 16, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tb.obs_grad, gr, (size_t)n_obs * 16, hipMemcpyHostToDevice, ctx->stream);
     off += (size_t)n_obs * 16;
   }
   if (e == hipSuccess && P) e = hipMemsetAsync(t->pt_unlinked, 0, P, ctx->stream);
@@ -1708,7 +1746,7 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
   for (int k = 0; k < N; ++k) {
     svo_hip_tracker* t = sh->members[(size_t)k];
     if (t->rekey_pending && t->n_kf > 0) {    // Map::safeDeletePoint of the previous frame: Frame::removeKeyPoint on the keyframes
-      hipLaunchKernelGGL(trk_rekey_kernel, dim3(t->n_kf), dim3(256), 0, ctx->stream, make_map(t), t->kf_key_point, cam);
+      hipLaunchKernelGGL(trk_rekey_kernel, dim3(t->n_kf), dim3(KEY_THREADS), 0, ctx->stream, make_map(t), t->kf_key_point, cam);
       SVO_CHECK_HIP(ctx, hipGetLastError());
     }
     t->rekey_pending = false;
@@ -1904,26 +1942,12 @@ int svo_hip_tracker_download_key_points(svo_hip_tracker* t, int32_t* kf_key_poin
   svo_hip_ctx* ctx = t->ctx;
   if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_download_key_points", "no map has been set");
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  if (t->rekey_pending && t->n_kf > 0) {
-    hipLaunchKernelGGL(trk_rekey_kernel, dim3(t->n_kf), dim3(256), 0, ctx->stream, make_map(t), t->kf_key_point, svo_make_cam(t->cam));
-    SVO_CHECK_HIP(ctx, hipGetLastError());
-  }
-  t->rekey_pending = false;
+  const int rc = trk_rekey_now(t);
+  if (rc != SVO_HIP_OK) return rc;
   if (t->n_kf > 0) {
     SVO_CHECK_HIP(ctx, hipMemcpyAsync(kf_key_point, t->kf_key_point, (size_t)t->n_kf * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
-  return SVO_HIP_OK;
-}
-
-// the pending re-selection of key points (the last frame deleted points), before anything reads or extends the feature rows
-static int trk_rekey_now(svo_hip_tracker* t) {
-  svo_hip_ctx* ctx = t->ctx;
-  if (t->rekey_pending && t->n_kf > 0) {
-    hipLaunchKernelGGL(trk_rekey_kernel, dim3(t->n_kf), dim3(256), 0, ctx->stream, make_map(t), t->kf_key_point, svo_make_cam(t->cam));
-    SVO_CHECK_HIP(ctx, hipGetLastError());
-  }
-  t->rekey_pending = false;
   return SVO_HIP_OK;
 }
 
@@ -1966,8 +1990,7 @@ int svo_hip_tracker_add_candidates(svo_hip_tracker* t, int n, const double* pos,
   }
   SVO_CHECK_HIP(ctx, hipMemcpyAsync(d, hs, bytes, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(trk_add_candidates_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, reinterpret_cast<const TrkCandRec*>(d),
-                     t->n_points, t->n_candidates, t->pt_pos, t->pt_type, t->pt_n_failed, t->pt_n_succeeded, t->pt_unlinked, t->pt_obs_offset,
-                     t->obs_kf, t->obs_px, t->obs_f, t->obs_level, t->obs_edgelet, t->obs_grad, t->cand_point);
+                     t->n_points, t->n_candidates, t->pt_pos, t->pt_type, t->pt_n_failed, t->pt_n_succeeded, t->pt_unlinked, t->tables[t->cur]);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   // existing indices keep their meaning: the last frame, the solver's copy of it and a pending re-selection stay as they are
   t->n_points += n; t->n_candidates += n; t->n_obs = at;
@@ -1975,75 +1998,40 @@ int svo_hip_tracker_add_candidates(svo_hip_tracker* t, int n, const double* pos,
   return SVO_HIP_OK;
 }
 
-// the second set of tables a promotion or a removal rebuilds into, at the capacities of the first: allocated by whichever runs first
-static int trk_grow_tables(svo_hip_tracker* t) {
-  if (t->have_grow) return SVO_HIP_OK;
-  svo_hip_ctx* ctx = t->ctx;
-  const svo_hip_tracker_config& c = t->cfg;
-  TrkGrow g;
-  memset(&g, 0, sizeof(g));
-  int rc = SVO_HIP_OK;
-  std::vector<void*> got;
-  auto D = [&](auto** p, size_t count) {
-    if (rc != SVO_HIP_OK) return;
-    rc = trk_alloc(ctx, p, count);
-    if (rc == SVO_HIP_OK) got.push_back((void*)*p);
-  };
-  const size_t K = c.max_keyframes, P = c.max_points, O = c.max_obs, F = c.max_kf_features, CN = c.max_candidates > 0 ? c.max_candidates : 1;
-  D(&g.pt_obs_offset, P + 1); D(&g.obs_kf, O); D(&g.obs_px, O * 2); D(&g.obs_f, O * 3); D(&g.obs_level, O); D(&g.obs_edgelet, O);
-  D(&g.obs_grad, O * 2); D(&g.kf_ftr_offset, K + 2); D(&g.kf_ftr_point, F); D(&g.cand_point, CN); D(&g.cand_seed, CN); D(&g.cand_scan, CN + 1);
-  D(&g.ftr_scan, F + 1); D(&g.out, 8);
-  if (rc != SVO_HIP_OK) { for (void* p : got) (void)hipFree(p); return rc; }
-  for (void* p : got) t->dev_allocs.push_back(p);
-  t->grow = g; t->have_grow = true;
-  return SVO_HIP_OK;
-}
-
-// the rebuilt tables are the map's from here on
-static void trk_swap_grown(svo_hip_tracker* t) {
-  TrkGrow& g = t->grow;
-  std::swap(t->pt_obs_offset, g.pt_obs_offset); std::swap(t->obs_kf, g.obs_kf); std::swap(t->obs_px, g.obs_px); std::swap(t->obs_f, g.obs_f);
-  std::swap(t->obs_level, g.obs_level); std::swap(t->obs_edgelet, g.obs_edgelet); std::swap(t->obs_grad, g.obs_grad);
-  std::swap(t->kf_ftr_offset, g.kf_ftr_offset); std::swap(t->kf_ftr_point, g.kf_ftr_point); std::swap(t->cand_point, g.cand_point);
-}
-
 int svo_hip_tracker_promote_last_frame(svo_hip_tracker* t, int slot, int* kf_index, int* n_promoted_candidates) {
   if (!t) return SVO_HIP_ERR_INVALID;
   svo_hip_ctx* ctx = t->ctx;
   const svo_hip_tracker_config& c = t->cfg;
   const char* who = "svo_hip_tracker_promote_last_frame";
-  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no map has been set");
-  // a frame from svo_hip_tracker_set_last_frame has no levels, edgelet flags or gradients
-  if (!t->have_last || !t->last_from_track) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "the last frame has to be a tracked one");
-  SVO_REQUIRE(ctx, slot >= 0 && slot < c.max_keyframes && t->n_kf < c.max_keyframes);
-  for (int k = 0; k < t->n_kf; ++k) SVO_REQUIRE(ctx, t->kf_slot_host[(size_t)k] != slot);
-  // the frame's features with a point, from the page-locked result block; every one is a new observation and a row entry of
-  // the new keyframe.  The promoted candidates add one row entry each at most, and each of them is one of those features:
-  // min(features with a point, candidates) bounds what the rows can gain beyond that.
   const int n_feat = t->last_n_host;
   const int32_t* fp = reinterpret_cast<const int32_t*>(t->res_host + t->o_point);
-  int n_with_point = 0;
-  for (int i = 0; i < n_feat; ++i) n_with_point += fp[i] >= 0 ? 1 : 0;
-  const int seeds_bound = n_with_point < t->n_candidates ? n_with_point : t->n_candidates;
-  SVO_REQUIRE(ctx, n_with_point <= c.max_obs - t->n_obs && n_with_point + seeds_bound <= c.max_kf_features - t->n_ftr);
-  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = trk_grow_tables(t);
-  if (rc != SVO_HIP_OK) return rc;
-  rc = trk_rekey_now(t);                    // (the re-selection owed to the last frame's deletions sees the rows as they were)
+  int rc = trk_rebuild_begin(t, who, [&]() -> int {
+    // a frame from svo_hip_tracker_set_last_frame has no levels, edgelet flags or gradients
+    if (!t->have_last || !t->last_from_track) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "the last frame has to be a tracked one");
+    SVO_REQUIRE(ctx, slot >= 0 && slot < c.max_keyframes && t->n_kf < c.max_keyframes);
+    for (int k = 0; k < t->n_kf; ++k) SVO_REQUIRE(ctx, t->kf_slot_host[(size_t)k] != slot);
+    // the frame's features with a point, from the page-locked result block; every one is a new observation and a row entry of
+    // the new keyframe.  The promoted candidates add one row entry each at most, and each of them is one of those features:
+    // min(features with a point, candidates) bounds what the rows can gain beyond that.
+    int n_with_point = 0;
+    for (int i = 0; i < n_feat; ++i) n_with_point += fp[i] >= 0 ? 1 : 0;
+    const int seeds_bound = n_with_point < t->n_candidates ? n_with_point : t->n_candidates;
+    SVO_REQUIRE(ctx, n_with_point <= c.max_obs - t->n_obs && n_with_point + seeds_bound <= c.max_kf_features - t->n_ftr);
+    return SVO_HIP_OK;
+  });
   if (rc != SVO_HIP_OK) return rc;
   rc = svo_hip_tracker_keyframe_from_last_frame(t, slot);
   if (rc != SVO_HIP_OK) return rc;
-  hipLaunchKernelGGL(trk_promote_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, make_map(t), t->grow, t->T_kf_w, t->T_slot_w, t->kf_slot,
-                     t->kf_key_point, t->pl.first_seq, t->ft, t->last, n_feat, slot, svo_make_cam(t->cam));
+  hipLaunchKernelGGL(trk_promote_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, make_map(t), t->tables[1 - t->cur], t->scratch, t->T_kf_w,
+                     t->T_slot_w, t->kf_slot, t->kf_key_point, t->pl.first_seq, t->ft, t->last, n_feat, slot, svo_make_cam(t->cam));
   SVO_CHECK_HIP(ctx, hipGetLastError());
   int out[4] = {0, 0, 0, 0};
-  SVO_CHECK_HIP(ctx, hipMemcpyAsync(out, t->grow.out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
-  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  trk_swap_grown(t);
+  rc = trk_rebuild_end(t, out, 4);
+  if (rc != SVO_HIP_OK) return rc;
   if (kf_index) *kf_index = t->n_kf;
   if (n_promoted_candidates) *n_promoted_candidates = out[0];
   t->kf_slot_host.push_back(slot);
-  t->n_kf += 1; t->n_ftr = out[1]; t->n_obs = out[2]; t->n_candidates = out[3];
+  t->n_kf += 1;
   if (!t->any_edgelet) {                    // the new observations carry the frame's edgelet flags
     const uint8_t* fe = reinterpret_cast<const uint8_t*>(t->res_host + t->o_edge);
     for (int i = 0; i < n_feat && !t->any_edgelet; ++i) t->any_edgelet = fp[i] >= 0 && fe[i] != 0;
@@ -2054,26 +2042,23 @@ int svo_hip_tracker_promote_last_frame(svo_hip_tracker* t, int slot, int* kf_ind
 int svo_hip_tracker_remove_keyframe(svo_hip_tracker* t, int kf_index, int* slot_freed, int* n_deleted_points, int* n_deleted_candidates) {
   if (!t) return SVO_HIP_ERR_INVALID;
   svo_hip_ctx* ctx = t->ctx;
-  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_remove_keyframe", "no map has been set");
-  // (the reference removes a keyframe only when Config::maxNKfs() > 2: the map never loses its only one)
-  SVO_REQUIRE(ctx, kf_index >= 0 && kf_index < t->n_kf && t->n_kf > 1);
-  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = trk_grow_tables(t);
+  int rc = trk_rebuild_begin(t, "svo_hip_tracker_remove_keyframe", [&]() -> int {
+    // (the reference removes a keyframe only when Config::maxNKfs() > 2: the map never loses its only one)
+    SVO_REQUIRE(ctx, kf_index >= 0 && kf_index < t->n_kf && t->n_kf > 1);
+    return SVO_HIP_OK;
+  });
   if (rc != SVO_HIP_OK) return rc;
-  rc = trk_rekey_now(t);                    // (the re-selection owed to the last frame's deletions sees the rows as they were)
-  if (rc != SVO_HIP_OK) return rc;
-  hipLaunchKernelGGL(trk_remove_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, make_map(t), t->grow, t->T_kf_w, t->kf_slot, t->kf_key_point,
-                     t->pl.first_seq, t->last, kf_index, t->n_ftr);
+  hipLaunchKernelGGL(trk_remove_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, make_map(t), t->tables[1 - t->cur], t->scratch, t->T_kf_w,
+                     t->kf_slot, t->kf_key_point, t->pl.first_seq, t->last, kf_index, t->n_ftr);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   int out[5] = {0, 0, 0, 0, 0};
-  SVO_CHECK_HIP(ctx, hipMemcpyAsync(out, t->grow.out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
-  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  trk_swap_grown(t);
+  rc = trk_rebuild_end(t, out, 5);
+  if (rc != SVO_HIP_OK) return rc;
   if (slot_freed) *slot_freed = t->kf_slot_host[(size_t)kf_index];
   if (n_deleted_points) *n_deleted_points = out[0];
   if (n_deleted_candidates) *n_deleted_candidates = out[4];
   t->kf_slot_host.erase(t->kf_slot_host.begin() + kf_index);
-  t->n_kf -= 1; t->n_ftr = out[1]; t->n_obs = out[2]; t->n_candidates = out[3];
+  t->n_kf -= 1;
   // the keyframes that lost a key feature to a point deleted here choose again (Frame::removeKeyPoint), on the new rows,
   // before anything reads the key points
   if (out[0] > 0) t->rekey_pending = true;
@@ -2083,23 +2068,18 @@ int svo_hip_tracker_remove_keyframe(svo_hip_tracker* t, int kf_index, int* slot_
 int svo_hip_tracker_compact_points(svo_hip_tracker* t, int* n_points_after, int32_t* old_to_new) {
   if (!t) return SVO_HIP_ERR_INVALID;
   svo_hip_ctx* ctx = t->ctx;
-  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_compact_points", "no map has been set");
-  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = trk_grow_tables(t);
-  if (rc != SVO_HIP_OK) return rc;
-  rc = trk_rekey_now(t);                    // (the re-selection owed to the last frame's deletions sees the rows as they were)
+  int rc = trk_rebuild_begin(t, "svo_hip_tracker_compact_points", []() -> int { return SVO_HIP_OK; });
   if (rc != SVO_HIP_OK) return rc;
   const int n_before = t->n_points;
-  hipLaunchKernelGGL(trk_compact_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, make_map(t), t->grow, t->pt_pos, t->kf_key_point,
-                     t->pl.first_seq, t->last, t->n_ftr);
+  hipLaunchKernelGGL(trk_compact_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, make_map(t), t->tables[1 - t->cur], t->scratch, t->pt_pos,
+                     t->kf_key_point, t->pl.first_seq, t->last, t->n_ftr);
   SVO_CHECK_HIP(ctx, hipGetLastError());
-  int out[5] = {0, 0, 0, 0, -1};
-  SVO_CHECK_HIP(ctx, hipMemcpyAsync(out, t->grow.out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
-  if (old_to_new && n_before > 0)
+  if (old_to_new && n_before > 0)           // (enqueued before trk_rebuild_end synchronises)
     SVO_CHECK_HIP(ctx, hipMemcpyAsync(old_to_new, t->pl.first_seq, (size_t)n_before * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  trk_swap_grown(t);
-  t->n_points = out[0]; t->n_ftr = out[1]; t->n_obs = out[2]; t->n_candidates = out[3];
+  int out[5] = {0, 0, 0, 0, -1};
+  rc = trk_rebuild_end(t, out, 5);
+  if (rc != SVO_HIP_OK) return rc;
+  t->n_points = out[0];
   // the last frame's features refer to the new numbering on the device; the result block (and track_n_points, its layout)
   // stays the tracked frame's under the old one
   t->last_max_point = out[4];
@@ -2131,16 +2111,17 @@ int svo_hip_tracker_download_map(svo_hip_tracker* t, svo_hip_tracker_map_out* ou
     if (dst && bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
   };
   const size_t K = (size_t)t->n_kf, P = (size_t)t->n_points, O = (size_t)t->n_obs;
+  const TrkTables& tb = t->tables[t->cur];
   out->n_kf = t->n_kf; out->n_points = t->n_points; out->n_candidates = t->n_candidates;
   get(out->kf_slot, t->kf_slot, K * 4); get(out->T_kf_w, t->T_kf_w, K * 56); get(out->kf_key_point, t->kf_key_point, K * 20);
-  if (K) get(out->kf_ftr_offset, t->kf_ftr_offset, (K + 1) * 4);
-  get(out->kf_ftr_point, t->kf_ftr_point, (size_t)t->n_ftr * 4);
+  if (K) get(out->kf_ftr_offset, tb.kf_ftr_offset, (K + 1) * 4);
+  get(out->kf_ftr_point, tb.kf_ftr_point, (size_t)t->n_ftr * 4);
   get(out->pt_pos, t->pt_pos, P * 24); get(out->pt_type, t->pt_type, P * 4); get(out->pt_n_failed, t->pt_n_failed, P * 4);
   get(out->pt_n_succeeded, t->pt_n_succeeded, P * 4);
-  if (P) get(out->pt_obs_offset, t->pt_obs_offset, (P + 1) * 4);
-  get(out->obs_kf, t->obs_kf, O * 4); get(out->obs_px, t->obs_px, O * 16); get(out->obs_f, t->obs_f, O * 24); get(out->obs_level, t->obs_level, O * 4);
-  get(out->obs_edgelet, t->obs_edgelet, O); get(out->obs_grad, t->obs_grad, O * 16);
-  get(out->cand_point, t->cand_point, (size_t)t->n_candidates * 4);
+  if (P) get(out->pt_obs_offset, tb.pt_obs_offset, (P + 1) * 4);
+  get(out->obs_kf, tb.obs_kf, O * 4); get(out->obs_px, tb.obs_px, O * 16); get(out->obs_f, tb.obs_f, O * 24); get(out->obs_level, tb.obs_level, O * 4);
+  get(out->obs_edgelet, tb.obs_edgelet, O); get(out->obs_grad, tb.obs_grad, O * 16);
+  get(out->cand_point, tb.cand_point, (size_t)t->n_candidates * 4);
   if (e != hipSuccess) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, "svo_hip_tracker_download_map", hipGetErrorString(e));
   SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SVO_HIP_OK;

@@ -5,6 +5,7 @@ under the same point numbering.  Every comparison is exact: integers equal, doub
 
 In the scenario tests tracker X uses the new calls and tracker Y today's path (set_map of the model's tables, which keeps the
 last frame for a map with the same numbering)."""
+import functools
 import os
 import subprocess
 
@@ -31,9 +32,12 @@ def ctx():
     c.close()
 
 
+_scenario = functools.lru_cache(maxsize=None)(sc.make)                          # (also read when the module is collected: PAD_TARGETS)
+
+
 @pytest.fixture(scope="module")
 def scen():
-    return sc.make()
+    return _scenario()
 
 
 def _fields(st, prefix=""):
@@ -179,6 +183,76 @@ def test_promote_with_candidates(grown, scen):
     for i, (a, b) in enumerate(zip(X["tail"], Y["tail"])):
         _same(a, b, ("frame", sc.PROMOTE_AT + 1 + i))
     assert any(1 in list(r["overlap_kf"]) for r in X["tail"])
+
+
+def _padding(seq, n):
+    """n candidates without an observation (kf_index -1) that no frame of the sequence sees: in the first keyframe's frame they
+    sit at (100, 0, 1) -- dozens of focal lengths right of the image in every frame of the sequence (x / z from 100 to 34).  (A
+    place BEHIND the camera would not do: the reprojector, like the reference's, projects without a depth test, and a point on
+    the optical axis behind the camera lands in the middle of the image.)"""
+    pos = synth.se3_act(synth.se3_inv(seq["T0"]), np.array([100.0, 0.0, 1.0]))
+    return dict(pos=np.tile(pos, (n, 1)), kf_index=np.full(n, -1, np.int32), px=np.zeros((n, 2)), f=np.tile([0.0, 0.0, 1.0], (n, 1)),
+                level=np.zeros(n, np.int32))
+
+
+def _scenario_points(s):
+    return s["base_map"]["n_points"] + len(s["cand"]["kf_index"])
+
+
+# point-table sizes on both sides of trk_promote_kernel's block of 1024 threads (its loops over the points and the candidates take
+# one round in the scenario's own map); a size the scenario's own points already exceed cannot be padded to
+PAD_TARGETS = [n for n in (1023, 1024, 1025, 2049) if n > _scenario_points(_scenario())]
+
+
+def test_padded_targets_beyond_one_block():
+    assert 1025 in PAD_TARGETS and 2049 in PAD_TARGETS
+
+
+@pytest.mark.parametrize("target", PAD_TARGETS)
+def test_promote_beyond_one_block(ctx, scen, grown, target):
+    """the scenario with the point table padded to `target` rows before the frames that precede the promotion: the padding changes
+    no tracked frame, the promotion gives the model's tables, and the next frame is the one a tracker with the model's tables
+    uploaded gives"""
+    seq, base, mp, cand = scen["seq"], scen["base"], scen["base_map"], scen["cand"]
+    X0, Y0 = grown                                                              # (the unpadded scenario)
+    n_real, n_new = _scenario_points(scen), len(cand["kf_index"])
+    pad = _padding(seq, target - n_real)
+    cfg = dict(CFG, max_points=target, max_candidates=n_new + target - n_real, max_obs=2 * target)
+    after = sc.PROMOTE_AT + 1
+
+    def unpadded(r):
+        """r with its point counters cut to the scenario's own points; the padding's: untouched candidates that failed to
+        project three times (Reprojector::reprojectMap adds 3 for a candidate outside the frame)"""
+        assert len(r["type"]) == target and (r["type"][n_real:] == synth.TYPE_CANDIDATE).all() and not r["n_succeeded"][n_real:].any()
+        return dict(r, **{k: r[k][:n_real] for k in ("type", "n_failed", "n_succeeded")})
+    x = hip.Tracker(ctx, seq["cam"], **cfg)
+    _start(x, base, mp)
+    _frames(x, seq, F_HEAD)
+    assert x.add_candidates(**cand) == X0["first"]
+    assert x.add_candidates(**pad) == n_real
+    mid = _frames(x, seq, F_MID)
+    for i, (a, b) in enumerate(zip(mid, X0["mid"])):
+        _same(unpadded(a), b, ("padded frame", sc.APPEND_AFTER + 1 + i))
+    assert (mid[-1]["n_failed"][n_real:] == 3 * len(F_MID)).all()
+    model_add, first = mg.append_candidates(mg.append_candidates(mp, **cand)[0], **pad)
+    model, n_promoted = mg.promote(model_add, mid[-1], 1, seq["cam"])
+    assert first == n_real and model["n_points"] == target
+    assert x.promote_last_frame(1) == (1, n_promoted) and n_promoted == Y0["n_promoted"]
+    mg.assert_tables_equal(x.download_map(), model)
+    assert x.map_sizes() == dict(n_kf=2, n_ftr=len(model["kf_ftr_point"]), n_points=target, n_obs=len(model["obs_kf"]),
+                                 n_candidates=len(model["cand_point"]))
+    assert len(model["cand_point"]) == n_new - n_promoted + target - n_real
+    nxt = x.track(seq["pyrs"][after][0])
+    x.destroy()
+    y = hip.Tracker(ctx, seq["cam"], **cfg)
+    _start(y, base, mp)
+    head = _frames(y, seq, F_HEAD)
+    y.set_map(_with_counters(model_add, head[-1]))
+    _same(_frames(y, seq, F_MID)[-1], mid[-1], "set_map twin before the promotion")
+    y.keyframe_from_last_frame(1)
+    y.set_map(model)
+    _same(nxt, y.track(seq["pyrs"][after][0]), ("frame", after))
+    y.destroy()
 
 
 def test_last_result_after_add_candidates(grown, scen):
