@@ -774,8 +774,23 @@ __device__ __noinline__ void fused_refactor_cold(const double* s_Hc, double* s_f
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
-// large update angles (theta^2 > 0.25): the library path of SE3::exp
+// large update angles (theta^2 > 0.25): the library path of SE3::exp ...
 __device__ __noinline__ void se3_exp_cold(const double* l, double* out) { se3_exp(l, out); }
+
+// ... and the same with the pose product, from LDS to LDS: the caller leaves x in s_x and the pose in s_model, so that on
+// the usual path neither -x, exp(-x) nor the new pose has an address (arrays whose address is taken live in scratch, and
+// wave 0 stored them there at every evaluation)
+__device__ __noinline__ void fused_large_step_cold(const double* s_x, double* s_model) {
+  double mx[6], cur[7], dT[7], nm[7];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) mx[i] = -s_x[i];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) cur[i] = s_model[i];
+  se3_exp(mx, dT);
+  se3_mul(cur, dT, nm);                                                            // T_new = T_old * exp(-x)
+#pragma unroll
+  for (int i = 0; i < 7; ++i) s_model[i] = nm[i];
+}
 
 // The Hessian row of a set of patches of one tile: lane e (< 21) returns entry e -- (i, j) of the upper triangle in
 // row-major order -- of the sum, over the lanes with `contributes`, of the patch's J^T J summed over its pixels
@@ -1485,7 +1500,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
       const long long t2 = __builtin_amdgcn_s_memtime();
 #endif
       double v = 0.0;                       // wave 0, lanes 0..28: sums over the waves
-      double x[6] = {0, 0, 0, 0, 0, 0};
+      double xi = 0.0;                      // wave 0, lane i < 6: x[i]
       double new_chi2 = 0.0;
       bool rollback = false;
       if (wave == 0) {
@@ -1519,10 +1534,6 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         // is reused (a deterministic function of H, so the result is the same number)
         const bool h_same = lane >= 21 || __double_as_longlong(v) == __double_as_longlong(hc_prev);
         const bool reuse = fac_valid != 0 && __ballot(!h_same) == 0ull;            // wave-uniform
-        // lanes 21..26 hold Jres: wave-uniform copies, no trip through LDS
-        double Jres[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) Jres[i] = readlane_f64(v, 21 + i);
 #ifdef SVO_STAMPS
         const long long q0 = __builtin_amdgcn_s_memtime();
         if (lane == 0) s_stamp[5] += q0 - t2;
@@ -1537,10 +1548,16 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
 #pragma unroll
           for (int j = 0; j < 6; ++j) inv_row[j] = s_inv[(lane < 6 ? lane : 0) * 6 + j];
         }
+        // lanes 21..26 hold Jres: wave-uniform copies, no trip through LDS (taken behind the cold call, so that they are
+        // not scalars that live across it)
+        double Jres[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) Jres[i] = readlane_f64(v, 21 + i);
         // x = H^-1 Jres, one component per lane (H^-1 is symmetric: lane i uses the column it computed as row i)
-        double xi = inv_row[0] * Jres[0];
+        xi = inv_row[0] * Jres[0];
 #pragma unroll
         for (int j = 1; j < 6; ++j) xi += inv_row[j] * Jres[j];
+        double x[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) x[i] = readlane_f64(xi, i);
         // the four series of exp(-x) on lanes 0..3 (theta^2 is the same for x and -x), collected wave-uniform
@@ -1566,21 +1583,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
             s_done = 1;
             if (stop_now) s_stop = 1;
           } else {
-            double mx[6], dT[7], nm[7];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) mx[i] = -x[i];
-#ifdef SVO_STAMPS
-            const long long q2 = __builtin_amdgcn_s_memtime();
-#endif
-            if (zt <= 0.25) se3_exp_small_finish(mx, zt, qs_t, pc_t, ps_h, pc_h, dT);
-            else se3_exp_cold(mx, dT);                                             // large angles: the library path
-            se3_mul(cur, dT, nm);                                                  // T_new = T_old * exp(-x) (:307)
-#ifdef SVO_STAMPS
-            const long long q3 = __builtin_amdgcn_s_memtime();
-            s_stamp[4] += q3 - q2;
-#endif
-#pragma unroll
-            for (int i = 0; i < 7; ++i) s_model[i] = nm[i];
+            // (the exits first: behind the cold call below nothing is left to do, so no scalar has to outlive it)
             bool done = it + 1 >= prm.n_iter;
             if (prm.early_stop) {                                                  // :97-98
               double mxn = -1;
@@ -1589,6 +1592,39 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
               if (mxn <= prm.eps) done = true;
             }
             if (done) s_done = 1;
+#ifdef SVO_STAMPS
+            const long long q2 = __builtin_amdgcn_s_memtime();
+#endif
+            if (zt <= 0.25) {
+              double mx[6], dT[7], nm[7];
+#pragma unroll
+              for (int i = 0; i < 6; ++i) mx[i] = -x[i];
+              se3_exp_small_finish(mx, zt, qs_t, pc_t, ps_h, pc_h, dT);
+              se3_mul(cur, dT, nm);                                                // T_new = T_old * exp(-x) (:307)
+#pragma unroll
+              for (int i = 0; i < 7; ++i) s_model[i] = nm[i];
+            } else if (TPW <= 4) {
+              // large angles: the library path, out of line and through LDS (s_model still holds cur; s_x gets the same
+              // values again behind the second barrier)
+#pragma unroll
+              for (int i = 0; i < 6; ++i) s_x[i] = x[i];
+              fused_large_step_cold(s_x, s_model);
+            } else {
+              // ... and in the shapes with five and six tiles per wave through arrays of this branch's own: with the LDS form
+              // their allocation spills 70 / 100 VGPRs instead of 66 / 98, three of them reloaded at every evaluation
+              // (measured at 2500 patches: 4.67 instead of 4.49 ms per step)
+              double mx[6], dT[7], nm[7];
+#pragma unroll
+              for (int i = 0; i < 6; ++i) mx[i] = -x[i];
+              se3_exp_cold(mx, dT);
+              se3_mul(cur, dT, nm);
+#pragma unroll
+              for (int i = 0; i < 7; ++i) s_model[i] = nm[i];
+            }
+#ifdef SVO_STAMPS
+            const long long q3 = __builtin_amdgcn_s_memtime();
+            s_stamp[4] += q3 - q2;
+#endif
           }
         }
 #ifdef SVO_STAMPS
@@ -1600,12 +1636,11 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         // what only wave 0 itself reads again (and thread 0 at the end): the other waves are already evaluating
         const double n_meas_d = readlane_f64(v, 28);       // exact integer counts (multiples of 16) carried as doubles
         if (!prm.early_stop) new_chi2 = (double)((float)readlane_f64(v, 27) / (float)n_meas_d);   // (:285)
+        if (lane < 6) s_x[lane] = xi;                      // x, from the lanes that formed it
         if (lane == 0) {
           s_nmeas = n_meas_d;
           s_nres = nres_old + n_meas_d * 0.0625;
           s_iters[level] = iters_l + 1;
-#pragma unroll
-          for (int i = 0; i < 6; ++i) s_x[i] = x[i];
           if (!rollback) {
 #pragma unroll
             for (int i = 0; i < 7; ++i) s_old[i] = cur[i];
@@ -2531,6 +2566,17 @@ int svo_hip_sia_download_all(svo_hip_sia* s, int n_slots, svo_hip_sia_result* ou
     for (int i = 0; i < n_slots; ++i) fill_result(h[i], out + i);
   delete[] h;
   return rc;
+}
+
+int svo_hip_sia_download_last_step(svo_hip_sia* s, int slot, double* Jres6, double* x6) {
+  if (!s || !Jres6 || !x6) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = s->ctx;
+  SVO_REQUIRE(ctx, slot >= 0 && slot < s->batch);
+  FrameState st;
+  int rc = svo_hip_memcpy_d2h(ctx, &st, s->st + slot, sizeof(FrameState));
+  if (rc != SVO_HIP_OK) return rc;
+  for (int i = 0; i < 6; ++i) { Jres6[i] = st.Jres[i]; x6[i] = st.x[i]; }
+  return SVO_HIP_OK;
 }
 
 int svo_hip_sia_download_fused_patches(svo_hip_sia* s, int slot, int level, float* ref_patch, float* dx, float* dy, uint8_t* valid) {

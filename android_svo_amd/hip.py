@@ -343,6 +343,13 @@ class SparseImgAlign:
         self.ctx.check(self.ctx.lib.svo_hip_sia_download(self.h, slot, C.byref(out)), "sia_download")
         return out
 
+    def download_last_step(self, slot: int):
+        """(Jres_, x_) of the slot's last evaluation"""
+        jres, x = np.zeros(6), np.zeros(6)
+        self.ctx.check(self.ctx.lib.svo_hip_sia_download_last_step(self.h, slot, _ptr(jres, C.c_double), _ptr(x, C.c_double)),
+                       "sia_download_last_step")
+        return jres, x
+
     def download_all(self, n_slots: int):
         arr = (CSiaResult * n_slots)()
         self.ctx.check(self.ctx.lib.svo_hip_sia_download_all(self.h, n_slots, arr), "sia_download_all")

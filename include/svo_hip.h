@@ -370,6 +370,9 @@ int svo_hip_sia_download_caches(svo_hip_sia* sia, int slot, float* ref_patch, fl
  * rows of other patches are not written.  Overwrites the streaming kernels' cache arrays of the slot. */
 int svo_hip_sia_download_fused_patches(svo_hip_sia* sia, int slot, int level, float* ref_patch, float* dx, float* dy,
                                        uint8_t* valid);
+/* Test support as well: Jres_ [6] and x_ [6] of the slot's last Gauss-Newton evaluation, which svo_hip_sia_result does not
+ * carry (tests/test_gpu_fused_window_paths.py holds them to recorded bits).  Blocks like svo_hip_sia_download. */
+int svo_hip_sia_download_last_step(svo_hip_sia* sia, int slot, double* Jres6, double* x6);
 
 /* ---- feature_alignment::align2D (I/feature_alignment.h:40-47, feature_alignment.cpp:154-282) */
 /* n independent 8x8 patches refined on level `level` of cur->slot: ref_patch_with_border
