@@ -1132,6 +1132,142 @@ __global__ void trk_scatter_positions_kernel(int n, const int* __restrict__ idx,
   pt_pos[3 * p] = pos[3 * i]; pt_pos[3 * p + 1] = pos[3 * i + 1]; pt_pos[3 * p + 2] = pos[3 * i + 2];
 }
 
+// ---- relocalisation: Map::getClosestKeyframe (S/map.cpp:109-151) and last_frame_ = ref_keyframe
+// (FrameHandlerMono::relocalizeFrame, S/frame_handler_mono.cpp:337) on the tables.  One workgroup of RELOC_THREADS.
+//   choose: every keyframe one of whose key points is visible from T is close (the first visible one decides), its distance is
+//           (T.translation_vec() - T_kf_w.translation_vec()).norm(); the answer is the close keyframe other than `exclude` with the
+//           smallest distance, the lower index on a tie (std::list::sort is stable over keyframes_ order).  Otherwise kf is given.
+//   apply:  the last frame becomes that keyframe when it exists and its features fit: pose = row kf of T_kf_w; features = the
+//           entries of its feature row whose point is living and observed in it, in row order, with the px / f of the point's first
+//           observation there.  Counted first, written only when the count fits (a refused call changes nothing).  The solver's
+//           slot gets the same features with T_ref_w = the keyframe's pose and T_cur_w_init = T (gate) or the keyframe's pose.
+// T: the pose of the device's last frame (use_last_pose; read before anything is written) or the one passed by value.
+constexpr int RELOC_THREADS = 256;
+struct TrkRelocArgs {
+  int kf, exclude, choose, apply, gate, use_last_pose, max_feat, pad;
+  double T[7];
+};
+struct TrkRelocOut {
+  double distance;               // of the chosen keyframe (choose)
+  int kf;                        // the keyframe, -1: none
+  int n_close;                   // close keyframes before the exclusion (choose)
+  int n_feat;                    // its features (apply), -1: not counted
+  int applied;                   // 1: the last frame is the keyframe now
+  int max_point;                 // largest point index among the features, -1: none
+  int pad;
+};
+__global__ __launch_bounds__(RELOC_THREADS) void trk_reloc_kernel(TrkMap m, TrkLast last, Cam cam, TrkRelocArgs a, TrkRelocOut* __restrict__ out) {
+  static_assert(TRK_LDS_KF <= RELOC_THREADS, "one keyframe per thread");
+  __shared__ double s_T[7], s_dist[TRK_LDS_KF];
+  __shared__ int s_close[TRK_LDS_KF], s_wave[RELOC_THREADS / 64];
+  __shared__ int s_kf, s_n_close, s_count, s_max_point;
+  const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6;
+  if (t < 7) s_T[t] = a.use_last_pose ? last.T_f_w[t] : a.T[t];
+  if (t == 0) { s_kf = a.kf; s_n_close = 0; s_count = 0; s_max_point = -1; }
+  __syncthreads();
+  double T[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) T[i] = s_T[i];
+  if (a.choose) {                                                              // block-uniform
+    for (int k = t; k < m.n_kf; k += nt) {
+      int kp[5];
+#pragma unroll
+      for (int j = 0; j < 5; ++j) kp[j] = m.kf_key_point[5 * k + j];
+      bool close = false;
+#pragma unroll
+      for (int j = 0; j < 5; ++j)
+        if (!close && kp[j] >= 0) close = frame_is_visible(cam, T, m.pt_pos + 3 * (size_t)kp[j]);
+      const double* tk = m.T_kf_w + 7 * (size_t)k;
+      const double dx = T[0] - tk[0], dy = T[1] - tk[1], dz = T[2] - tk[2];
+      s_close[k] = close ? 1 : 0;
+      s_dist[k] = sqrt(dx * dx + dy * dy + dz * dz);
+    }
+    __syncthreads();
+    if (t == 0) {                                                              // at most TRK_LDS_KF keyframes: one walk in index order
+      int best = -1, n_close = 0;
+      for (int k = 0; k < m.n_kf; ++k) {
+        if (!s_close[k]) continue;
+        ++n_close;
+        if (k != a.exclude && (best < 0 || s_dist[k] < s_dist[best])) best = k;
+      }
+      s_kf = best; s_n_close = n_close;
+    }
+    __syncthreads();
+  }
+  const int k = s_kf;
+  int n_feat = -1;
+  bool apply = false;
+  if (a.apply && k >= 0) {                                                     // block-uniform
+    const int r0 = m.kf_ftr_offset[k], r1 = m.kf_ftr_offset[k + 1];
+    // the point's first observation in keyframe k (-1: none, or the point is not living)
+    auto obs_in_kf = [&](int i) {
+      const int p = m.kf_ftr_point[i];
+      if (p < 0 || m.pt_unlinked[p]) return -1;
+      for (int o = m.pt_obs_offset[p]; o < m.pt_obs_offset[p + 1]; ++o)
+        if (m.obs_kf[o] == k) return o;
+      return -1;
+    };
+    int mine = 0;
+    for (int i = r0 + t; i < r1; i += nt) mine += obs_in_kf(i) >= 0 ? 1 : 0;
+    if (mine) atomicAdd(&s_count, mine);
+    __syncthreads();
+    n_feat = s_count;
+    apply = n_feat <= a.max_feat;
+    if (apply) {
+      // ordered compaction of the row, a chunk of the workgroup's size at a time: ranks inside a wave from the ballot, across
+      // the waves through LDS, across the chunks in `base`
+      int base = 0;
+      for (int c0 = r0; c0 < r1; c0 += nt) {                                   // block-uniform
+        const int i = c0 + t;
+        const int o = i < r1 ? obs_in_kf(i) : -1;
+        const unsigned long long bal = __ballot(o >= 0);
+        if (lane == 0) s_wave[wave] = __popcll(bal);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < RELOC_THREADS / 64; ++w) { const int c = s_wave[w]; before += w < wave ? c : 0; total += c; }
+        if (o >= 0) {
+          const int r = base + before + __popcll(bal & ((1ull << lane) - 1ull));
+          const int p = m.kf_ftr_point[i];
+          const double x = m.obs_px[2 * (size_t)o], y = m.obs_px[2 * (size_t)o + 1];
+          const double f0 = m.obs_f[3 * (size_t)o], f1 = m.obs_f[3 * (size_t)o + 1], f2 = m.obs_f[3 * (size_t)o + 2];
+          last.px[2 * r] = x; last.px[2 * r + 1] = y;
+          last.f[3 * r] = f0; last.f[3 * r + 1] = f1; last.f[3 * r + 2] = f2;
+          last.point[r] = p;
+          if (r < last.sia_max_n) {
+            last.sia_px[2 * r] = x; last.sia_px[2 * r + 1] = y;
+            last.sia_f[3 * r] = f0; last.sia_f[3 * r + 1] = f1; last.sia_f[3 * r + 2] = f2;
+            last.sia_pos[3 * r] = m.pt_pos[3 * (size_t)p]; last.sia_pos[3 * r + 1] = m.pt_pos[3 * (size_t)p + 1];
+            last.sia_pos[3 * r + 2] = m.pt_pos[3 * (size_t)p + 2];
+            last.sia_has_point[r] = 1;
+          }
+          atomicMax(&s_max_point, p);
+        }
+        base += total;
+        __syncthreads();                                                       // (s_wave is rewritten by the next chunk)
+      }
+      if (t == 0) {
+        *last.n = n_feat;
+        FrameConst c;
+        c.cam = cam;
+        const double* tk = m.T_kf_w + 7 * (size_t)k;
+        for (int i = 0; i < 7; ++i) { const double v = tk[i]; last.T_f_w[i] = v; c.T_ref_w[i] = v; c.T_cur_w_init[i] = a.gate ? T[i] : v; }
+        double Tinv[7];
+        se3_inverse(c.T_ref_w, Tinv);                                          // Frame::pos()
+        c.ref_pos[0] = Tinv[0]; c.ref_pos[1] = Tinv[1]; c.ref_pos[2] = Tinv[2];
+        c.n_feat = n_feat < last.sia_max_n ? n_feat : last.sia_max_n; c.pad = 0;
+        last.sia_fc[0] = c;
+      }
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    TrkRelocOut r;
+    r.distance = a.choose && k >= 0 ? s_dist[k] : 0.0;
+    r.kf = k; r.n_close = s_n_close; r.n_feat = n_feat; r.applied = apply ? 1 : 0; r.max_point = s_max_point; r.pad = 0;
+    *out = r;
+  }
+}
+
 // device memory for count elements, recorded in got (whose owner frees it); a no-op once *rc holds an error
 template <typename T>
 void trk_alloc(svo_hip_ctx* ctx, std::vector<void*>* got, int* rc, T** p, size_t count) {
@@ -1210,6 +1346,7 @@ struct svo_hip_tracker {
   bool need_gather = true;                  // the solver's slot 0 does not hold the last frame yet (a host upload came in between)
   bool any_edgelet = false;                 // the map holds EDGELET reference features (align1D stage needed)
   svo_hip_pose_opt_result* po = nullptr;    // (its entry of the shared array)
+  TrkRelocOut* reloc_out = nullptr;         // what trk_reloc_kernel reports
   // result block: [svo_hip_track_result][px][f][level][point][edgelet][grad][pt_type][pt_failed][pt_succeeded]
   char* res_dev = nullptr;                  // device address of res_host
   char* res_host = nullptr;                 // page-locked, mapped into the device: the hand-over kernel writes it directly
@@ -1425,6 +1562,7 @@ static int trk_member_create(svo_hip_tracker_shared* sh, int index, const svo_hi
   ft.f = sh->ft_f + 3 * NF * (size_t)index; ft.pos = sh->ft_pos + 3 * NF * (size_t)index;
   ft.level = sh->ft_level + NF * (size_t)index; ft.has_point = sh->ft_has_point + NF * (size_t)index;
   D(&t->last.n, 1); D(&t->last.T_f_w, 7); D(&t->last.px, NF * 2); D(&t->last.f, NF * 3); D(&t->last.point, NF);
+  D(&t->reloc_out, 1);
   // result block
   auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
   t->o_px = al(sizeof(svo_hip_track_result)); t->o_f = al(t->o_px + NF * 16); t->o_level = al(t->o_f + NF * 24); t->o_point = al(t->o_level + NF * 4);
@@ -1704,7 +1842,8 @@ static void trk_copy_out(svo_hip_tracker* t, svo_hip_track_result* result, doubl
 
 // One frame for every camera of the shared part: ONE chain of launches whatever the number of cameras.  level0[c]: camera c's
 // new image (its own page-locked buffer: no copy).
-static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level0, const char* who) {
+// image_ready: the new frames' pyramids are built already (svo_hip_tracker_relocalize, whose gate ran on them).
+static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level0, const char* who, bool image_ready = false) {
   svo_hip_ctx* ctx = sh->ctx;
   const int N = sh->n_cams;
   svo_hip_tracker* t0 = sh->members[0];
@@ -1719,11 +1858,11 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
   svo_hip_pyramid* ref = sh->frame_pyr[sh->last_idx];
   svo_hip_pyramid* cur = sh->frame_pyr[1 - sh->last_idx];
   // ---- new Frame(cam, img, t): the images cross the link once, from page-locked memory; the pyramids are built on the device
-  for (int k = 0; k < N; ++k) {
+  for (int k = 0; k < N && !image_ready; ++k) {
     svo_hip_tracker* t = sh->members[(size_t)k];
     if (level0[k] != reinterpret_cast<const uint8_t*>(t->img_host)) memcpy(t->img_host, level0[k], l0);      // (svo_hip_tracker_image_buffer: already there)
   }
-  int rc = svo_pyramid_build_levels(cur, 0, N, sh->img_dev, sh->img_stride);
+  int rc = image_ready ? SVO_HIP_OK : svo_pyramid_build_levels(cur, 0, N, sh->img_dev, sh->img_stride);
   if (rc != SVO_HIP_OK) return rc;
   // ---- SparseImgAlign(kltMaxLevel, kltMinLevel, 30, GaussNewton, false, false).run(last_frame_, new_frame_)
   rc = svo_hip_sia_set_frames(sh->sia, ref, cur);
@@ -2085,6 +2224,150 @@ int svo_hip_tracker_compact_points(svo_hip_tracker* t, int* n_points_after, int3
   t->last_max_point = out[4];
   t->last_renumbered = t->last_from_track;
   if (n_points_after) *n_points_after = t->n_points;
+  return SVO_HIP_OK;
+}
+
+// ---- relocalisation against a keyframe of the device map (FrameHandlerMono::relocalizeFrame, S/frame_handler_mono.cpp:317-349)
+
+// trk_reloc_kernel and its report: one launch, one synchronisation.  The owed re-selection of key points runs first.
+static int trk_reloc_run(svo_hip_tracker* t, const TrkRelocArgs& a, TrkRelocOut* out) {
+  svo_hip_ctx* ctx = t->ctx;
+  int rc = trk_rekey_now(t);
+  if (rc == SVO_HIP_OK) {
+    hipLaunchKernelGGL(trk_reloc_kernel, dim3(1), dim3(RELOC_THREADS), 0, ctx->stream, make_map(t), t->last, svo_make_cam(t->cam), a, t->reloc_out);
+    if (hipGetLastError() != hipSuccess) rc = svo_fail(ctx, SVO_HIP_ERR_DEVICE, "trk_reloc_kernel", "launch failed");
+  }
+  hipError_t e = rc == SVO_HIP_OK ? hipMemcpyAsync(out, t->reloc_out, sizeof(TrkRelocOut), hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  const hipError_t es = hipStreamSynchronize(ctx->stream);                      // (on the error paths too)
+  if (rc != SVO_HIP_OK) return rc;
+  if (e != hipSuccess || es != hipSuccess) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, "trk_reloc_kernel", hipGetErrorString(e != hipSuccess ? e : es));
+  return SVO_HIP_OK;
+}
+
+static TrkRelocArgs trk_reloc_args(const svo_hip_tracker* t, int kf, int exclude, const double* T) {
+  TrkRelocArgs a;
+  memset(&a, 0, sizeof(a));
+  a.kf = kf; a.exclude = exclude; a.choose = kf < 0 ? 1 : 0; a.max_feat = t->cfg.max_frame_features;
+  a.use_last_pose = T ? 0 : 1;
+  if (T) memcpy(a.T, T, sizeof(a.T)); else a.T[6] = 1.0;
+  return a;
+}
+
+// the host's side of "the last frame is keyframe k now" (the kernel has written the device's): the keyframe's pyramid becomes
+// the last frame's, and the tracker is where svo_hip_tracker_set_last_frame leaves it
+static int trk_last_is_keyframe(svo_hip_tracker* t, int k, const TrkRelocOut& o) {
+  svo_hip_pyramid* dst = t->sh->frame_pyr[t->sh->last_idx];
+  const svo_hip_pyramid* kf = t->sh->kf_pyr;
+  const int rc = svo_hip_copy_d2d(t->ctx, dst->base + (size_t)t->cam_index * dst->pyr_bytes,
+                                  kf->base + ((size_t)t->cam_index * t->cfg.max_keyframes + t->kf_slot_host[(size_t)k]) * kf->pyr_bytes, dst->pyr_bytes);
+  t->last_n_host = o.n_feat;
+  t->last_max_point = o.max_point;
+  t->last_from_track = false;
+  t->last_renumbered = false;
+  t->have_last = true;
+  t->need_gather = true;
+  return rc;
+}
+
+int svo_hip_tracker_closest_keyframe(svo_hip_tracker* t, const double T_f_w[7], int exclude_kf, int* kf_index, int* n_close, double* distance) {
+  if (!t || !kf_index) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  const char* who = "svo_hip_tracker_closest_keyframe";
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no map has been set");
+  if (!T_f_w && !t->have_last) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no pose given and the device holds no last frame");
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  TrkRelocOut o;
+  const int rc = trk_reloc_run(t, trk_reloc_args(t, -1, exclude_kf, T_f_w), &o);
+  if (rc != SVO_HIP_OK) return rc;
+  *kf_index = o.kf;
+  if (n_close) *n_close = o.n_close;
+  if (distance) *distance = o.distance;
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_last_frame_from_keyframe(svo_hip_tracker* t, int kf_index, int* n_features) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  const char* who = "svo_hip_tracker_last_frame_from_keyframe";
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no map has been set");
+  SVO_REQUIRE(ctx, kf_index >= 0 && kf_index < t->n_kf);
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  TrkRelocArgs a = trk_reloc_args(t, kf_index, -1, nullptr);
+  a.apply = 1; a.use_last_pose = 0;                                             // (no pose is read: nothing is chosen, no gate follows)
+  TrkRelocOut o;
+  int rc = trk_reloc_run(t, a, &o);
+  if (rc != SVO_HIP_OK) return rc;
+  if (!o.applied) return svo_fail(ctx, SVO_HIP_ERR_INVALID, who, "the keyframe has more living features than max_frame_features");
+  rc = trk_last_is_keyframe(t, kf_index, o);
+  if (rc != SVO_HIP_OK) return rc;
+  if (n_features) *n_features = o.n_feat;
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_relocalize(svo_hip_tracker* t, const uint8_t* level0, int kf_index, int exclude_kf, const double T_f_w_init[7], int min_tracked,
+                               svo_hip_reloc_result* reloc, svo_hip_track_result* result, double* feat_px, double* feat_f, int32_t* feat_level,
+                               int32_t* feat_point, uint8_t* feat_edgelet, double* feat_grad, int32_t* pt_type, int32_t* pt_n_failed,
+                               int32_t* pt_n_succeeded) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  svo_hip_tracker_shared* sh = t->sh;
+  const char* who = "svo_hip_tracker_relocalize";
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no map has been set");
+  if (!T_f_w_init && !t->have_last) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no pose given and the device holds no last frame");
+  if (sh->n_cams != 1)
+    return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "a camera of a tracker group relocalises with svo_hip_tracker_last_frame_from_keyframe and svo_hip_tracker_group_track");
+  SVO_REQUIRE(ctx, level0 && reloc && kf_index < t->n_kf && min_tracked >= 0);
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  memset(reloc, 0, sizeof(*reloc));
+  reloc->kf_index = -1;
+  // whatever fails from here on: the stream is through with the staging areas before the call returns
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); t->need_gather = true; return rc; };
+  // ---- new Frame(cam, img, t): the image and its pyramid, as in svo_hip_tracker_track (the pyramid batch that is not the last frame's)
+  svo_hip_pyramid* cur = sh->frame_pyr[1 - sh->last_idx];
+  if (level0 != reinterpret_cast<const uint8_t*>(t->img_host)) memcpy(t->img_host, level0, (size_t)t->cam.width * t->cam.height);
+  int rc = svo_pyramid_build_levels(cur, 0, 1, sh->img_dev, sh->img_stride);
+  if (rc != SVO_HIP_OK) return fail(rc);
+  // ---- the keyframe (Map::getClosestKeyframe unless given), and last_frame_ = ref_keyframe with the gate's poses in the solver
+  TrkRelocArgs a = trk_reloc_args(t, kf_index < 0 ? -1 : kf_index, exclude_kf, T_f_w_init);
+  a.apply = 1; a.gate = 1;
+  TrkRelocOut o;
+  rc = trk_reloc_run(t, a, &o);
+  if (rc != SVO_HIP_OK) return fail(rc);
+  reloc->kf_index = o.kf;
+  reloc->n_close = kf_index < 0 ? o.n_close : 0;
+  if (o.kf < 0) return SVO_HIP_OK;                                               // no keyframe is close: the last frame is kept
+  if (!o.applied) return svo_fail(ctx, SVO_HIP_ERR_INVALID, who, "the keyframe has more living features than max_frame_features");
+  rc = trk_last_is_keyframe(t, o.kf, o);
+  if (rc != SVO_HIP_OK) return fail(rc);
+  // ---- SparseImgAlign(kltMaxLevel, kltMinLevel, 30, GaussNewton).run(ref_keyframe, new_frame) from T_f_w_init (:329-333)
+  const svo_hip_tracker_config& c = t->cfg;
+  svo_hip_sia_params sp;
+  sp.max_level = c.klt_max_level; sp.min_level = c.klt_min_level; sp.n_iter = c.sia_n_iter; sp.eps = c.sia_eps; sp.early_stop = 1;
+  svo_hip_sia_result gate;
+  rc = svo_hip_sia_set_frames(sh->sia, sh->frame_pyr[sh->last_idx], cur);
+  if (rc == SVO_HIP_OK) rc = svo_sia_note_device_slot(sh->sia, 0, &t->cam, o.n_feat);
+  if (rc == SVO_HIP_OK) rc = svo_hip_sia_run(sh->sia, 1, &sp);
+  if (rc == SVO_HIP_OK) rc = svo_hip_sia_download(sh->sia, 0, &gate);             // (synchronises: the outcome steers the host)
+  if (rc != SVO_HIP_OK) return fail(rc);
+  reloc->gate_stop = gate.stop;
+  reloc->gate_n_tracked = gate.n_tracked;
+  for (int i = 0; i < SVO_HIP_MAX_LEVELS; ++i) reloc->gate_iters[i] = gate.iters[i];
+  memcpy(reloc->T_f_w_gate, gate.T_cur_w, sizeof(reloc->T_f_w_gate));
+  if (gate.n_tracked > (uint64_t)min_tracked) {
+    // ---- processFrame (:338) with last_frame_ = ref_keyframe: the chain starts SparseImgAlign again from the keyframe's pose (:175)
+    reloc->accepted = 1;
+    rc = trk_track_all(sh, &level0, who, true);
+    if (rc != SVO_HIP_OK) return fail(rc);
+    trk_copy_out(t, result, feat_px, feat_f, feat_level, feat_point, feat_edgelet, feat_grad, pt_type, pt_n_failed, pt_n_succeeded);
+    return SVO_HIP_OK;
+  }
+  // ---- refused: last_frame_ = new_frame_ (FrameHandlerMono::addImage :90) -- the new image, no features, the pose the gate left
+  hipError_t e = hipMemsetAsync(t->last.n, 0, sizeof(int), ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(t->last.T_f_w, svo_sia_state_dev(sh->sia, 0)->T_cur_w, 7 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
+  if (e != hipSuccess) return fail(svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, hipGetErrorString(e)));
+  sh->last_idx = 1 - sh->last_idx;
+  t->last_n_host = 0;
+  t->last_max_point = -1;
   return SVO_HIP_OK;
 }
 

@@ -926,6 +926,11 @@ class CTrackResult(C.Structure):
                 ("overlap_count", C.c_int32 * 16), ("n_candidates", C.c_int32), ("items_overflow", C.c_int32), ("pose", CPoseOptResult)]
 
 
+class CRelocResult(C.Structure):             # svo_hip_reloc_result
+    _fields_ = [("kf_index", C.c_int32), ("n_close", C.c_int32), ("accepted", C.c_int32), ("gate_stop", C.c_int32),
+                ("gate_n_tracked", C.c_uint64), ("gate_iters", C.c_int32 * MAX_LEVELS), ("T_f_w_gate", C.c_double * 7)]
+
+
 class Tracker:
     """svo_hip_tracker: SparseImgAlign -> Reprojector::reprojectMap -> pose_optimizer on one stream, one synchronisation per
     frame, the frame's matches handed over to the next call on the device."""
@@ -1088,6 +1093,42 @@ class Tracker:
                                                                    len(pt), _ptr(p, C.c_double), _ptr(ff, C.c_double), _ptr(pt, C.c_int32)),
                        "tracker_set_last_frame")
         self.ctx.sync()
+
+    def closest_keyframe(self, T_f_w=None, exclude_kf: int = -1) -> dict:
+        """svo_hip_tracker_closest_keyframe: Map::getClosestKeyframe on the device's tables for pose T_f_w (None: the device's last
+        frame's).  Returns dict(kf_index (-1: none is close), n_close, distance)."""
+        T = None if T_f_w is None else _f64(T_f_w)
+        k, n, d = C.c_int(-2), C.c_int(-1), C.c_double(0.0)
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_closest_keyframe(self.h, None if T is None else _ptr(T, C.c_double), int(exclude_kf),
+                                                                     C.byref(k), C.byref(n), C.byref(d)), "tracker_closest_keyframe")
+        return dict(kf_index=k.value, n_close=n.value, distance=d.value)
+
+    def last_frame_from_keyframe(self, kf_index: int) -> int:
+        """svo_hip_tracker_last_frame_from_keyframe: the device's last frame becomes keyframe kf_index of its map (pose, pyramid,
+        the living features of its row).  Returns the number of features."""
+        n = C.c_int(-1)
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_last_frame_from_keyframe(self.h, int(kf_index), C.byref(n)), "tracker_last_frame_from_keyframe")
+        return n.value
+
+    def relocalize(self, img: np.ndarray, T_f_w_init=None, kf_index: int = -1, exclude_kf: int = -1, min_tracked: int = 30,
+                   want_points: bool = True) -> dict:
+        """svo_hip_tracker_relocalize: FrameHandlerMono::relocalizeFrame as one call.  Returns dict(reloc = CRelocResult) joined,
+        when the gate accepted, with the dict track() returns for the frame."""
+        im = np.ascontiguousarray(img, dtype=np.uint8)
+        assert im.shape == (self.cam.height, self.cam.width)
+        T = None if T_f_w_init is None else _f64(T_f_w_init)
+        o = self._outputs()
+        rel, res = CRelocResult(), CTrackResult()
+        I, D = C.c_int32, C.c_double
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_relocalize(
+            self.h, _ptr(im, C.c_uint8), int(kf_index), int(exclude_kf), None if T is None else _ptr(T, D), int(min_tracked), C.byref(rel),
+            C.byref(res), _ptr(o["px"], D), _ptr(o["f"], D), _ptr(o["level"], I), _ptr(o["point"], I), _ptr(o["edgelet"], C.c_uint8),
+            _ptr(o["grad"], D), _ptr(o["pt_type"], I) if want_points else None, _ptr(o["pt_n_failed"], I) if want_points else None,
+            _ptr(o["pt_n_succeeded"], I) if want_points else None), "tracker_relocalize")
+        if not rel.accepted:
+            return dict(reloc=rel)
+        self._tracked_n_points = self.n_points
+        return dict(reloc=rel, **self._as_dict(res, o))
 
     def _outputs(self):
         nf = self.cfg.max_frame_features

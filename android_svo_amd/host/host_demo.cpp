@@ -135,8 +135,12 @@ static svo_hip_tracker_config track_config(const std::vector<double>& m, int max
 // compact: FrameTracker::setPointCompaction.  map_compactions.bin: per frame, the compactions so far (beside track_uploads.bin);
 // map_points_room.bin: the largest (living points + candidates waiting to be appended) at the end of a frame, and the rows of
 // the device's point tables at the end.
+// reloc_at K: frame K is not tracked from the last frame but relocalised (svo::relocalizeFrame: FrameHandlerMono::relocalizeFrame
+// against Map::getClosestKeyframe(last_frame_)) with FrameTracker::setDeviceRelocalisation -- keyframe choice, gate and tracking in
+// one device call.  track_reloc.bin: the result (UpdateResult), the reference keyframe (in order of creation, -1: none), how many
+// device relocalisations the bridge made, gate_n_tracked, accepted, n_close, the gate's pose.
 static int track_demo(const std::string& dir, const std::string& out, TrackerPort& port, bool incremental = false, bool times = false,
-                      int max_kfs = 0, bool full_remove = false, int kf_every = 0, bool compact = false, int new_seeds = 0) {
+                      int max_kfs = 0, bool full_remove = false, int kf_every = 0, bool compact = false, int new_seeds = 0, int reloc_at = -1) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
   PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
   const int n_kf = (int)m[6], n_points = (int)m[7], n_obs = (int)m[8], n_cand = (int)m[10], n_frames = (int)m[11];
@@ -198,6 +202,7 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
   if (!tracker.ok()) throw std::runtime_error("svo::FrameTracker: no device tracker");
   tracker.setIncrementalMap(incremental);
   if (compact) tracker.setPointCompaction(true);
+  if (reloc_at >= 0) tracker.setDeviceRelocalisation(true);
   std::vector<double> track_us;
 
   // the last frame: a keyframe of the map, or a frame of its own without features (SparseImgAlign::run then returns at once)
@@ -221,6 +226,16 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
     std::vector<std::pair<FramePtr, size_t>> overlap_kfs;
     FrameTracker::Outcome oc;
     const auto t0 = std::chrono::steady_clock::now();
+    if (k == reloc_at) {
+      oc = FrameTracker::Outcome();
+      const UpdateResult res = relocalizeFrame(tracker, map, last, cur, FramePtr(), overlap_kfs, oc, (size_t)m[14]);
+      const svo_hip_reloc_result& rr = tracker.lastRelocalisation();
+      double ref = -1.0;
+      for (size_t j = 0; j < kfs.size(); ++j) if (res != RESULT_FAILURE && kfs[j] == last) ref = (double)j;
+      std::vector<double> rel{(double)res, ref, (double)tracker.deviceRelocalisations(), (double)rr.gate_n_tracked, (double)rr.accepted, (double)rr.n_close};
+      rel.insert(rel.end(), rr.T_f_w_gate, rr.T_f_w_gate + 7);
+      write_bin(out + "/track_reloc.bin", rel);
+    } else
     if (!port.track(last, cur, map, overlap_kfs, oc)) throw std::runtime_error("svo::FrameTracker::track failed at frame " + std::to_string(k));
     track_us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
     poses.insert(poses.end(), cur->T_f_w_.p, cur->T_f_w_.p + 7);
@@ -351,13 +366,13 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
 }
 
 static int track_lone(const std::string& dir, const std::string& out, bool incremental, bool times, int max_kfs, bool full_remove, int kf_every,
-                      int max_points, bool compact, int new_seeds) {
+                      int max_points, bool compact, int new_seeds, int reloc_at) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
   PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
   FrameTracker tracker(cam, track_config(m, max_kfs, max_points));
   TrackerPort port;
   port.lone = &tracker;
-  return track_demo(dir, out, port, incremental, times, max_kfs, full_remove, kf_every, compact, new_seeds);
+  return track_demo(dir, out, port, incremental, times, max_kfs, full_remove, kf_every, compact, new_seeds, reloc_at);
 }
 
 // n copies of the world, one svo::FrameTrackerGroup: every world's outputs must equal the lone tracker's
@@ -485,7 +500,7 @@ static int churn_demo(const std::string& dir, const std::string& out) {
 }
 
 int main(int argc, char** argv) {
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact]|trackgroup n|churn]\n", argv[0]); return 2; }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n|churn]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {
@@ -506,7 +521,7 @@ int main(int argc, char** argv) {
   if (argc > 3 && std::string(argv[3]) == "track") {
     try {
       bool incremental = false, times = false, full_remove = false, compact = false;     // optional trailing arguments
-      int max_kfs = 0, kf_every = 0, max_points = 0, new_seeds = 0;
+      int max_kfs = 0, kf_every = 0, max_points = 0, new_seeds = 0, reloc_at = -1;
       for (int a = 4; a < argc; ++a) {
         incremental = incremental || std::string(argv[a]) == "incremental";
         times = times || std::string(argv[a]) == "times";
@@ -515,9 +530,10 @@ int main(int argc, char** argv) {
         else if (std::string(argv[a]) == "kf_every" && a + 1 < argc) kf_every = std::atoi(argv[++a]);
         else if (std::string(argv[a]) == "max_points" && a + 1 < argc) max_points = std::atoi(argv[++a]);
         else if (std::string(argv[a]) == "new_seeds" && a + 1 < argc) new_seeds = std::atoi(argv[++a]);
+        else if (std::string(argv[a]) == "reloc_at" && a + 1 < argc) reloc_at = std::atoi(argv[++a]);
         else if (std::string(argv[a]) == "compact") compact = true;
       }
-      return track_lone(dir, out, incremental, times, max_kfs, full_remove, kf_every, max_points, compact, new_seeds);
+      return track_lone(dir, out, incremental, times, max_kfs, full_remove, kf_every, max_points, compact, new_seeds, reloc_at);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "svo_host_demo FAILED: %s\n", e.what());
       return 1;

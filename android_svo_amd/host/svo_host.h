@@ -84,6 +84,16 @@ struct PinholeCamera {            // vk::PinholeCamera: pinhole + optional 5-coe
     c.distortion = std::fabs(d[0]) > 0.0000001 ? 1 : 0;       // distortion_(fabs(d0) > 0.0000001), S/pinhole_camera.cpp:26
     return c;
   }
+  /// vk::PinholeCamera::world2cam (S/pinhole_camera.cpp:80-107): the pixel of a point in the camera frame
+  Vector2d world2cam(const Vector3d& xyz) const {
+    const double x = xyz[0] / xyz[2], y = xyz[1] / xyz[2];
+    if (!(std::fabs(d[0]) > 0.0000001)) return Vector2d{{fx * x + cx, fy * y + cy}};
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
+    const double cdist = 1 + d[0] * r2 + d[1] * r4 + d[4] * r6;
+    const double xd = x * cdist + d[2] * a1 + d[3] * a2, yd = y * cdist + d[2] * a3 + d[3] * a1;
+    return Vector2d{{xd * fx + cx, yd * fy + cy}};
+  }
 };
 
 struct Feature;
@@ -130,6 +140,13 @@ struct Frame {
   Vector3d pos() const { const SE3 T_w_f = T_f_w_.inverse(); return Vector3d{{T_w_f.p[0], T_w_f.p[1], T_w_f.p[2]}}; }   // I/frame.h: the camera centre
   void setKeyframe() { is_keyframe_ = true; setKeyPoints(); }                    // S/frame.cpp:67-71
   void addFeature(Feature* ftr) { fts_.push_back(ftr); }                         // :75-78
+  /// S/frame.cpp:162-172: the world point lies in front of the camera and projects into the image
+  bool isVisible(const Vector3d& xyz_w) const {
+    const Vector3d xyz_f = T_f_w_ * xyz_w;
+    if (xyz_f[2] < 0.0) return false;
+    const Vector2d px = cam_->world2cam(xyz_f);
+    return px[0] >= 0.0 && px[1] >= 0.0 && px[0] < cam_->width && px[1] < cam_->height;
+  }
 
   /// S/frame.cpp:83-92: key features whose point is gone are dropped, then every feature with a point competes again
   void setKeyPoints() {
@@ -303,6 +320,29 @@ struct Map {
     point_candidates_.removeFrameCandidates(frame);
     return found;
   }
+  /// :109-131: the keyframes one of whose key points the frame sees, each with the distance between the two translation_vec()
+  void getCloseKeyframes(const FramePtr& frame, std::list<std::pair<FramePtr, double>>& close_kfs) const {
+    for (const FramePtr& kf : keyframes_)
+      for (const Feature* keypoint : kf->key_pts_) {
+        if (keypoint == nullptr) continue;
+        if (frame->isVisible(keypoint->point->pos_)) {
+          const double d[3] = {frame->T_f_w_.p[0] - kf->T_f_w_.p[0], frame->T_f_w_.p[1] - kf->T_f_w_.p[1], frame->T_f_w_.p[2] - kf->T_f_w_.p[2]};
+          close_kfs.push_back(std::make_pair(kf, std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])));
+          break;                                     // this keyframe has an overlapping field of view
+        }
+      }
+  }
+  /// :133-151: the closest of them that is not the frame itself (none: no keyframe is close -- where the reference reads front()
+  /// of an empty list after the pop, the twin returns none, as the device does)
+  FramePtr getClosestKeyframe(const FramePtr& frame) const {
+    std::list<std::pair<FramePtr, double>> close_kfs;
+    getCloseKeyframes(frame, close_kfs);
+    if (close_kfs.empty()) return nullptr;
+    close_kfs.sort([](const std::pair<FramePtr, double>& l, const std::pair<FramePtr, double>& r) { return l.second < r.second; });
+    if (close_kfs.front().first != frame) return close_kfs.front().first;
+    close_kfs.pop_front();
+    return close_kfs.empty() ? nullptr : close_kfs.front().first;
+  }
   /// :156-169: the keyframe whose camera centre is furthest from pos (none: no keyframe lies away from it)
   FramePtr getFurthestKeyframe(const Vector3d& pos) const {
     FramePtr furthest;
@@ -347,6 +387,37 @@ class FrameTracker : public hip_bridge::FrameTrackerT<HostTrackerPolicy> {
  public:
   FrameTracker(const PinholeCamera& cam, const svo_hip_tracker_config& cfg) : hip_bridge::FrameTrackerT<HostTrackerPolicy>(cam.toC(), cfg) {}
 };
+
+/// FrameHandlerMono::relocalizeFrame (frame_handler_mono.cpp:317-349) as addImage calls it (:80-82: against
+/// map_.getClosestKeyframe(last_frame_)), on the bridge: with FrameTrackerT::setDeviceRelocalisation(true) the keyframe is chosen,
+/// the gate is run and the frame is tracked by ONE device call and the map is not flattened; otherwise, or when the device
+/// refuses, the keyframe is chosen on the objects and goes up as the last frame (the path there was before, without a gate).
+/// last_frame: the caller's last_frame_, set to the reference keyframe when the gate accepted (:337).  ref_keyframe: NULL = the
+/// closest one.  quality_min_fts: Config::qualityMinFts() (processFrame :208-215; :231-232 asks for 20 edges).
+enum UpdateResult { RESULT_NO_KEYFRAME, RESULT_IS_KEYFRAME, RESULT_FAILURE };      // I/frame_handler_base.h:60-64
+template <class Tracker>
+inline UpdateResult relocalizeFrame(Tracker& tracker, Map& map, FramePtr& last_frame, const FramePtr& new_frame, FramePtr ref_keyframe,
+                                    std::vector<std::pair<FramePtr, size_t>>& overlap_kfs, typename Tracker::Outcome& out, size_t quality_min_fts,
+                                    int min_tracked = 30) {
+  bool accepted = false;
+  FramePtr ref_used;
+  const FramePtr exclude = last_frame->isKeyframe() ? last_frame : FramePtr();
+  bool ok = tracker.relocalize(ref_keyframe, last_frame->T_f_w_.p, new_frame, map, overlap_kfs, out, &accepted, &ref_used, min_tracked, exclude);
+  if (!ok && ref_keyframe == nullptr) {                     // (the old path has nothing to start from: choose on the objects)
+    ref_keyframe = map.getClosestKeyframe(last_frame);
+    if (ref_keyframe == nullptr) return RESULT_FAILURE;     // "No reference keyframe." (:322-326)
+    ok = tracker.relocalize(ref_keyframe, last_frame->T_f_w_.p, new_frame, map, overlap_kfs, out, &accepted, &ref_used, min_tracked, exclude);
+  }
+  if (!ok || ref_used == nullptr || !accepted) return RESULT_FAILURE;
+  const SE3 T_f_w_last = last_frame->T_f_w_;
+  last_frame = ref_used;                                    // :337
+  if (out.repr_n_matches < quality_min_fts || out.sfba_n_edges_final < 20) {     // processFrame returned RESULT_FAILURE
+    new_frame->T_f_w_ = T_f_w_last;                         // reset to last well localized pose (:345)
+    tracker.lastFrameChanged();
+    return RESULT_FAILURE;
+  }
+  return RESULT_NO_KEYFRAME;
+}
 
 /// N cameras with a map each, tracked together (hip_bridge::FrameTrackerGroupT on this file's data model; svo_hip_tracker_group)
 class FrameTrackerGroup : public hip_bridge::FrameTrackerGroupT<HostTrackerPolicy> {

@@ -136,6 +136,67 @@ class FrameTrackerT {
   /// last_frame_ was set by somebody else (initialisation, relocalisation)
   void lastFrameChanged() { have_last_ = false; }
 
+  /// Opt-in (default off): relocalize() below runs FrameHandlerMono::relocalizeFrame on the device
+  /// (svo_hip_tracker_relocalize) instead of uploading the reference keyframe as a new last frame.  With the option off every
+  /// path is what it was.  (The C-ABI function is reached through a pointer set here, so that code which never turns the
+  /// option on does not refer to it.)
+  void setDeviceRelocalisation(bool on) { reloc_fn_ = on ? &svo_hip_tracker_relocalize : (RelocFn)NULL; }
+  bool deviceRelocalisation() const { return reloc_fn_ != NULL; }
+  /// how often relocalize() went through the device call (diagnostic), and what the last of those calls reported
+  size_t deviceRelocalisations() const { return n_relocs_; }
+  const svo_hip_reloc_result& lastRelocalisation() const { return last_reloc_; }
+
+  /// FrameHandlerMono::relocalizeFrame (frame_handler_mono.cpp:317-349) for new_frame.  ref_keyframe: the keyframe to
+  /// relocalise against, or NULL = Map::getClosestKeyframe for last_pose, chosen by the device (exclude: the caller's last frame
+  /// when that is a keyframe of the map, the reference's "front() != frame" branch).  last_pose = last_frame_->T_f_w_.
+  /// With setDeviceRelocalisation(true), a keyframe the device's tables hold and a device that accepts the call:
+  ///   *ref_used  the keyframe (NULL: none was close -- RESULT_FAILURE, nothing changed, on the device either)
+  ///   *accepted  true: the gate passed (more than min_tracked patches) and the frame went through processFrame's three stages:
+  ///              new_frame holds the outcome as after track(), and the caller sets last_frame_ = ref_keyframe as :337 does;
+  ///              false: the gate refused; new_frame->T_f_w_ is the pose the gate's SparseImgAlign::run left (:333), and the
+  ///              device's last frame is new_frame as addImage (:90) makes it the host's.
+  /// Otherwise -- option off, a keyframe the tables do not hold, a refusal of the device -- lastFrameChanged() and the path there
+  /// was before: track(ref_keyframe, new_frame) without a gate, *accepted = true; with ref_keyframe == NULL that path has
+  /// nothing to start from and the call returns false (the caller chooses the keyframe on its objects and calls again).
+  /// Returns false on a device error, as track().
+  bool relocalize(const FramePtr& ref_keyframe, const double last_pose[7], const FramePtr& new_frame, Map& map,
+                  std::vector<std::pair<FramePtr, size_t> >& overlap_kfs, Outcome& out, bool* accepted, FramePtr* ref_used,
+                  int min_tracked = 30, const FramePtr& exclude = FramePtr()) {
+    if (accepted) *accepted = false;
+    if (ref_used) *ref_used = FramePtr();
+    if (!trk_) return false;
+    if (reloc_fn_ == NULL) return relocalizeByUpload(ref_keyframe, new_frame, map, overlap_kfs, out, accepted, ref_used);
+    if (!mapCurrent(map)) return false;
+    int kf = -1, excl = -1;
+    if (ref_keyframe) {
+      std::map<int, int>::const_iterator fi = index_of_frame_.find(ref_keyframe->id_);
+      if (fi == index_of_frame_.end()) return relocalizeByUpload(ref_keyframe, new_frame, map, overlap_kfs, out, accepted, ref_used);
+      kf = fi->second;
+    }
+    if (exclude) {
+      std::map<int, int>::const_iterator fi = index_of_frame_.find(exclude->id_);
+      if (fi != index_of_frame_.end()) excl = fi->second;
+    }
+    const uint8_t* level0 = stageFrame(*new_frame);
+    svo_hip_track_result r;
+    if (reloc_fn_(trk_, level0, kf, excl, last_pose, min_tracked, &last_reloc_, &r, f_px_.data(), f_f_.data(), f_level_.data(), f_point_.data(),
+                  f_edge_.data(), f_grad_.data(), p_type_.data(), p_failed_.data(), p_succ_.data()) != SVO_HIP_OK) {
+      fprintf(stderr, "[svo_hip] FrameTracker::relocalize: the device refused (%s)\n", svo_hip_last_error(err_ctx_));
+      return relocalizeByUpload(ref_keyframe, new_frame, map, overlap_kfs, out, accepted, ref_used);
+    }
+    ++n_relocs_;
+    if (last_reloc_.kf_index < 0 || last_reloc_.kf_index >= (int)keyframes_.size()) return true;      // no keyframe is close: nothing changed
+    if (ref_used) *ref_used = keyframes_[(size_t)last_reloc_.kf_index];
+    if (last_reloc_.accepted) {
+      apply(r, new_frame, map, overlap_kfs, out);
+      if (accepted) *accepted = true;
+    } else {
+      Host::setPose(*new_frame, last_reloc_.T_f_w_gate);
+      have_last_ = true;                                       // the device's last frame is the new frame, without features
+    }
+    return true;
+  }
+
   /// new_frame->T_f_w_ = last_frame->T_f_w_; SparseImgAlign::run; Reprojector::reprojectMap; pose_optimizer::optimizeGaussNewton.
   /// Returns false on a device error (the caller treats the frame as a tracking failure).
   bool track(const FramePtr& last_frame, const FramePtr& new_frame, Map& map,
@@ -157,26 +218,9 @@ class FrameTrackerT {
   /// call + apply; a FrameTrackerGroupT calls prepare on every camera, svo_hip_tracker_group_track once, then fetch + apply.
   bool prepare(const FramePtr& last_frame, const FramePtr& new_frame, Map& map, const uint8_t** level0_out) {
     if (!trk_) return false;
-    if (!map_dirty_) {
-      // the depth filter's thread adds candidates behind the tracker's back (its convergence callback is
-      // MapPointCandidates::newCandidatePoint, frame_handler_mono.cpp:46-48): a list that has grown is flattened again
-      std::unique_lock<std::mutex> lock(map.point_candidates_.mut_);
-      const size_t n_now = map.point_candidates_.candidates_.size();
-      if (n_now != n_candidates_ && !(incremental_ && n_now > n_candidates_ && appendCandidates(map, n_now - n_candidates_))) map_dirty_ = true;
-    }
-    if (map_dirty_ && !uploadMap(map)) return false;
+    if (!mapCurrent(map)) return false;
     if (!have_last_ && !uploadLastFrame(*last_frame)) return false;
-    int stride = 0, cols = 0, rows = 0;
-    const uint8_t* level0 = Host::level0(*new_frame, &stride, &cols, &rows);
-    if (stride != cols) {                                    // the kernels assume stride == cols
-      packed_.resize((size_t)rows * cols);
-      for (int y = 0; y < rows; ++y) memcpy(&packed_[(size_t)y * cols], level0 + (size_t)y * stride, cols);
-      level0 = packed_.data();
-    }
-    const size_t cap = (size_t)cfg_.max_frame_features, np = points_.size();
-    f_px_.resize(cap * 2); f_f_.resize(cap * 3); f_level_.resize(cap); f_point_.resize(cap); f_edge_.resize(cap); f_grad_.resize(cap * 2);
-    p_type_.resize(np + 1); p_failed_.resize(np + 1); p_succ_.resize(np + 1);
-    *level0_out = level0;
+    *level0_out = stageFrame(*new_frame);
     return true;
   }
 
@@ -337,6 +381,42 @@ class FrameTrackerT {
   }
 
  private:
+  /// the device's map is the host's: flattened again if it changed, or -- the depth filter's thread adds candidates behind the
+  /// tracker's back (its convergence callback is MapPointCandidates::newCandidatePoint, frame_handler_mono.cpp:46-48) -- when
+  /// the candidate list has grown and the new tail could not be appended in place
+  bool mapCurrent(Map& map) {
+    if (!map_dirty_) {
+      std::unique_lock<std::mutex> lock(map.point_candidates_.mut_);
+      const size_t n_now = map.point_candidates_.candidates_.size();
+      if (n_now != n_candidates_ && !(incremental_ && n_now > n_candidates_ && appendCandidates(map, n_now - n_candidates_))) map_dirty_ = true;
+    }
+    return !map_dirty_ || uploadMap(map);
+  }
+  /// the new frame's full-resolution image (valid until the next call) and room for the frame's outcome
+  const uint8_t* stageFrame(const Frame& new_frame) {
+    int stride = 0, cols = 0, rows = 0;
+    const uint8_t* level0 = Host::level0(new_frame, &stride, &cols, &rows);
+    if (stride != cols) {                                    // the kernels assume stride == cols
+      packed_.resize((size_t)rows * cols);
+      for (int y = 0; y < rows; ++y) memcpy(&packed_[(size_t)y * cols], level0 + (size_t)y * stride, cols);
+      level0 = packed_.data();
+    }
+    const size_t cap = (size_t)cfg_.max_frame_features, np = points_.size();
+    f_px_.resize(cap * 2); f_f_.resize(cap * 3); f_level_.resize(cap); f_point_.resize(cap); f_edge_.resize(cap); f_grad_.resize(cap * 2);
+    p_type_.resize(np + 1); p_failed_.resize(np + 1); p_succ_.resize(np + 1);
+    return level0;
+  }
+  /// relocalisation as it was before setDeviceRelocalisation: last_frame_ = ref_keyframe goes up as any last frame somebody else
+  /// set, and the frame is tracked from it (no gate: the tracker's chain has none)
+  bool relocalizeByUpload(const FramePtr& ref_keyframe, const FramePtr& new_frame, Map& map, std::vector<std::pair<FramePtr, size_t> >& overlap_kfs,
+                          Outcome& out, bool* accepted, FramePtr* ref_used) {
+    lastFrameChanged();
+    if (!ref_keyframe) return false;                          // (the caller chooses the keyframe itself: Map::getClosestKeyframe)
+    if (ref_used) *ref_used = ref_keyframe;
+    if (!track(ref_keyframe, new_frame, map, overlap_kfs, out)) return false;
+    if (accepted) *accepted = true;
+    return true;
+  }
   /// lowest keyframe pyramid slot no known keyframe occupies, or -1
   int freeSlot() const {
     std::vector<char> used((size_t)cfg_.max_keyframes, 0);
@@ -532,6 +612,11 @@ class FrameTrackerT {
   typedef int (*CompactFn)(svo_hip_tracker*, int*, int32_t*);
   CompactFn compact_fn_ = NULL;                              // setPointCompaction: svo_hip_tracker_compact_points, or NULL
   size_t n_compactions_ = 0;
+  typedef int (*RelocFn)(svo_hip_tracker*, const uint8_t*, int, int, const double*, int, svo_hip_reloc_result*, svo_hip_track_result*, double*, double*,
+                         int32_t*, int32_t*, uint8_t*, double*, int32_t*, int32_t*, int32_t*);
+  RelocFn reloc_fn_ = NULL;                                  // setDeviceRelocalisation: svo_hip_tracker_relocalize, or NULL
+  size_t n_relocs_ = 0;
+  svo_hip_reloc_result last_reloc_ = svo_hip_reloc_result();
   std::map<int, int> index_of_frame_;                        // Frame::id_ -> keyframe index of the device tables
   size_t n_uploads_ = 0;
   size_t n_candidates_ = 0;                                  // MapPointCandidates::candidates_.size() as uploaded, minus our own deletions

@@ -633,7 +633,9 @@ int svo_hip_point_optimize_batch(svo_hip_ctx* ctx, int n_points, int n_iter, dou
  * the affected keyframes re-select before the next frame with the reference's rule -- and the result says map_changed so that
  * the host applies the same deletions to its own objects; a new upload of the map is NOT needed for that.
  * Host code keeps what it keeps in the reference: keyframe selection, Map / Point / Feature objects, optimizeStructure
- * (svo_hip_point_optimize_batch + svo_hip_tracker_update_point_positions), relocalisation (svo_hip_tracker_set_last_frame). */
+ * (svo_hip_point_optimize_batch + svo_hip_tracker_update_point_positions).  Relocalisation is a device job like everything
+ * else between two keyframes (svo_hip_tracker_relocalize below); svo_hip_tracker_set_last_frame remains the way in for a last
+ * frame the device's map does not hold (after initialisation). */
 typedef struct svo_hip_tracker svo_hip_tracker;
 
 typedef struct {
@@ -876,6 +878,77 @@ int svo_hip_tracker_remove_keyframe(svo_hip_tracker* trk, int kf_index, int* slo
  * No table grows, so there is no capacity check; n_points == 0 is valid.  SVO_HIP_ERR_STATE without a map (nothing changes).
  * One launch, synchronises once. */
 int svo_hip_tracker_compact_points(svo_hip_tracker* trk, int* n_points_after, int32_t* old_to_new);
+
+/* ---- relocalisation against a keyframe of the device map: FrameHandlerMono::relocalizeFrame (frame_handler_mono.cpp:317-349)
+ * without the host flattening its pointer graph: the keyframe's feature row, each point's observation in that keyframe, its pose
+ * and pyramid slot, and the key points Map::getClosestKeyframe walks are all in the device tables.  The first two calls take a
+ * lone tracker's handle or a handle from svo_hip_tracker_group_camera; each applies a re-selection of key points the last
+ * frame's deletions still owe first, on the rows as they were, makes one small launch and synchronises once.
+ *
+ * svo_hip_tracker_closest_keyframe: Map::getClosestKeyframe (map.cpp:109-151) for a frame with pose T_f_w (NULL: the pose of the
+ * device's last frame).  A keyframe is close when one of its five key points is Frame::isVisible from T_f_w (the first visible
+ * one decides, as the reference's break); its distance is (T_f_w.translation_vec() - T_kf_w.translation_vec()).norm() -- the
+ * translation of T_f_w, not pos(); squares summed in x, y, z order, uncontracted, then sqrt.  *kf_index = the close keyframe with
+ * the smallest distance, the LOWER index on a tie (std::list::sort is stable over keyframes_ order); *distance its distance;
+ * *n_close the close keyframes, counted before the exclusion (the last two may be NULL).  exclude_kf (-1: none) is the
+ * reference's "close_kfs.front().first != frame" branch: the host knows whether its frame is a keyframe of the map and names
+ * it; that keyframe is skipped.  When no candidate is left *kf_index = -1 and the call returns SVO_HIP_OK (the reference reads
+ * front() of an empty list there: behaviour defined here).  SVO_HIP_ERR_STATE without a map, and for
+ * T_f_w == NULL without a last frame. */
+int svo_hip_tracker_closest_keyframe(svo_hip_tracker* trk, const double T_f_w[7], int exclude_kf, int* kf_index, int* n_close,
+                                     double* distance);
+/* svo_hip_tracker_last_frame_from_keyframe: last_frame_ = ref_keyframe (frame_handler_mono.cpp:337) from the device's own tables.
+ *   - pose: row kf_index of T_kf_w; pyramid: the keyframe's slot, copied device to device into the last frame's pyramid (what
+ *     svo_hip_tracker_set_last_frame(level0 = NULL, kf_slot) does);
+ *   - features: the entries of the keyframe's feature row whose point is living (not unlinked), in row order = fts_ order, the
+ *     order SparseImgAlign::precomputeReferencePatches walks.  Entries of unlinked points are DROPPED, not kept as point = -1; a
+ *     point uploaded as TYPE_DELETED but never unlinked is a living row, as everywhere else;
+ *   - px and f of a feature: the point's observation with obs_kf == kf_index -- the FIRST such observation in the point's
+ *     observation order, should a keyframe observe a point twice.  (An entry whose point has no observation in the keyframe is no
+ *     feature of it and is dropped too; tables a host flatten writes hold none.)
+ * *n_features (may be NULL) = the features the last frame holds now.  Afterwards the tracker is exactly where
+ * svo_hip_tracker_set_last_frame leaves it: the last frame is not a tracked one (svo_hip_tracker_promote_last_frame refuses it),
+ * the solver's inputs are gathered again before the next frame, and the page-locked result block of the last tracked frame is
+ * not rewritten.  Refused with nothing changed: SVO_HIP_ERR_STATE without a map; SVO_HIP_ERR_INVALID for kf_index outside
+ * [0, n_kf), and when the living entries exceed max_frame_features (known only on the device: counted first, then decided).
+ * A camera of a group relocalises with this call followed by svo_hip_tracker_group_track, without the gate. */
+int svo_hip_tracker_last_frame_from_keyframe(svo_hip_tracker* trk, int kf_index, int* n_features);
+/* svo_hip_tracker_relocalize: FrameHandlerMono::relocalizeFrame (:317-349) as one call, for a lone tracker.
+ *   1. The reference keyframe is kf_index when kf_index >= 0, else svo_hip_tracker_closest_keyframe's answer for T_f_w_init
+ *      (last_frame_->T_f_w_; NULL: the pose of the device's last frame) with exclude_kf applied.  When none is close:
+ *      reloc->kf_index = -1, accepted = 0, SVO_HIP_OK, nothing changed -- the reference returns RESULT_FAILURE before it touches
+ *      the new frame's pose; here the device's last frame is simply kept.
+ *   2. The gate: the new image goes up and its pyramid is built as in svo_hip_tracker_track; the last frame becomes the keyframe
+ *      as in svo_hip_tracker_last_frame_from_keyframe; SparseImgAlign(kltMaxLevel, kltMinLevel, sia_n_iter, GaussNewton)
+ *      .run(ref_keyframe, new_frame) runs on the tracker's solver (its options, its SVO_HIP_SIA_OPT_REDUCTION) with T_ref_w = the
+ *      keyframe's pose and T_cur_w_init = T_f_w_init (:329-333).
+ *   3. gate_n_tracked > min_tracked (the reference's 30): accepted = 1 and the chain of svo_hip_tracker_track runs on the same
+ *      image with last_frame_ = ref_keyframe; as in the reference it starts SparseImgAlign again from the keyframe's own pose
+ *      (:175) -- the gate's pose is reported, not used.  result and the feature / counter outputs (those of
+ *      svo_hip_tracker_track; any may be NULL) are that frame's, and the new frame is the device's last frame like any tracked
+ *      one (svo_hip_tracker_promote_last_frame works on it).  Otherwise accepted = 0: the map tables and point counters are
+ *      untouched (the gate only reads), the device's last frame is the new image with zero features and the pose T_f_w_gate --
+ *      what addImage (:90) leaves in last_frame_, of which the reference's next attempt reads only that pose -- and result is
+ *      not written.
+ * Synchronises after the choice (the keyframe's feature count steers the solver's launch), after the gate and at the end of the
+ * chain.  Refused before anything is enqueued, nothing changed: SVO_HIP_ERR_STATE without a map, for T_f_w_init == NULL
+ * without a last frame, and for a handle of a group of more than one camera (a group tracks all its cameras per call);
+ * SVO_HIP_ERR_INVALID for kf_index >= n_kf, min_tracked < 0, a NULL level0 / reloc.  SVO_HIP_ERR_INVALID with the last frame
+ * kept when the keyframe's living features exceed max_frame_features.  On every error path after the first enqueue the stream
+ * is synchronised before the call returns. */
+typedef struct {
+  int32_t kf_index;          /* the reference keyframe (the argument, or the device's choice); -1: none was close */
+  int32_t n_close;           /* valid when the device chose */
+  int32_t accepted;          /* 1: gate_n_tracked > min_tracked and the frame went through processFrame's stages */
+  int32_t gate_stop;
+  uint64_t gate_n_tracked;   /* img_align_n_tracked of :333 */
+  int32_t gate_iters[SVO_HIP_MAX_LEVELS];
+  double T_f_w_gate[7];      /* new_frame_->T_f_w_ as img_align.run leaves it (:333) */
+} svo_hip_reloc_result;
+int svo_hip_tracker_relocalize(svo_hip_tracker* trk, const uint8_t* level0, int kf_index, int exclude_kf, const double T_f_w_init[7],
+                               int min_tracked, svo_hip_reloc_result* reloc, svo_hip_track_result* result, double* feat_px,
+                               double* feat_f, int32_t* feat_level, int32_t* feat_point, uint8_t* feat_edgelet, double* feat_grad,
+                               int32_t* pt_type, int32_t* pt_n_failed, int32_t* pt_n_succeeded);
 /* diagnostics and parity tests: the sizes of the tables the device holds, and the tables themselves in svo_hip_tracker_map's
  * layout (the key points with the owed re-selections applied).  The caller's buffers hold at least the sizes
  * svo_hip_tracker_map_sizes reports (kf_ftr_offset n_kf + 1, pt_obs_offset n_points + 1); a NULL pointer skips its table.
