@@ -26,6 +26,7 @@
 //     (cell.sort(pointQualityComparator)) -- every item gets its sequence number and a rank inside its cell;
 //   * all candidates are matched in one batch, then "first success per cell wins, stop once n_matches exceeds maxFts" is
 //     replayed over the results (Matcher::findMatchDirect is a pure function of its candidate).
+#include <cfloat>
 #include <climits>
 #include <cstring>
 #include <new>
@@ -971,12 +972,12 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_compact_kernel(TrkMap m, TrkT
 // positions written into the point table, into the solver's copy of the last frame's points (the next SparseImgAlign::run reads
 // point->pos_) and into the page-locked result block.  One workgroup.
 struct TrkStructSel { int n; int point[TRK_MAX_STRUCT]; };
-__global__ __launch_bounds__(256) void trk_structure_kernel(TrkMap m, double* __restrict__ pt_pos, TrkLast last, TrkStructSel sel, int n_iter,
-                                                            double* __restrict__ out_pos, int* __restrict__ out_iters,
-                                                            unsigned long long* __restrict__ done_flag, unsigned long long seq) {
+// (the body of trk_structure_kernel up to its hand-over: trk_finish_frame_body runs it in front of the keyframe decision)
+SVO_DEV void trk_structure_body(const TrkMap& m, double* __restrict__ pt_pos, const TrkLast& last, const TrkStructSel& sel, int n_iter,
+                                double* __restrict__ out_pos, int* __restrict__ out_iters) {
   __shared__ double s_new[TRK_MAX_STRUCT][3];
-  const int t = threadIdx.x, nt = blockDim.x;
-  if (t < sel.n) {
+  const int t = threadIdx.x, nt = blockDim.x, n_sel = sel.n;
+  if (t < n_sel) {
     const int p = sel.point[t];
     double P[3] = {pt_pos[3 * (size_t)p], pt_pos[3 * (size_t)p + 1], pt_pos[3 * (size_t)p + 2]};
     const int done = point_refine_one(P, m.pt_obs_offset[p], m.pt_obs_offset[p + 1], n_iter, [&](int o, double* T, double* fo) {
@@ -992,12 +993,222 @@ __global__ __launch_bounds__(256) void trk_structure_kernel(TrkMap m, double* __
   for (int j = t; j < n_last; j += nt) {
     const int p = last.point[j];
     if (p < 0) continue;
-    for (int i = 0; i < sel.n; ++i)
+    for (int i = 0; i < n_sel; ++i)
       if (sel.point[i] == p) { last.sia_pos[3 * j] = s_new[i][0]; last.sia_pos[3 * j + 1] = s_new[i][1]; last.sia_pos[3 * j + 2] = s_new[i][2]; }
   }
+}
+__global__ __launch_bounds__(256) void trk_structure_kernel(TrkMap m, double* __restrict__ pt_pos, TrkLast last, TrkStructSel sel, int n_iter,
+                                                            double* __restrict__ out_pos, int* __restrict__ out_iters,
+                                                            unsigned long long* __restrict__ done_flag, unsigned long long seq) {
+  const int t = threadIdx.x;
+  trk_structure_body(m, pt_pos, last, sel, n_iter, out_pos, out_iters);
   __threadfence_system();
   __syncthreads();
   if (t == 0) __hip_atomic_store(done_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- the keyframe decision behind the structure step (FrameHandlerMono::processFrame, S/frame_handler_mono.cpp:258-260, :305):
+// frame_utils::getSceneDepth (S/frame.cpp:200-221), needNewKf (:391-403) and Map::getFurthestKeyframe (S/map.cpp:156-169) of the
+// device's last frame.  One workgroup of FIN_THREADS; block-uniform call.  pt_pos: the table the structure step has just written
+// (read through the same pointer, behind the caller's barrier).
+//   depths     every thread walks its features; the numbers become order-preserving 64-bit keys in LDS (any order: what is
+//              asked for is an order statistic), the minimum (and the maximum) an integer comparison of the keys
+//   median     radix select on the keys, 8 bits a pass from the first byte the keys differ in: a 256-bin histogram of the keys
+//              that share the prefix so far, its scan, and the bin that holds the rank extends the prefix -- exact, O(n), no
+//              floating-point atomics
+//   needNewKf  one thread per overlap keyframe, the first blocking one in list order
+//   furthest   one thread per keyframe (TRK_LDS_KF <= FIN_THREADS); "dist > maxdist from 0.0" in index order = the largest
+//              distance above zero, the lower index among equals, a NaN never: reduced with that order
+constexpr int FIN_THREADS = 256;
+constexpr int FIN_MAX_FEAT = 2816;             // svo_hip_tracker_config::max_frame_features <= this (trk_check_config)
+SVO_DEV unsigned long long depth_key(double z) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(z);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+SVO_DEV double depth_from_key(unsigned long long k) {
+  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __longlong_as_double((long long)u);
+}
+SVO_DEV void trk_decision_body(const TrkMap& m, const double* pt_pos, const TrkLast& last, const int* __restrict__ overlap_kf,
+                               const int* __restrict__ counters, int overlap_valid, double min_dist, svo_hip_kf_decision* __restrict__ out) {
+  static_assert(TRK_LDS_KF <= FIN_THREADS, "one keyframe per thread");
+  static_assert(TRK_MAX_SEL <= FIN_THREADS, "one overlap keyframe per thread");
+  __shared__ unsigned long long s_key[FIN_MAX_FEAT];
+  __shared__ unsigned long long s_min_key, s_max_key, s_prefix;
+  __shared__ int s_hist[256], s_wave[FIN_THREADS / 64];
+  __shared__ int s_n, s_n_nan, s_rank, s_block[TRK_MAX_SEL];
+  __shared__ double s_T[7], s_pos[3], s_wdist[FIN_THREADS / 64];
+  __shared__ int s_wkf[FIN_THREADS / 64];
+  const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6;
+  if (t < 7) s_T[t] = last.T_f_w[t];
+  if (t == 0) { s_n = 0; s_n_nan = 0; s_min_key = ~0ull; s_max_key = 0ull; }
+  s_hist[t] = 0;
+  __syncthreads();
+  double T[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) T[i] = s_T[i];
+  if (t == 0) {
+    double Tinv[7];
+    se3_inverse(T, Tinv);                                                      // Frame::pos()
+    s_pos[0] = Tinv[0]; s_pos[1] = Tinv[1]; s_pos[2] = Tinv[2];
+  }
+  // ---- the depths: a wave appends its keys with one atomic (ranks inside the wave from the ballot) and keeps the smallest
+  // and the largest key and its NaN count in registers
+  const int n_last = *last.n < FIN_MAX_FEAT ? *last.n : FIN_MAX_FEAT;
+  unsigned long long kmin = ~0ull, kmax = 0ull;
+  int my_nan = 0;
+  for (int base = 0; base < n_last; base += nt) {                              // block-uniform
+    const int j = base + t;
+    const int p = j < n_last ? last.point[j] : -1;
+    bool have = false;
+    unsigned long long key = 0ull;
+    if (p >= 0 && p < m.n_points) {
+      double xyz_f[3];
+      se3_act(T, pt_pos + 3 * (size_t)p, xyz_f);
+      const double z = xyz_f[2];
+      if (z != z) ++my_nan;
+      else { have = true; key = depth_key(z); }
+    }
+    const unsigned long long bal = __ballot(have);
+    if (bal != 0ull) {                                                         // wave-uniform
+      const int first = __ffsll((long long)bal) - 1;
+      int slot = 0;
+      if (lane == first) slot = atomicAdd(&s_n, __popcll(bal));
+      slot = __shfl(slot, first, 64);
+      if (have) {
+        s_key[slot + __popcll(bal & ((1ull << lane) - 1ull))] = key;
+        kmin = key < kmin ? key : kmin; kmax = key > kmax ? key : kmax;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const unsigned long long a = __shfl_xor(kmin, o, 64), b = __shfl_xor(kmax, o, 64);
+    kmin = a < kmin ? a : kmin; kmax = b > kmax ? b : kmax;
+    my_nan += __shfl_xor(my_nan, o, 64);
+  }
+  if (lane == 0) {
+    atomicMin(&s_min_key, kmin); atomicMax(&s_max_key, kmax);
+    if (my_nan) atomicAdd(&s_n_nan, my_nan);
+  }
+  __syncthreads();
+  const int n = s_n, n_nan = s_n_nan;
+  const bool have_median = n > 0 && n_nan == 0;
+  // ---- the median: the key of rank n / 2.  The bytes the smallest and the largest key share are every key's: the selection
+  // starts at the first byte in which they differ (none: all depths are equal).
+  const unsigned long long spread = s_min_key ^ s_max_key;
+  const int first_shift = spread == 0ull ? -8 : 56 - (__clzll((long long)spread) & ~7);
+  if (t == 0) { s_rank = n / 2; s_prefix = first_shift >= 56 ? 0ull : first_shift < 0 ? s_min_key : s_min_key & (~0ull << (first_shift + 8)); }
+  __syncthreads();
+  if (have_median) {                                                           // block-uniform
+    for (int shift = first_shift; shift >= 0; shift -= 8) {                    // (every bin is zero here)
+      const unsigned long long prefix = s_prefix;
+      const int rank = s_rank;
+      const unsigned long long above = shift == 56 ? 0ull : ~0ull << (shift + 8);
+      for (int j = t; j < n; j += nt) {
+        const unsigned long long k = s_key[j];
+        if ((k & above) == prefix) atomicAdd(&s_hist[(int)((k >> shift) & 255ull)], 1);
+      }
+      __syncthreads();
+      const int c = s_hist[t];
+      s_hist[t] = 0;                                                           // (nobody else reads this bin)
+      int incl = c;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+      }
+      if (lane == 63) s_wave[wave] = incl;
+      __syncthreads();
+      int before = 0;
+      for (int w = 0; w < wave; ++w) before += s_wave[w];
+      const int excl = before + incl - c;
+      if (rank >= excl && rank < excl + c) {                                   // exactly one bin holds the rank
+        s_prefix = prefix | ((unsigned long long)t << shift);
+        s_rank = rank - excl;
+      }
+      __syncthreads();
+    }
+  }
+  // ---- needNewKf: rel = T_f_w * kf->pos() of every overlap keyframe
+  const double depth_mean = have_median ? depth_from_key(s_prefix) : __longlong_as_double(0x7ff8000000000000ll);
+  const int n_overlap = overlap_valid ? (counters[3] < TRK_MAX_SEL ? counters[3] : TRK_MAX_SEL) : 0;
+  if (t < n_overlap) {
+    const int k = overlap_kf[t];
+    int block = 0;
+    if (k >= 0 && k < m.n_kf) {
+      const double* tk = m.T_kf_w + 7 * (size_t)k;
+      double Tk[7], Tinv[7], rel[3];
+#pragma unroll
+      for (int i = 0; i < 7; ++i) Tk[i] = tk[i];
+      se3_inverse(Tk, Tinv);
+      se3_act(T, Tinv, rel);
+      block = fabs(rel[0]) / depth_mean < min_dist && fabs(rel[1]) / depth_mean < min_dist * 0.8 && fabs(rel[2]) / depth_mean < min_dist * 1.3;
+    }
+    s_block[t] = block;
+  }
+  // ---- Map::getFurthestKeyframe
+  double best_d = 0.0;
+  int best_k = INT_MAX;
+  if (t < m.n_kf && t < TRK_LDS_KF) {
+    const double* tk = m.T_kf_w + 7 * (size_t)t;
+    double Tk[7], Tinv[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) Tk[i] = tk[i];
+    se3_inverse(Tk, Tinv);
+    const double dx = Tinv[0] - s_pos[0], dy = Tinv[1] - s_pos[1], dz = Tinv[2] - s_pos[2];
+    const double d = sqrt(dx * dx + dy * dy + dz * dz);
+    if (d > 0.0) { best_d = d; best_k = t; }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const double od = __shfl_xor(best_d, o, 64);
+    const int ok = __shfl_xor(best_k, o, 64);
+    if (od > best_d || (od == best_d && ok < best_k)) { best_d = od; best_k = ok; }
+  }
+  if (lane == 0) { s_wdist[wave] = best_d; s_wkf[wave] = best_k; }
+  __syncthreads();
+  if (t == 0) {
+    for (int w = 1; w < FIN_THREADS / 64; ++w)
+      if (s_wdist[w] > best_d || (s_wdist[w] == best_d && s_wkf[w] < best_k)) { best_d = s_wdist[w]; best_k = s_wkf[w]; }
+    svo_hip_kf_decision r;
+    r.n_depths = n; r.n_nan_depths = n_nan;
+    r.depth_mean = depth_mean;
+    r.depth_min = n > 0 ? depth_from_key(s_min_key) : DBL_MAX;
+    r.overlap_valid = overlap_valid ? 1 : 0;
+    r.need_new_kf = overlap_valid ? 1 : -1;
+    r.blocking_kf = -1;
+    for (int i = 0; i < n_overlap; ++i)
+      if (s_block[i]) { r.need_new_kf = 0; r.blocking_kf = overlap_kf[i]; break; }
+    r.furthest_kf = best_k == INT_MAX ? -1 : best_k;
+    r.furthest_distance = best_k == INT_MAX ? 0.0 : best_d;
+    r.pos[0] = s_pos[0]; r.pos[1] = s_pos[1]; r.pos[2] = s_pos[2];
+    *out = r;                              // (out lies in host memory: written, never read back here)
+  }
+}
+
+// The structure step, a barrier, the decision, the hand-over.  st: the camera's page-locked block [pos 64 x 3][iters 64][flag]
+// [decision] (device address).
+constexpr size_t ST_O_ITERS = TRK_MAX_STRUCT * 24, ST_O_FLAG = ST_O_ITERS + TRK_MAX_STRUCT * 4, ST_O_DECISION = ST_O_FLAG + 64;
+constexpr size_t ST_BYTES = ST_O_DECISION + 128;
+static_assert(sizeof(svo_hip_kf_decision) <= 128, "the decision fits its part of the block");
+SVO_DEV void trk_finish_frame_body(const TrkMap& m, double* __restrict__ pt_pos, const TrkLast& last, const TrkStructSel& sel, int n_iter,
+                                   const int* __restrict__ overlap_kf, const int* __restrict__ counters, int overlap_valid, double min_dist,
+                                   char* st, unsigned long long seq) {
+  if (sel.n > 0) {                                                             // block-uniform
+    trk_structure_body(m, pt_pos, last, sel, n_iter, reinterpret_cast<double*>(st), reinterpret_cast<int*>(st + ST_O_ITERS));
+    __syncthreads();                                                           // the decision reads the new positions
+  }
+  trk_decision_body(m, pt_pos, last, overlap_kf, counters, overlap_valid, min_dist, reinterpret_cast<svo_hip_kf_decision*>(st + ST_O_DECISION));
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(st + ST_O_FLAG), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// (one workgroup per camera and nothing beside it: the occupancy bound leaves the structure step's per-thread arrays their place in LDS)
+__global__ __launch_bounds__(FIN_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) void trk_finish_frame_kernel(TrkMap m, double* __restrict__ pt_pos, TrkLast last, TrkStructSel sel, int n_iter,
+                                                                       const int* __restrict__ overlap_kf, const int* __restrict__ counters,
+                                                                       int overlap_valid, double min_dist, char* st, unsigned long long seq) {
+  trk_finish_frame_body(m, pt_pos, last, sel, n_iter, overlap_kf, counters, overlap_valid, min_dist, st, seq);
 }
 
 // ---- last_frame_ = new_frame_ (frame_handler_mono.cpp:91) and the result block.  One workgroup.
@@ -1123,6 +1334,29 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_replay_one_kernel(TrkCamArgs 
   trk_replay_args(a, max_fts, quality_min_fts);
 }
 __global__ __launch_bounds__(256) void trk_finish_one_kernel(TrkCamArgs a, unsigned long long seq) { trk_finish_args(a, seq); }
+
+// svo_hip_tracker_group_finish_frames: workgroup c finishes camera c's frame.  The tables come from the chain's argument table, what
+// changes with every call from a page-locked array the kernel reads directly (a camera that sits out: active == 0).
+struct TrkFinishReq {
+  TrkStructSel sel;
+  int n_iter, active, overlap_valid, pad;
+  char* st;                            // the camera's page-locked block (device address)
+  unsigned long long seq;
+};
+__global__ __launch_bounds__(FIN_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) void trk_finish_frames_cams_kernel(const TrkCamArgs* __restrict__ args, const TrkFinishReq* __restrict__ req,
+                                                                             double min_dist) {
+  // the request crosses the link once, into LDS (the structure step compares every feature of the last frame with the selection)
+  static_assert(sizeof(TrkFinishReq) % 4 == 0 && sizeof(TrkFinishReq) / 4 <= FIN_THREADS, "one word per thread");
+  __shared__ TrkFinishReq s_req;
+  if (threadIdx.x < sizeof(TrkFinishReq) / 4)
+    reinterpret_cast<unsigned*>(&s_req)[threadIdx.x] = reinterpret_cast<const unsigned*>(req + blockIdx.x)[threadIdx.x];
+  __syncthreads();
+  const TrkFinishReq& r = s_req;
+  if (!r.active) return;                                                       // block-uniform
+  const TrkCamArgs& a = args[blockIdx.x];
+  trk_finish_frame_body(a.m, const_cast<double*>(a.m.pt_pos), a.last, r.sel, r.n_iter, a.pl.overlap_kf, a.pl.counters, r.overlap_valid, min_dist,
+                        r.st, r.seq);
+}
 
 // Point::pos_ of n points after the host optimised them: one staged block in, one launch
 __global__ void trk_scatter_positions_kernel(int n, const int* __restrict__ idx, const double* __restrict__ pos, double* __restrict__ pt_pos) {
@@ -1305,6 +1539,8 @@ struct svo_hip_tracker_shared {
   TrkCamArgs* args_host = nullptr;          // page-locked: the bytes of the last upload
   TrkCamArgs* args_dev = nullptr;
   bool args_valid = false;                  // args_dev holds args_host
+  TrkFinishReq* fin_host = nullptr;         // page-locked, mapped: the cameras' requests of svo_hip_tracker_group_finish_frames
+  TrkFinishReq* fin_dev = nullptr;
   unsigned long long seq = 0;               // frames tracked: the hand-over kernel stores it behind every camera's block (o_flag)
   std::vector<svo_hip_tracker*> members;
   std::vector<void*> dev_allocs;
@@ -1333,6 +1569,7 @@ struct svo_hip_tracker {
   std::vector<int> kf_slot_host;            // kf_slot as the device holds it (svo_hip_tracker_promote_last_frame checks against it)
   int track_n_points = 0;                   // n_points when the last frame was tracked: the layout of the counters in the result block
   bool have_map = false, have_last = false;
+  bool overlap_valid = false;               // pl.overlap_kf / counters[3] are the last frame's and still name keyframes of the map (svo_hip_tracker_finish_frame)
   bool rekey_pending = false;               // the last frame deleted points: keyframes that lost a key feature choose again before the next frame
   int last_n_host = 0;
   int last_max_point = -1;                  // largest map point index the last frame's features refer to (set_last_frame input)
@@ -1352,7 +1589,7 @@ struct svo_hip_tracker {
   char* res_host = nullptr;                 // page-locked, mapped into the device: the hand-over kernel writes it directly
   size_t o_flag = 0;
   uint8_t* img_dev = nullptr;               // device address of img_host (this camera's part of the shared image block)
-  char* st_host = nullptr;                  // page-locked result of svo_hip_tracker_optimize_structure: [pos 64 x 3][iters 64][flag]
+  char* st_host = nullptr;                  // page-locked result of svo_hip_tracker_optimize_structure / _finish_frame: [pos 64 x 3][iters 64][flag][decision]
   char* st_dev = nullptr;
   unsigned long long st_seq = 0;
   size_t o_px = 0, o_f = 0, o_level = 0, o_point = 0, o_edge = 0, o_grad = 0, o_pt = 0, res_bytes = 0;
@@ -1463,6 +1700,7 @@ static void trk_shared_destroy(svo_hip_tracker_shared* sh) {
   for (void* p : sh->dev_allocs) if (p) (void)hipFree(p);
   if (sh->img_host) (void)hipHostFree(sh->img_host);
   if (sh->args_host) (void)hipHostFree(sh->args_host);
+  if (sh->fin_host) (void)hipHostFree(sh->fin_host);
   delete sh;
 }
 
@@ -1523,6 +1761,8 @@ static int trk_shared_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const 
   if (rc == SVO_HIP_OK && hipHostGetDevicePointer((void**)&sh->img_dev, sh->img_host, 0) != hipSuccess) rc = SVO_HIP_ERR_DEVICE;
   if (rc == SVO_HIP_OK && hipHostMalloc((void**)&sh->args_host, N * sizeof(TrkCamArgs), hipHostMallocDefault) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
   D(&sh->args_dev, N);
+  if (rc == SVO_HIP_OK && hipHostMalloc((void**)&sh->fin_host, N * sizeof(TrkFinishReq), hipHostMallocMapped) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
+  if (rc == SVO_HIP_OK && hipHostGetDevicePointer((void**)&sh->fin_dev, sh->fin_host, 0) != hipSuccess) rc = SVO_HIP_ERR_DEVICE;
   if (rc == SVO_HIP_OK) sh->args_next.resize(N);
   if (rc != SVO_HIP_OK) { trk_shared_destroy(sh); return rc; }
   *out = sh;
@@ -1573,7 +1813,7 @@ static int trk_member_create(svo_hip_tracker_shared* sh, int index, const svo_hi
   if (rc == SVO_HIP_OK) memset(t->res_host, 0, t->res_bytes);
   t->img_host = sh->img_host + sh->img_stride * (size_t)index;
   t->img_dev = sh->img_dev + sh->img_stride * (size_t)index;
-  const size_t st_bytes = TRK_MAX_STRUCT * (24 + 4) + 64;
+  const size_t st_bytes = ST_BYTES;
   if (rc == SVO_HIP_OK && hipHostMalloc((void**)&t->st_host, st_bytes, hipHostMallocMapped) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
   if (rc == SVO_HIP_OK) memset(t->st_host, 0, st_bytes);
   if (rc == SVO_HIP_OK && hipHostGetDevicePointer((void**)&t->st_dev, t->st_host, 0) != hipSuccess) rc = SVO_HIP_ERR_DEVICE;
@@ -1718,6 +1958,7 @@ int svo_hip_tracker_set_map(svo_hip_tracker* t, const svo_hip_tracker_map* mp) {
   t->any_edgelet = false;
   if (mp->obs_edgelet) for (int o = 0; o < n_obs && !t->any_edgelet; ++o) t->any_edgelet = mp->obs_edgelet[o] != 0;
   t->have_map = true; t->rekey_pending = false;
+  t->overlap_valid = false;                 // the keyframes may be others now
   t->need_gather = true;                    // point positions may have changed
   return SVO_HIP_OK;
 }
@@ -1816,6 +2057,7 @@ int svo_hip_tracker_set_last_frame(svo_hip_tracker* t, const uint8_t* level0, in
   t->last_from_track = false;
   t->last_renumbered = false;
   t->have_last = true;
+  t->overlap_valid = false;
   t->need_gather = true;
   return SVO_HIP_OK;
 }
@@ -1840,6 +2082,44 @@ static void trk_copy_out(svo_hip_tracker* t, svo_hip_track_result* result, doubl
   if (pt_n_succeeded) memcpy(pt_n_succeeded, rh + t->o_pt + 2 * np4, np4);
 }
 
+// The cameras' arguments of the chain's kernels: one table, uploaded only when it differs from the last upload (the map, the
+// scratch behind the records); the previous call's kernels are through with the staging copy: the host waited for them.  A lone
+// tracker passes its entry by value instead (trk_plan_one_kernel) and uploads nothing.
+static int trk_args_table(svo_hip_tracker_shared* sh, SeedRec* recs) {
+  svo_hip_ctx* ctx = sh->ctx;
+  const int N = sh->n_cams;
+  svo_hip_tracker* t0 = sh->members[0];
+  const svo_hip_tracker_config& c = t0->cfg;
+  const int stride = sh->rec_stride;
+  MdFrame mf;
+  memset(&mf, 0, sizeof(mf));
+  mf.cam = svo_make_cam(t0->cam); mf.n_pyr_levels = c.n_pyr_levels; mf.n_kf = c.max_keyframes; mf.n_ref_levels = c.n_levels;
+  TrkCamArgs* an = sh->args_next.data();
+  memset(an, 0, (size_t)N * sizeof(TrkCamArgs));
+  for (int k = 0; k < N; ++k) {
+    svo_hip_tracker* t = sh->members[(size_t)k];
+    TrkCamArgs& a = an[k];
+    a.m = make_map(t); a.pl = t->pl; a.ft = t->ft; a.last = t->last;
+    a.mf = mf; a.mf.slot_base = k * c.max_keyframes;
+    a.T_slot_w = t->T_slot_w;
+    a.recs = recs + (size_t)k * stride;
+    a.sia_state = svo_sia_state_dev(sh->sia, k);
+    a.cell_winner = t->cell_winner; a.cell_cum = t->cell_cum;
+    a.po = t->po;
+    a.res = t->res_dev;
+    a.o_px = t->o_px; a.o_f = t->o_f; a.o_level = t->o_level; a.o_point = t->o_point; a.o_edge = t->o_edge; a.o_grad = t->o_grad; a.o_pt = t->o_pt;
+    a.o_flag = t->o_flag;
+  }
+  const size_t args_bytes = (size_t)N * sizeof(TrkCamArgs);
+  if (N > 1 && (!sh->args_valid || memcmp(sh->args_host, an, args_bytes) != 0)) {
+    sh->args_valid = false;
+    memcpy(sh->args_host, an, args_bytes);
+    SVO_CHECK_HIP(ctx, hipMemcpyAsync(sh->args_dev, sh->args_host, args_bytes, hipMemcpyHostToDevice, ctx->stream));
+    sh->args_valid = true;
+  }
+  return SVO_HIP_OK;
+}
+
 // One frame for every camera of the shared part: ONE chain of launches whatever the number of cameras.  level0[c]: camera c's
 // new image (its own page-locked buffer: no copy).
 // image_ready: the new frames' pyramids are built already (svo_hip_tracker_relocalize, whose gate ran on them).
@@ -1854,6 +2134,7 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
       return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "svo_hip_tracker_set_map and svo_hip_tracker_set_last_frame come first (every camera)");
   }
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  for (int k = 0; k < N; ++k) sh->members[(size_t)k]->overlap_valid = false;    // (until the chain has completed: its plan rewrites the list)
   const size_t l0 = (size_t)t0->cam.width * t0->cam.height;
   svo_hip_pyramid* ref = sh->frame_pyr[sh->last_idx];
   svo_hip_pyramid* cur = sh->frame_pyr[1 - sh->last_idx];
@@ -1897,35 +2178,9 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
   const int stride = sh->rec_stride;
   rc = svo_match_scratch(ctx, N * stride, &recs, &pwb_t, &n_pad);
   if (rc != SVO_HIP_OK) return rc;
-  MdFrame mf;
-  memset(&mf, 0, sizeof(mf));
-  mf.cam = cam; mf.n_pyr_levels = c.n_pyr_levels; mf.n_kf = c.max_keyframes; mf.n_ref_levels = c.n_levels;
-  // the cameras' arguments: one table, uploaded only when it differs from the last upload (the map, the scratch behind the
-  // records); the previous call's kernels are through with the staging copy: this thread waited for them.  A lone tracker
-  // passes its entry by value instead (trk_plan_one_kernel).
-  TrkCamArgs* an = sh->args_next.data();
-  memset(an, 0, (size_t)N * sizeof(TrkCamArgs));
-  for (int k = 0; k < N; ++k) {
-    svo_hip_tracker* t = sh->members[(size_t)k];
-    TrkCamArgs& a = an[k];
-    a.m = make_map(t); a.pl = t->pl; a.ft = t->ft; a.last = t->last;
-    a.mf = mf; a.mf.slot_base = k * c.max_keyframes;
-    a.T_slot_w = t->T_slot_w;
-    a.recs = recs + (size_t)k * stride;
-    a.sia_state = svo_sia_state_dev(sh->sia, k);
-    a.cell_winner = t->cell_winner; a.cell_cum = t->cell_cum;
-    a.po = t->po;
-    a.res = t->res_dev;
-    a.o_px = t->o_px; a.o_f = t->o_f; a.o_level = t->o_level; a.o_point = t->o_point; a.o_edge = t->o_edge; a.o_grad = t->o_grad; a.o_pt = t->o_pt;
-    a.o_flag = t->o_flag;
-  }
-  const size_t args_bytes = (size_t)N * sizeof(TrkCamArgs);
-  if (N > 1 && (!sh->args_valid || memcmp(sh->args_host, an, args_bytes) != 0)) {
-    sh->args_valid = false;
-    memcpy(sh->args_host, an, args_bytes);
-    SVO_CHECK_HIP(ctx, hipMemcpyAsync(sh->args_dev, sh->args_host, args_bytes, hipMemcpyHostToDevice, ctx->stream));
-    sh->args_valid = true;
-  }
+  rc = trk_args_table(sh, recs);
+  if (rc != SVO_HIP_OK) return rc;
+  const TrkCamArgs* an = sh->args_next.data();
   const TrkCamArgs* ad = sh->args_dev;
   if (N == 1) hipLaunchKernelGGL(trk_plan_one_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, an[0]);
   else hipLaunchKernelGGL(trk_plan_cams_kernel, dim3(N), dim3(TRK_THREADS), 0, ctx->stream, ad);
@@ -1978,6 +2233,7 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
     t->last_from_track = true;
     t->last_renumbered = false;
     t->need_gather = false;
+    t->overlap_valid = true;
     if (r->map_changed) t->rekey_pending = true;
   }
   return SVO_HIP_OK;
@@ -2171,6 +2427,7 @@ int svo_hip_tracker_promote_last_frame(svo_hip_tracker* t, int slot, int* kf_ind
   if (n_promoted_candidates) *n_promoted_candidates = out[0];
   t->kf_slot_host.push_back(slot);
   t->n_kf += 1;
+  t->overlap_valid = false;                 // the frame is a keyframe of the map now
   if (!t->any_edgelet) {                    // the new observations carry the frame's edgelet flags
     const uint8_t* fe = reinterpret_cast<const uint8_t*>(t->res_host + t->o_edge);
     for (int i = 0; i < n_feat && !t->any_edgelet; ++i) t->any_edgelet = fp[i] >= 0 && fe[i] != 0;
@@ -2198,6 +2455,7 @@ int svo_hip_tracker_remove_keyframe(svo_hip_tracker* t, int kf_index, int* slot_
   if (n_deleted_candidates) *n_deleted_candidates = out[4];
   t->kf_slot_host.erase(t->kf_slot_host.begin() + kf_index);
   t->n_kf -= 1;
+  t->overlap_valid = false;                 // the keyframes are renumbered
   // the keyframes that lost a key feature to a point deleted here choose again (Frame::removeKeyPoint), on the new rows,
   // before anything reads the key points
   if (out[0] > 0) t->rekey_pending = true;
@@ -2265,6 +2523,7 @@ static int trk_last_is_keyframe(svo_hip_tracker* t, int k, const TrkRelocOut& o)
   t->last_from_track = false;
   t->last_renumbered = false;
   t->have_last = true;
+  t->overlap_valid = false;
   t->need_gather = true;
   return rc;
 }
@@ -2368,6 +2627,140 @@ int svo_hip_tracker_relocalize(svo_hip_tracker* t, const uint8_t* level0, int kf
   sh->last_idx = 1 - sh->last_idx;
   t->last_n_host = 0;
   t->last_max_point = -1;
+  return SVO_HIP_OK;
+}
+
+// ---- the structure step and the keyframe decision in one call (svo_hip_tracker_finish_frame, svo_hip_tracker_group_finish_frames)
+
+// what svo_hip_tracker_optimize_structure checks of a selection (the map has to be there), and the selection as the kernel takes it
+static int trk_finish_check(svo_hip_tracker* t, int n, const int32_t* point, int n_iter, const double* pos_out, TrkStructSel* sel) {
+  svo_hip_ctx* ctx = t->ctx;
+  SVO_REQUIRE(ctx, n >= 0 && n <= TRK_MAX_STRUCT && n_iter >= 0 && (n == 0 || (point && pos_out)));
+  memset(sel, 0, sizeof(*sel));
+  sel->n = n;
+  for (int i = 0; i < n; ++i) {
+    SVO_REQUIRE(ctx, point[i] >= 0 && point[i] < t->n_points);
+    for (int j = 0; j < i; ++j) SVO_REQUIRE(ctx, point[j] != point[i]);         // a point is optimised once per call
+    sel->point[i] = point[i];
+  }
+  return SVO_HIP_OK;
+}
+
+// the one wait: every listed camera's flag shows its sequence number (a spin on page-locked memory, the stream's own
+// synchronisation as the fall-back and the error check)
+static int trk_finish_wait(svo_hip_ctx* ctx, svo_hip_tracker* const* cams, int n_cams, const char* who) {
+  auto done = [&](int k) {
+    volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(cams[k]->st_host + ST_O_FLAG);
+    return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == cams[k]->st_seq;
+  };
+  bool all = false;
+  for (long spins = 0; spins < 4000000L && !all; ++spins) {
+    all = true;
+    for (int k = 0; k < n_cams && all; ++k) all = done(k);
+    if (!all) __builtin_ia32_pause();
+  }
+  if (!all) SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < n_cams; ++k)
+    if (!done(k)) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "the kernel did not complete");
+  return SVO_HIP_OK;
+}
+
+static void trk_finish_copy_out(const svo_hip_tracker* t, int n, double* pos_out, int32_t* iters_out, svo_hip_kf_decision* decision) {
+  if (n > 0) memcpy(pos_out, t->st_host, (size_t)n * 24);
+  if (n > 0 && iters_out) memcpy(iters_out, t->st_host + ST_O_ITERS, (size_t)n * 4);
+  memcpy(decision, t->st_host + ST_O_DECISION, sizeof(*decision));
+}
+
+int svo_hip_tracker_finish_frame(svo_hip_tracker* t, int n, const int32_t* point, int n_iter, double* pos_out, int32_t* iters_out,
+                                 double kf_select_min_dist, svo_hip_kf_decision* decision) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  const char* who = "svo_hip_tracker_finish_frame";
+  SVO_REQUIRE(ctx, decision != nullptr && kf_select_min_dist >= 0.0);          // (a NaN compares false)
+  TrkStructSel sel;
+  int rc = trk_finish_check(t, n, point, n_iter, pos_out, &sel);
+  if (rc != SVO_HIP_OK) return rc;
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no map has been set");
+  if (!t->have_last) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "the device holds no last frame");
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  const unsigned long long seq = ++t->st_seq;
+  hipLaunchKernelGGL(trk_finish_frame_kernel, dim3(1), dim3(FIN_THREADS), 0, ctx->stream, make_map(t), t->pt_pos, t->last, sel, n_iter,
+                     t->pl.overlap_kf, t->pl.counters, t->overlap_valid ? 1 : 0, kf_select_min_dist, t->st_dev, seq);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  rc = trk_finish_wait(ctx, &t, 1, who);
+  if (rc != SVO_HIP_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+  trk_finish_copy_out(t, n, pos_out, iters_out, decision);
+  // (the point table and the solver's copy of the last frame's points were updated by the kernel: nothing to gather)
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_group_finish_frames(svo_hip_tracker_group* g, const svo_hip_structure_request* req, double kf_select_min_dist,
+                                        svo_hip_kf_decision* decisions, int32_t* camera_ok) {
+  if (!g || !g->sh) return SVO_HIP_ERR_INVALID;
+  svo_hip_tracker_shared* sh = g->sh;
+  svo_hip_ctx* ctx = sh->ctx;
+  const char* who = "svo_hip_tracker_group_finish_frames";
+  const int N = sh->n_cams;
+  SVO_REQUIRE(ctx, decisions != nullptr && camera_ok != nullptr && kf_select_min_dist >= 0.0);
+  // every camera's request, before anything is enqueued or written
+  std::vector<TrkStructSel> sels((size_t)N);
+  std::vector<svo_hip_tracker*> active;
+  for (int k = 0; k < N; ++k) {
+    svo_hip_tracker* t = sh->members[(size_t)k];
+    const svo_hip_structure_request none = {0, nullptr, 0, nullptr, nullptr};
+    const svo_hip_structure_request& r = req ? req[k] : none;
+    if (!t->have_map || !t->have_last) {                                       // the camera sits out
+      SVO_REQUIRE(ctx, r.n == 0);
+      memset(&sels[(size_t)k], 0, sizeof(TrkStructSel));
+      continue;
+    }
+    const int rc = trk_finish_check(t, r.n, r.point, r.n_iter, r.pos_out, &sels[(size_t)k]);
+    if (rc != SVO_HIP_OK) return rc;
+    active.push_back(t);
+  }
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  for (int k = 0; k < N; ++k) { camera_ok[k] = 0; memset(&decisions[k], 0, sizeof(svo_hip_kf_decision)); }
+  if (active.empty()) return SVO_HIP_OK;
+  // (the previous call's kernel is through with the requests: the host waited for it)
+  for (int k = 0; k < N; ++k) {
+    svo_hip_tracker* t = sh->members[(size_t)k];
+    TrkFinishReq r;
+    memset(&r, 0, sizeof(r));
+    r.sel = sels[(size_t)k];
+    r.active = t->have_map && t->have_last ? 1 : 0;
+    if (r.active) {
+      r.n_iter = req ? req[k].n_iter : 0;
+      r.overlap_valid = t->overlap_valid ? 1 : 0;
+      r.st = t->st_dev;
+      r.seq = ++t->st_seq;
+    }
+    sh->fin_host[k] = r;
+  }
+  // a failure from here on: the stream is through with the staging areas before the call returns
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; };
+  SeedRec* recs = nullptr;
+  uint32_t* pwb_t = nullptr;
+  int n_pad = 0;
+  int rc = svo_match_scratch(ctx, N * sh->rec_stride, &recs, &pwb_t, &n_pad);      // (the records' address is part of the table)
+  if (rc == SVO_HIP_OK) rc = trk_args_table(sh, recs);
+  if (rc != SVO_HIP_OK) return fail(rc);
+  if (N == 1) {
+    svo_hip_tracker* t = sh->members[0];
+    const TrkFinishReq& r = sh->fin_host[0];
+    hipLaunchKernelGGL(trk_finish_frame_kernel, dim3(1), dim3(FIN_THREADS), 0, ctx->stream, make_map(t), t->pt_pos, t->last, r.sel, r.n_iter,
+                       t->pl.overlap_kf, t->pl.counters, r.overlap_valid, kf_select_min_dist, r.st, r.seq);
+  } else {
+    hipLaunchKernelGGL(trk_finish_frames_cams_kernel, dim3(N), dim3(FIN_THREADS), 0, ctx->stream, sh->args_dev, sh->fin_dev, kf_select_min_dist);
+  }
+  if (hipGetLastError() != hipSuccess) return fail(svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "launch failed"));
+  rc = trk_finish_wait(ctx, active.data(), (int)active.size(), who);
+  if (rc != SVO_HIP_OK) return fail(rc);
+  for (int k = 0; k < N; ++k) {
+    svo_hip_tracker* t = sh->members[(size_t)k];
+    if (!sh->fin_host[k].active) continue;
+    camera_ok[k] = 1;
+    trk_finish_copy_out(t, sels[(size_t)k].n, req ? req[k].pos_out : nullptr, req ? req[k].iters_out : nullptr, &decisions[k]);
+  }
   return SVO_HIP_OK;
 }
 

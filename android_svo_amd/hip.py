@@ -931,6 +931,23 @@ class CRelocResult(C.Structure):             # svo_hip_reloc_result
                 ("gate_n_tracked", C.c_uint64), ("gate_iters", C.c_int32 * MAX_LEVELS), ("T_f_w_gate", C.c_double * 7)]
 
 
+class CKfDecision(C.Structure):               # svo_hip_kf_decision
+    _fields_ = [("n_depths", C.c_int32), ("n_nan_depths", C.c_int32), ("depth_mean", C.c_double), ("depth_min", C.c_double),
+                ("overlap_valid", C.c_int32), ("need_new_kf", C.c_int32), ("blocking_kf", C.c_int32), ("furthest_kf", C.c_int32),
+                ("furthest_distance", C.c_double), ("pos", C.c_double * 3)]
+
+
+class CStructureRequest(C.Structure):         # svo_hip_structure_request
+    _fields_ = [("n", C.c_int32), ("point", C.POINTER(C.c_int32)), ("n_iter", C.c_int32), ("pos_out", C.POINTER(C.c_double)),
+                ("iters_out", C.POINTER(C.c_int32))]
+
+
+def _decision_dict(d: CKfDecision) -> dict:
+    return dict(n_depths=int(d.n_depths), n_nan_depths=int(d.n_nan_depths), depth_mean=float(d.depth_mean), depth_min=float(d.depth_min),
+                overlap_valid=int(d.overlap_valid), need_new_kf=int(d.need_new_kf), blocking_kf=int(d.blocking_kf),
+                furthest_kf=int(d.furthest_kf), furthest_distance=float(d.furthest_distance), pos=np.array(d.pos))
+
+
 class Tracker:
     """svo_hip_tracker: SparseImgAlign -> Reprojector::reprojectMap -> pose_optimizer on one stream, one synchronisation per
     frame, the frame's matches handed over to the next call on the device."""
@@ -976,6 +993,17 @@ class Tracker:
         self.ctx.check(self.ctx.lib.svo_hip_tracker_optimize_structure(self.h, len(pt), _ptr(pt, C.c_int32), int(n_iter), _ptr(pos, C.c_double),
                                                                        _ptr(it, C.c_int32)), "tracker_optimize_structure")
         return pos[:len(pt)], it[:len(pt)]
+
+    def finish_frame(self, points, n_iter: int = 5, kf_select_min_dist: float = 0.12):
+        """svo_hip_tracker_finish_frame: optimize_structure(points, n_iter) and, in the same launch, the keyframe decision of the
+        device's last frame (scene depth, needNewKf, Map::getFurthestKeyframe).  Returns (pos [n,3], iters [n], decision dict)."""
+        pt = np.ascontiguousarray(points, dtype=np.int32)
+        pos, it = np.zeros((max(len(pt), 1), 3)), np.zeros(max(len(pt), 1), np.int32)
+        dec = CKfDecision()
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_finish_frame(self.h, len(pt), _ptr(pt, C.c_int32), int(n_iter), _ptr(pos, C.c_double),
+                                                                 _ptr(it, C.c_int32), C.c_double(kf_select_min_dist), C.byref(dec)),
+                       "tracker_finish_frame")
+        return pos[:len(pt)], it[:len(pt)], _decision_dict(dec)
 
     def image_buffer(self) -> np.ndarray:
         """the tracker's page-locked image buffer as a (height, width) u8 view (svo_hip_tracker_image_buffer): an image written
@@ -1219,6 +1247,25 @@ class TrackerGroup:
         for t in self.cameras:
             t._tracked_n_points = t.n_points
         return [self._res[c] for c in range(self.n)]
+
+    def finish_frames(self, requests=None, kf_select_min_dist: float = 0.12) -> list:
+        """svo_hip_tracker_group_finish_frames: Tracker.finish_frame for every camera in one launch with one wait.
+        requests[c]: None / a list of point indices / (points, n_iter) for camera c (requests = None: no structure step anywhere).
+        Returns [(pos [n,3], iters [n], decision dict, or None for a camera that sat out)] per camera."""
+        req = (CStructureRequest * self.n)()
+        keep = []
+        for c in range(self.n):
+            r = None if requests is None else requests[c]
+            pts, n_iter = (r if isinstance(r, tuple) else (r, 5)) if r is not None else ([], 0)
+            pt = np.ascontiguousarray(pts, dtype=np.int32)
+            pos, it = np.zeros((max(len(pt), 1), 3)), np.zeros(max(len(pt), 1), np.int32)
+            keep.append((pt, pos, it))
+            req[c] = CStructureRequest(len(pt), _ptr(pt, C.c_int32), int(n_iter), _ptr(pos, C.c_double), _ptr(it, C.c_int32))
+        dec = (CKfDecision * self.n)()
+        ok = (C.c_int32 * self.n)()
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_group_finish_frames(self.h, None if requests is None else req, C.c_double(kf_select_min_dist),
+                                                                        dec, ok), "tracker_group_finish_frames")
+        return [(keep[c][1][:len(keep[c][0])], keep[c][2][:len(keep[c][0])], _decision_dict(dec[c]) if ok[c] else None) for c in range(self.n)]
 
     def destroy(self):
         if self.h:

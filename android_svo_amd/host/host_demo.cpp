@@ -139,6 +139,12 @@ static svo_hip_tracker_config track_config(const std::vector<double>& m, int max
 // against Map::getClosestKeyframe(last_frame_)) with FrameTracker::setDeviceRelocalisation -- keyframe choice, gate and tracking in
 // one device call.  track_reloc.bin: the result (UpdateResult), the reference keyframe (in order of creation, -1: none), how many
 // device relocalisations the bridge made, gate_n_tracked, accepted, n_close, the gate's pose.
+// Manifest field 21 (optional), kf_select_min_dist > 0 (Config::kfSelectMinDist()): every tracked frame is finished with
+// FrameTracker::finishFrame -- optimizeStructure(frame, field 18 or 20 points, 5 iterations) and the keyframe decision in one device
+// call -- and the host twins (frame_utils::getSceneDepth, needNewKf, Map::getFurthestKeyframe) decide again on the objects, which
+// hold the positions the call wrote.  track_decision.bin, 13 doubles per frame: the device's have_depth, depth_mean, depth_min,
+// overlap_valid, need_new_kf, furthest keyframe (in order of creation, -1: none), the host's six, and the device decisions so far.
+// With max_kfs the keyframe that leaves is the one the device named; the run throws if the host names another.
 static int track_demo(const std::string& dir, const std::string& out, TrackerPort& port, bool incremental = false, bool times = false,
                       int max_kfs = 0, bool full_remove = false, int kf_every = 0, bool compact = false, int new_seeds = 0, int reloc_at = -1) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
@@ -219,6 +225,9 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
   std::vector<double> poses, stats, overlap, uploads, removed, compactions;
   size_t room_needed = 0;
   const int keyframe_at = m.size() > 19 ? (int)m[19] : -1;
+  const double kf_select_min_dist = m.size() > 21 ? m[21] : 0.0;
+  const bool decide = kf_select_min_dist > 0.0;
+  std::vector<double> decisions;
   for (int k = 0; k < n_frames; ++k) {
     std::vector<std::vector<uint8_t>> pyr;
     pyr.push_back(read_bin<uint8_t>(dir + "/trk_frame_" + std::to_string(k) + ".bin"));
@@ -260,7 +269,21 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
         for (int j = 0; j < n_kf; ++j) if (kfs[j] == ov.first) idx = j;
         overlap.push_back((double)idx); overlap.push_back((double)ov.second);
       }
-    if (k == 0 && m.size() > 18 && m[18] > 0) {
+    FrameTracker::Decision dec = FrameTracker::Decision();
+    if (decide) {
+      // processFrame :242-260 and :305 in one device call, then the same decision by the host twins on the objects as the call left them
+      auto created = [&](const FramePtr& f) { double j = -1.0; for (size_t i = 0; i < kfs.size(); ++i) if (kfs[i] == f) j = (double)i; return j; };
+      if (!tracker.finishFrame(cur, map, m.size() > 18 && m[18] > 0 ? (size_t)m[18] : (size_t)20, 5, kf_select_min_dist, dec))
+        throw std::runtime_error("svo::FrameTracker::finishFrame failed at frame " + std::to_string(k));
+      double depth_mean = std::numeric_limits<double>::quiet_NaN(), depth_min = 0.0;
+      const bool have = frame_utils::getSceneDepth(*cur, depth_mean, depth_min);
+      const bool need = needNewKf(*cur, overlap_kfs, depth_mean, kf_select_min_dist);
+      const FramePtr far = map.getFurthestKeyframe(cur->pos());
+      decisions.insert(decisions.end(), {dec.have_depth ? 1.0 : 0.0, dec.depth_mean, dec.depth_min, dec.overlap_valid ? 1.0 : 0.0, dec.need_new_kf ? 1.0 : 0.0,
+                                         created(dec.furthest), have ? 1.0 : 0.0, depth_mean, depth_min, 1.0, need ? 1.0 : 0.0, created(far),
+                                         (double)tracker.deviceDecisions()});
+    }
+    if (!decide && k == 0 && m.size() > 18 && m[18] > 0) {
       // FrameHandlerBase::optimizeStructure(new_frame, 20, 5) as processFrame calls it behind the pose refinement (:242-244)
       std::vector<const Point*> had;
       for (const Feature* ftr : cur->fts_) if (ftr->point) had.push_back(ftr->point);
@@ -312,6 +335,10 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
       FramePtr furthest;
       if (max_kfs > 2 && (int)map.size() >= max_kfs) {
         furthest = map.getFurthestKeyframe(cur->pos());
+        if (decide) {                                                            // the device named it; the objects have to agree
+          if (dec.furthest != furthest) throw std::runtime_error("the device and Map::getFurthestKeyframe name different keyframes at frame " + std::to_string(k));
+          furthest = dec.furthest;
+        }
         if (!furthest) throw std::runtime_error("no furthest keyframe at frame " + std::to_string(k) + ": the frame's pose is not a number, tracking was lost");
       }
       map.addKeyframe(cur);
@@ -360,6 +387,7 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
     write_bin(out + "/track_map_size.bin", std::vector<double>{(double)map.size(), n_ftr, (double)seen.size(), (double)map.point_candidates_.candidates_.size()});
   }
   write_bin(out + "/track_overlap_first.bin", overlap);
+  if (decide) write_bin(out + "/track_decision.bin", decisions);
   if (times) write_bin(out + "/times_track.bin", track_us);
   if (port.lone) std::printf("svo_host_demo track OK\n");
   return 0;

@@ -20,12 +20,14 @@
 #ifndef SVO_HOST_H_
 #define SVO_HOST_H_
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <list>
 #include <map>
 #include <memory>
@@ -356,6 +358,44 @@ struct Map {
     return furthest;
   }
 };
+
+namespace frame_utils {
+/// S/frame.cpp:200-221: the depths (T_f_w * pos_).z() of the features that have a point; their median as vk::getMedian takes it
+/// (I/math_utils.h:125-131: std::nth_element at size / 2) and their minimum by fmin from the largest double.  false, with
+/// depth_mean untouched, for a frame without such a feature.  The host twin of svo_hip_kf_decision's depth pair.
+inline bool getSceneDepth(const Frame& frame, double& depth_mean, double& depth_min) {
+  std::vector<double> depth_vec;
+  depth_vec.reserve(frame.fts_.size());
+  depth_min = std::numeric_limits<double>::max();
+  for (const Feature* ftr : frame.fts_) {
+    if (ftr->point == nullptr) continue;
+    const double z = (frame.T_f_w_ * ftr->point->pos_)[2];
+    depth_vec.push_back(z);
+    depth_min = std::fmin(z, depth_min);
+  }
+  if (depth_vec.empty()) return false;
+  std::vector<double>::iterator it = depth_vec.begin() + depth_vec.size() / 2;
+  std::nth_element(depth_vec.begin(), it, depth_vec.end());
+  depth_mean = *it;
+  return true;
+}
+}  // namespace frame_utils
+
+/// FrameHandlerMono::needNewKf (S/frame_handler_mono.cpp:391-403) as a free function: no new keyframe while one of the overlap
+/// keyframes lies within min_dist (Config::kfSelectMinDist()) scene depths of the frame, the box 1 : 0.8 : 1.3 in the frame's
+/// axes.  *blocking (may be NULL): the first keyframe that says so.
+inline bool needNewKf(const Frame& frame, const std::vector<std::pair<FramePtr, size_t>>& overlap_kfs, double scene_depth_mean, double min_dist,
+                      FramePtr* blocking = nullptr) {
+  for (const std::pair<FramePtr, size_t>& kf : overlap_kfs) {
+    const Vector3d relpos = frame.T_f_w_ * kf.first->pos();
+    if (std::fabs(relpos[0]) / scene_depth_mean < min_dist && std::fabs(relpos[1]) / scene_depth_mean < min_dist * 0.8 &&
+        std::fabs(relpos[2]) / scene_depth_mean < min_dist * 1.3) {
+      if (blocking) *blocking = kf.first;
+      return false;
+    }
+  }
+  return true;
+}
 
 /// Host policy of hip_bridge::FrameTrackerT on this file's data model (the drop-in instantiates the same template on the
 /// reference's types: include/svo_dropin/frame_tracker_hip.h)

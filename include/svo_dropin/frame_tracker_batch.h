@@ -311,6 +311,68 @@ class FrameTrackerT {
     return true;
   }
 
+  /// What processFrame decides behind the structure step (frame_handler_mono.cpp:258-260, :305), as the device found it.
+  struct Decision {
+    bool have_depth;          // frame_utils::getSceneDepth returned true: the frame has point observations and every depth is a number
+    double depth_mean, depth_min;
+    bool overlap_valid;       // need_new_kf is an answer (the device's overlap keyframes are the tracked frame's)
+    bool need_new_kf;         // needNewKf(depth_mean); false without an answer
+    FramePtr furthest;        // Map::getFurthestKeyframe(frame->pos()), NULL: none
+    svo_hip_kf_decision raw;  // the device's record
+  };
+  /// optimiseStructure(frame, map, max_n_pts, max_iter) and the keyframe decision of `frame` in ONE device call
+  /// (svo_hip_tracker_finish_frame): the points are selected as optimiseStructure selects them, their positions and
+  /// Point::last_structure_optim_ are written as it writes them, and `decision` holds frame_utils::getSceneDepth, needNewKf
+  /// (kf_select_min_dist = Config::kfSelectMinDist()) and Map::getFurthestKeyframe for the frame -- the keyframe index
+  /// translated through this tracker's own keyframe list.  Precondition: `frame` is the frame the device tracked last.
+  /// false, with the host's objects untouched: no tracker, the device's last frame is not the tracked one (the map had to be
+  /// flattened again, a last frame is owed), a selection above the 64 points of one call, or the device refused.  The caller
+  /// then runs the host path (optimiseStructure, frame_utils::getSceneDepth, needNewKf, Map::getFurthestKeyframe).
+  /// (A member of a class template: only code that calls it refers to svo_hip_tracker_finish_frame.)
+  bool finishFrame(const FramePtr& frame, Map& map, size_t max_n_pts, int max_iter, double kf_select_min_dist, Decision& decision) {
+    if (!trk_) return false;
+    std::deque<Point*> pts;
+    bool unknown = false;
+    for (typename Host::FeatureList::iterator it = frame->fts_.begin(); it != frame->fts_.end(); ++it)
+      if ((*it)->point != NULL) {
+        pts.push_back((*it)->point);
+        if (index_of_point_.find((*it)->point) == index_of_point_.end()) unknown = true;
+      }
+    if ((map_dirty_ || unknown) && !uploadMap(map)) return false;
+    if (!have_last_) return false;
+    max_n_pts = std::min(max_n_pts, pts.size());
+    if (max_n_pts > 0) std::nth_element(pts.begin(), pts.begin() + max_n_pts, pts.end(), LastOptimLess());
+    std::vector<int32_t> idx;
+    std::vector<Point*> chosen;
+    for (size_t i = 0; i < max_n_pts; ++i) {
+      typename std::map<const Point*, int>::const_iterator pi = index_of_point_.find(pts[i]);
+      if (pi == index_of_point_.end()) continue;
+      bool twice = false;
+      for (size_t j = 0; j < chosen.size(); ++j) twice = twice || chosen[j] == pts[i];
+      if (twice) continue;
+      idx.push_back(pi->second); chosen.push_back(pts[i]);
+    }
+    if (idx.size() > 64) return false;
+    std::vector<double> pos(idx.size() * 3 + 3);
+    svo_hip_kf_decision d;
+    if (svo_hip_tracker_finish_frame(trk_, (int)idx.size(), idx.data(), max_iter, pos.data(), NULL, kf_select_min_dist, &d) != SVO_HIP_OK) return false;
+    if (d.furthest_kf >= (int)keyframes_.size()) return false;     // (cannot happen: both sides count the same keyframes)
+    for (size_t i = 0; i < chosen.size(); ++i) {
+      chosen[i]->pos_[0] = pos[3 * i]; chosen[i]->pos_[1] = pos[3 * i + 1]; chosen[i]->pos_[2] = pos[3 * i + 2];
+    }
+    for (size_t i = 0; i < max_n_pts; ++i) pts[i]->last_structure_optim_ = frame->id_;          // :208
+    decision.raw = d;
+    decision.have_depth = d.n_depths > 0 && d.n_nan_depths == 0;
+    decision.depth_mean = d.depth_mean; decision.depth_min = d.depth_min;
+    decision.overlap_valid = d.overlap_valid != 0 && d.need_new_kf >= 0;
+    decision.need_new_kf = decision.overlap_valid && d.need_new_kf == 1;
+    decision.furthest = d.furthest_kf >= 0 ? keyframes_[(size_t)d.furthest_kf] : FramePtr();
+    ++n_decisions_;
+    return true;
+  }
+  /// how often finishFrame went through the device call (diagnostic)
+  size_t deviceDecisions() const { return n_decisions_; }
+
   /// new_frame_->setKeyframe(); map_.addKeyframe(new_frame_) (:284-330): keep the frame's pyramid on the device as a keyframe
   bool lastFrameBecameKeyframe(const Frame& frame) {
     const int slot = freeSlot();
@@ -616,6 +678,7 @@ class FrameTrackerT {
                          int32_t*, int32_t*, uint8_t*, double*, int32_t*, int32_t*, int32_t*);
   RelocFn reloc_fn_ = NULL;                                  // setDeviceRelocalisation: svo_hip_tracker_relocalize, or NULL
   size_t n_relocs_ = 0;
+  size_t n_decisions_ = 0;                                   // finishFrame
   svo_hip_reloc_result last_reloc_ = svo_hip_reloc_result();
   std::map<int, int> index_of_frame_;                        // Frame::id_ -> keyframe index of the device tables
   size_t n_uploads_ = 0;

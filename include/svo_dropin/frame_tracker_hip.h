@@ -74,6 +74,14 @@ class FrameTracker : public FrameTrackerT<SvoTrackerHost> {
   bool newKeyframe(const FramePtr& frame, Map& map) { return lastFrameBecameKeyframe(frame, map); }
   /// processFrame :307 with setIncrementalMap(true): map_.safeDeleteFrame(frame) has run, the device removes the keyframe in place
   bool keyframeLeft(const FramePtr& frame, Map& map) { return keyframeRemoved(frame, map); }
+  /// processFrame :242-260 and :305 in one device call with svo::Config's values: optimizeStructure(new_frame_,
+  /// structureOptimMaxPts, structureOptimNumIter), frame_utils::getSceneDepth, needNewKf and map_.getFurthestKeyframe.  false:
+  /// run those on the host, nothing was changed.  (A template, so that only code that calls it refers to the device entry point.)
+  template <class DecisionT>
+  bool finishFrame(const FramePtr& frame, Map& map, DecisionT& decision) {
+    return FrameTrackerT<SvoTrackerHost>::finishFrame(frame, map, Config::structureOptimMaxPts(), (int)Config::structureOptimNumIter(),
+                                                      Config::kfSelectMinDist(), decision);
+  }
   /// a bounded map (Config::maxNKfs() > 0) on one upload for good: setIncrementalMap with setPointCompaction, so that the rows of
   /// deleted points are given back in place when a table is full
   void keepMapOnDevice(bool on) { setIncrementalMap(on); setPointCompaction(on); }

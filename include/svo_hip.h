@@ -632,8 +632,9 @@ int svo_hip_point_optimize_batch(svo_hip_ctx* ctx, int n_points, int n_iter, dou
  * feature chooses its key features again, Frame::removeKeyPoint): the device tables follow -- the point is unlinked there and
  * the affected keyframes re-select before the next frame with the reference's rule -- and the result says map_changed so that
  * the host applies the same deletions to its own objects; a new upload of the map is NOT needed for that.
- * Host code keeps what it keeps in the reference: keyframe selection, Map / Point / Feature objects, optimizeStructure
- * (svo_hip_point_optimize_batch + svo_hip_tracker_update_point_positions).  Relocalisation is a device job like everything
+ * Host code keeps the Map / Point / Feature objects and acts on the decisions.  The structure step, the scene depth, needNewKf
+ * and Map::getFurthestKeyframe -- keyframe selection -- are one device call (svo_hip_tracker_finish_frame below), so the host
+ * needs no poses or point positions of its own between two keyframes.  Relocalisation is a device job like everything
  * else between two keyframes (svo_hip_tracker_relocalize below); svo_hip_tracker_set_last_frame remains the way in for a last
  * frame the device's map does not hold (after initialisation). */
 typedef struct svo_hip_tracker svo_hip_tracker;
@@ -949,6 +950,63 @@ int svo_hip_tracker_relocalize(svo_hip_tracker* trk, const uint8_t* level0, int 
                                int min_tracked, svo_hip_reloc_result* reloc, svo_hip_track_result* result, double* feat_px,
                                double* feat_f, int32_t* feat_level, int32_t* feat_point, uint8_t* feat_edgelet, double* feat_grad,
                                int32_t* pt_type, int32_t* pt_n_failed, int32_t* pt_n_succeeded);
+/* ---- the structure step and the keyframe decision in one device call: what FrameHandlerMono::processFrame does behind the pose
+ * refinement (frame_handler_mono.cpp:242-260, :305) from what the device holds already -- the last frame's pose and point
+ * indices, the overlap keyframes the reprojector chose, the point positions and the keyframe poses.
+ *
+ * svo_hip_tracker_finish_frame, in ONE launch of one workgroup with one wait (the page-locked flag of
+ * svo_hip_tracker_optimize_structure, the stream's synchronisation as the fall-back):
+ *   1. optimizeStructure: exactly svo_hip_tracker_optimize_structure(n, point, n_iter, pos_out, iters_out) -- same checks, same
+ *      outputs, same bits (one device function serves both kernels).  n == 0 skips the step.
+ *   2. behind a barrier, on the positions just written:
+ *      - frame_utils::getSceneDepth (frame.cpp:200-221): z = (T_f_w * pos_).z() of every feature of the device's last frame that
+ *        has a point.  n_depths counts the depths that are numbers, n_nan_depths the NaNs (excluded).  depth_mean is
+ *        vk::getMedian (math_utils.h:125-131): the element of rank floor(n_depths / 2) in ascending order, the exact order
+ *        statistic (a radix select over order-preserving 64-bit keys, no sort, no float atomics); depth_min is fmin over the
+ *        depths from DBL_MAX.  With n_nan_depths > 0 or without any depth depth_mean is NaN (the reference leaves it
+ *        undefined in both cases: behaviour defined here).
+ *      - needNewKf(depth_mean) (:391-403) over the overlap keyframes of the last tracked frame in overlap_kfs_ order:
+ *        rel = T_f_w * kf->pos(); false at the first keyframe with fabs(rel.x)/depth_mean < d && fabs(rel.y)/depth_mean < d*0.8
+ *        && fabs(rel.z)/depth_mean < d*1.3 (d = kf_select_min_dist = Config::kfSelectMinDist(), an argument because the
+ *        configuration's size is fixed); blocking_kf names that keyframe.  A NaN depth_mean compares false: need_new_kf = 1.
+ *      - Map::getFurthestKeyframe(frame->pos()) (map.cpp:156-169): dist = (kf->pos() - pos).norm(), squares summed in x, y, z
+ *        order; dist > maxdist from 0.0, so the lowest index wins a tie, a NaN never wins and furthest_kf = -1 when every
+ *        keyframe sits at the frame's position.
+ * overlap_valid: the overlap keyframes are those of the last tracked frame and still name keyframes of the map.
+ * svo_hip_tracker_track, svo_hip_tracker_group_track and an accepted svo_hip_tracker_relocalize set it;
+ * svo_hip_tracker_set_map, _promote_last_frame, _remove_keyframe, _set_last_frame, _last_frame_from_keyframe and a refused
+ * relocalisation gate clear it (each renumbers keyframes or replaces the frame); _optimize_structure,
+ * _update_point_positions, _add_candidates and _compact_points keep it.  With the flag clear the call succeeds all the same:
+ * depths and the furthest keyframe are valid for any last frame (processSecondFrame after svo_hip_tracker_set_last_frame),
+ * need_new_kf = -1 and blocking_kf = -1.
+ * Apart from the structure step's positions the call only reads: it applies no owed re-selection of key points (it reads no
+ * key points) and leaves the page-locked result block of the last tracked frame alone.  Takes a lone tracker's handle or a
+ * handle from svo_hip_tracker_group_camera.  Refused before anything is enqueued, nothing changed: SVO_HIP_ERR_INVALID for
+ * what svo_hip_tracker_optimize_structure refuses, for decision == NULL and for a kf_select_min_dist that is NaN or negative;
+ * SVO_HIP_ERR_STATE without a map or without a last frame. */
+typedef struct {
+  int32_t n_depths;          /* features of the device's last frame that have a point and whose depth is a number */
+  int32_t n_nan_depths;      /* ... whose depth is NaN */
+  double  depth_mean;        /* vk::getMedian: the element of rank floor(n_depths/2) in ascending order (the UPPER median for even n) */
+  double  depth_min;         /* fmin over the depths, starting from DBL_MAX (NaNs skipped, as fmin skips them) */
+  int32_t overlap_valid;     /* 1: the overlap keyframes of the last tracked frame still name keyframes of the map */
+  int32_t need_new_kf;       /* needNewKf(depth_mean): 1 / 0; -1 when !overlap_valid */
+  int32_t blocking_kf;       /* keyframe index of the FIRST overlap keyframe, in overlap_kfs_ order, that makes it return false; -1 */
+  int32_t furthest_kf;       /* Map::getFurthestKeyframe(last frame's pos()): keyframe index, -1: none */
+  double  furthest_distance; /* its distance, 0.0 without one */
+  double  pos[3];            /* Frame::pos() of the last frame */
+} svo_hip_kf_decision;
+int svo_hip_tracker_finish_frame(svo_hip_tracker* trk, int n, const int32_t* point, int n_iter, double* pos_out, int32_t* iters_out,
+                                 double kf_select_min_dist, svo_hip_kf_decision* decision);
+/* The same for every camera of a group in ONE launch (workgroup c = camera c) with ONE wait.  req[c]: camera c's structure
+ * request (req == NULL: n = 0 for all).  A camera without a map or without a last frame sits out: camera_ok[c] = 0, its
+ * decision is zero-filled and its request has to be n == 0; the others get camera_ok[c] = 1 and, bit for bit, the positions and
+ * the decision svo_hip_tracker_finish_frame gives on their handle.  Every request is checked before anything is enqueued: one
+ * refused request (SVO_HIP_ERR_INVALID, as above) refuses the call for every camera and changes nothing. */
+typedef struct { int32_t n; const int32_t* point; int32_t n_iter; double* pos_out; int32_t* iters_out; } svo_hip_structure_request;
+int svo_hip_tracker_group_finish_frames(svo_hip_tracker_group* group, const svo_hip_structure_request* req /*[n_cameras], may be NULL: n = 0 for all*/,
+                                        double kf_select_min_dist, svo_hip_kf_decision* decisions /*[n_cameras]*/, int32_t* camera_ok /*[n_cameras]*/);
+
 /* diagnostics and parity tests: the sizes of the tables the device holds, and the tables themselves in svo_hip_tracker_map's
  * layout (the key points with the owed re-selections applied).  The caller's buffers hold at least the sizes
  * svo_hip_tracker_map_sizes reports (kf_ftr_offset n_kf + 1, pt_obs_offset n_points + 1); a NULL pointer skips its table.
