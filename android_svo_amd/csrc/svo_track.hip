@@ -33,1474 +33,13 @@
 #include <utility>
 #include <vector>
 
-#include "svo_internal.h"
-#include "svo_match_device.h"
-#include "svo_point_refine.h"
-
-using namespace svo_dev;
+#include "svo_track_types.h"
+#include "svo_track_chain.h"
+#include "svo_track_map_edit.h"
+#include "svo_track_frame_end.h"
+#include "svo_track_reloc.h"
 
 namespace {
-
-constexpr int TRK_THREADS = 1024;
-constexpr int TRK_MAX_SEL = 16;            // >= Reprojector::Options::max_n_kfs
-constexpr int TRK_MAX_STRUCT = 64;         // points per structure-optimisation call (Config::structureOptimMaxPts() = 20)
-constexpr int TRK_LDS_KF = 256;            // keyframes of the map (svo_hip_tracker_config::max_keyframes <= this): per-keyframe scratch in LDS
-constexpr int TRK_LDS_ITEMS = 2048;        // a frame with at most this many candidates keeps their per-cell sort keys in LDS
-constexpr int TRK_LDS_CELLS = 2048;        // a grid with at most this many cells keeps the cell counters in LDS
-constexpr int TYPE_DELETED = 0, TYPE_CANDIDATE = 1, TYPE_UNKNOWN = 2, TYPE_GOOD = 3;   // Point::PointType (I/point.h:33-38)
-
-// the map as index tables (device pointers)
-struct TrkMap {
-  int n_kf, n_points, n_candidates;
-  const double* T_kf_w;          // [n_kf][7]
-  const int* kf_slot;            // [n_kf] pyramid slot
-  const int* kf_key_point;       // [n_kf][5]
-  const int* kf_ftr_offset;      // [n_kf + 1]
-  const int* kf_ftr_point;
-  const double* pt_pos;          // [n_points][3]
-  int* pt_type;
-  int* pt_n_failed;
-  int* pt_n_succeeded;
-  uint8_t* pt_unlinked;
-  const int* pt_obs_offset;      // [n_points + 1]
-  const int* obs_kf;
-  const double* obs_px;
-  const double* obs_f;
-  const int* obs_level;
-  const uint8_t* obs_edgelet;
-  const double* obs_grad;
-  const int* cand_point;
-};
-
-// The tables whose entries move when the map is rebuilt in place (a keyframe joins or leaves, the points are renumbered): the
-// observation CSR, the keyframes' feature rows and the candidate list.  A tracker holds two such sets, each at the capacities of
-// its configuration; a rebuild reads the current one (through TrkMap) and writes the other, which is the current one afterwards.
-struct TrkTables {
-  int* pt_obs_offset;            // [max_points + 1]
-  int* obs_kf; double* obs_px; double* obs_f; int* obs_level; uint8_t* obs_edgelet; double* obs_grad;   // [max_obs] rows, as in TrkMap
-  int* kf_ftr_offset;            // [max_keyframes + 1]
-  int* kf_ftr_point;             // [max_kf_features]
-  int* cand_point;               // [max_candidates]
-};
-
-// scratch of the rebuild kernels (one workgroup each), and what they report to the host
-struct TrkScratch {
-  int* cand_seed;                // [max_candidates] trk_promote_kernel: -2 stays, -1 promoted without a seed observation, else its seed keyframe
-  int* cand_scan;                // [max_candidates + 1]
-  int* ftr_scan;                 // [max_kf_features + 1]
-  int* out;                      // [8]: 0 the call's own count, 1 n_ftr, 2 n_obs, 3 n_candidates afterwards (trk_rebuild_end), 4 the call's own
-};
-
-// scratch and outputs of the planning kernel; cap = capacity of the candidate arrays
-struct TrkPlan {
-  int cap, n_cells, grid_cols, grid_size, max_n_kfs;
-  int* first_seq;                // [n_points]
-  int* item_point;               // [cap] kept items in arrival order
-  double* item_px;               // [cap][2]
-  int* item_cell;                // [cap]
-  unsigned long long* item_key;  // [cap]
-  int* seg;                      // [cap]
-  unsigned long long* seg_key;   // [cap] item_key in segment order (frames beyond TRK_LDS_ITEMS candidates)
-  int* cell_count;               // [n_cells + 1]
-  int* cell_fill;                // [n_cells]
-  // outputs (the candidates of every cell in trial order)
-  int* counters;                 // [8]: 0 n_cand, 1 overflow, 2 map_changed, 3 n_overlap, 4 n_features, 5 n_pose_opt, 6.. n_trials (64 bit)
-  int* cell_offset;              // [n_cells + 1]
-  int* overlap_kf;               // [TRK_MAX_SEL]
-  int* overlap_count;            // [TRK_MAX_SEL]
-  int* cand_point;               // [cap]
-  int* cand_obs;                 // [cap] (-1: Point::getCloseViewObs failed)
-  int* cand_level_ref;           // [cap] pyramid level of the reference feature (read by the warp stage)
-  uint8_t* cand_deleted;         // [cap]
-};
-
-// the new frame's features (what Reprojector::reprojectCell adds to frame->fts_, in creation order) + pose-refinement inputs
-struct TrkFeat {
-  int cap;
-  double* px;        // [cap][2]
-  double* f;         // [cap][3]
-  double* pos;       // [cap][3]
-  int* level;        // [cap]
-  int* point;        // [cap]
-  uint8_t* edgelet;  // [cap]
-  double* grad;      // [cap][2]
-  uint8_t* has_point;   // [cap] in/out of the pose refinement
-};
-
-// the last frame (reference of the next SparseImgAlign)
-struct TrkLast {
-  int* n;            // [1]
-  double* T_f_w;     // [7]
-  double* px;        // [cap][2]
-  double* f;         // [cap][3]
-  int* point;        // [cap]
-  // slot 0 of the SparseImgAlign solver: the hand-over kernel writes the next solve's inputs there directly
-  FrameConst* sia_fc;
-  double *sia_px, *sia_f, *sia_pos;
-  uint8_t* sia_has_point;
-  int sia_max_n;
-};
-
-// Frame::isVisible (S/frame.cpp:162-172)
-SVO_DEV bool frame_is_visible(const Cam& cam, const double* T_f_w, const double* xyz_w) {
-  double xyz_f[3], px[2];
-  se3_act(T_f_w, xyz_w, xyz_f);
-  if (xyz_f[2] < 0.0) return false;
-  world2cam(cam, xyz_f, px);
-  return px[0] >= 0.0 && px[1] >= 0.0 && px[0] < cam.width && px[1] < cam.height;
-}
-
-// v.normalize() of Eigen 3.4: divide by the norm when the squared norm is positive
-SVO_DEV void normalize3(double* v) {
-  const double n2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-  if (n2 > 0.0) { const double nn = sqrt(n2); v[0] = v[0] / nn; v[1] = v[1] / nn; v[2] = v[2] / nn; }
-}
-
-// Point::getCloseViewObs (S/point.cpp:101-125): the observation whose viewing direction is closest to the frame's (first
-// maximum of the cosine above zero, else the first observation); false when the angle exceeds 60 degrees
-SVO_DEV bool close_view_obs(const TrkMap& m, int p, const double* framepos, const double (*kf_pos)[3], int* obs_out) {
-  const double* pos = m.pt_pos + 3 * (size_t)p;
-  double od[3] = {framepos[0] - pos[0], framepos[1] - pos[1], framepos[2] - pos[2]};
-  normalize3(od);
-  const int o0 = m.pt_obs_offset[p], o1 = m.pt_obs_offset[p + 1];
-  int min_it = o0;
-  double min_cos_angle = 0;
-  for (int ob = o0; ob < o1; ob += 4) {                                      // the keyframe indices of four observations at once
-    int kf[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) kf[e] = ob + e < o1 ? m.obs_kf[ob + e] : -1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (kf[e] < 0) continue;
-      double d[3] = {kf_pos[kf[e]][0] - pos[0], kf_pos[kf[e]][1] - pos[1], kf_pos[kf[e]][2] - pos[2]};   // (*it)->frame->pos() - pos_
-      normalize3(d);
-      const double cos_angle = od[0] * d[0] + od[1] * d[1] + od[2] * d[2];
-      if (cos_angle > min_cos_angle) { min_cos_angle = cos_angle; min_it = ob + e; }
-    }
-  }
-  *obs_out = min_it;
-  return !(min_cos_angle < 0.5);
-}
-
-// exclusive scan of v[0..n) in place by one workgroup, total -> v[n]; s_part: blockDim.x ints of LDS (64 used).
-// Thread t owns a contiguous chunk; the thread sums are scanned inside each wave with lane shifts and across the waves
-// through LDS: two barriers (a log-step scan over all 1024 threads took twenty).
-SVO_DEV void block_exclusive_scan(int* v, int n, int* s_part) {
-  const int t = threadIdx.x, nt = blockDim.x;
-  const int lane = t & 63, wave = t >> 6, n_waves = nt >> 6;
-  const int chunk = (n + nt - 1) / nt;
-  const int lo = min(n, t * chunk), hi = min(n, lo + chunk);
-  int sum = 0;
-  for (int i = lo; i < hi; ++i) sum += v[i];
-  int incl = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += up;
-  }
-  if (lane == 63) s_part[wave] = incl;
-  __syncthreads();
-  int before = 0;
-  for (int w = 0; w < wave; ++w) before += s_part[w];
-  int run = before + incl - sum;                          // exclusive prefix of this thread's chunk
-  for (int i = lo; i < hi; ++i) { const int c = v[i]; v[i] = run; run += c; }
-  if (t == nt - 1) v[n] = before + incl;
-  __syncthreads();
-  (void)n_waves;
-}
-
-// ordered compaction by one workgroup: the elements i of [0, n) with keep(i) get the ranks 0, 1, ... in ascending i, and
-// put(rank, i) is called once for each of them, by the thread that owns i.  scan: n + 1 ints of scratch; scan[n] = how many
-// were kept.  keep is evaluated twice, before and after the scan.  Block-uniform call with three barriers inside (one behind
-// the flags, two in the scan; the last one is behind scan[n], not behind the calls of put).
-template <typename Keep, typename Put>
-SVO_DEV void block_compact(int n, int* scan, int* s_part, Keep keep, Put put) {
-  const int t = threadIdx.x, nt = blockDim.x;
-  for (int i = t; i < n; i += nt) scan[i] = keep(i) ? 1 : 0;
-  __syncthreads();
-  block_exclusive_scan(scan, n, s_part);
-  for (int i = t; i < n; i += nt)
-    if (keep(i)) put(scan[i], i);
-}
-
-// ---- Reprojector::reprojectMap up to the cell loop (S/reprojector.cpp:72-146) + the per-candidate choice of the reference
-// feature (Point::getCloseViewObs, the first statement of Matcher::findMatchDirect).  One workgroup.
-SVO_DEV void trk_plan_body(const TrkMap& m, const TrkPlan& pl, MdFrame mf, const double* __restrict__ T_slot_w,
-                           SeedRec* __restrict__ recs, const FrameState* __restrict__ sia_state) {
-  const Cam cam = mf.cam;
-  __shared__ int s_part[TRK_THREADS];
-  __shared__ int s_sel[TRK_MAX_SEL], s_seq_base[TRK_MAX_SEL + 1], s_ftr_off[TRK_MAX_SEL], s_ftr_cnt[TRK_MAX_SEL];
-  __shared__ int s_n_close, s_n_sel, s_n_kept, s_overflow, s_changed;
-  __shared__ int s_overlap[TRK_MAX_SEL];
-  __shared__ double s_T[7], s_framepos[3];
-  // per-keyframe scratch, and -- for frames and grids that fit (block-uniform choice) -- the cell counters and the sort keys
-  // in segment order: what one phase writes and the next one reads costs an LDS access instead of a trip to L2
-  __shared__ int s_kf_close[TRK_LDS_KF];
-  __shared__ double s_kf_dist[TRK_LDS_KF], s_kf_pos[TRK_LDS_KF][3];
-  __shared__ int s_cell_count[TRK_LDS_CELLS + 1], s_cell_fill[TRK_LDS_CELLS];
-  __shared__ unsigned long long s_seg_key[TRK_LDS_ITEMS];
-  const int t = threadIdx.x, nt = blockDim.x;
-  int* const cell_count = pl.n_cells <= TRK_LDS_CELLS ? s_cell_count : pl.cell_count;
-  int* const cell_fill = pl.n_cells <= TRK_LDS_CELLS ? s_cell_fill : pl.cell_fill;
-  if (t < 7) s_T[t] = sia_state->T_cur_w[t];
-  if (t == 0) { s_n_close = 0; s_n_kept = 0; s_overflow = 0; s_changed = 0; }
-  if (t < TRK_MAX_SEL) { s_sel[t] = -1; s_overlap[t] = 0; }
-  __syncthreads();
-  double T[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) { T[k] = s_T[k]; mf.T_cur_w[k] = s_T[k]; }
-  if (t == 0) {
-    double Tinv[7];
-    se3_inverse(T, Tinv);                                                  // cur_frame.pos()
-    s_framepos[0] = Tinv[0]; s_framepos[1] = Tinv[1]; s_framepos[2] = Tinv[2];
-  }
-  // ---- Map::getCloseKeyframes (S/map.cpp:109-131): keyframes one of whose key points is visible in the frame
-  for (int k = t; k < m.n_kf; k += nt) {
-    int kp[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) kp[j] = m.kf_key_point[5 * k + j];
-    bool close = false;
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-      if (!close && kp[j] >= 0) close = frame_is_visible(cam, T, m.pt_pos + 3 * (size_t)kp[j]);
-    const double* tk = m.T_kf_w + 7 * (size_t)k;
-    double Tk[7], Tinv[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) Tk[i] = tk[i];
-    const double dx = T[0] - Tk[0], dy = T[1] - Tk[1], dz = T[2] - Tk[2];
-    s_kf_close[k] = close ? 1 : 0;
-    s_kf_dist[k] = sqrt(dx * dx + dy * dy + dz * dz);                      // (translation_vec difference).norm()
-    se3_inverse(Tk, Tinv);                                                 // Frame::pos() of the keyframe (Point::getCloseViewObs)
-    s_kf_pos[k][0] = Tinv[0]; s_kf_pos[k][1] = Tinv[1]; s_kf_pos[k][2] = Tinv[2];
-    if (close) atomicAdd(&s_n_close, 1);
-  }
-  for (int p = t; p < m.n_points; p += nt) pl.first_seq[p] = INT_MAX;
-  for (int c = t; c <= pl.n_cells; c += nt) cell_count[c] = 0;
-  for (int c = t; c < pl.n_cells; c += nt) cell_fill[c] = 0;
-  __syncthreads();
-  // ---- close_kfs.sort by distance (stable: std::list::sort), the first max_n_kfs of them (:82-88)
-  for (int k = t; k < m.n_kf; k += nt) {
-    if (!s_kf_close[k]) continue;
-    const double dk = s_kf_dist[k];
-    int rank = 0;
-    for (int j = 0; j < m.n_kf; ++j)
-      if (s_kf_close[j] && (s_kf_dist[j] < dk || (!(dk < s_kf_dist[j]) && j < k))) ++rank;
-    if (rank < pl.max_n_kfs) s_sel[rank] = k;
-  }
-  __syncthreads();
-  if (t < TRK_MAX_SEL) {                                                    // the selected keyframes' feature ranges, all at once
-    const int n_sel = s_n_close < pl.max_n_kfs ? s_n_close : pl.max_n_kfs;
-    if (t < n_sel) {
-      const int off = m.kf_ftr_offset[s_sel[t]];
-      s_ftr_off[t] = off;
-      s_ftr_cnt[t] = m.kf_ftr_offset[s_sel[t] + 1] - off;
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    const int n_sel = s_n_close < pl.max_n_kfs ? s_n_close : pl.max_n_kfs;
-    s_n_sel = n_sel;
-    int base = 0;
-    for (int r = 0; r < n_sel; ++r) { s_seq_base[r] = base; base += s_ftr_cnt[r]; }
-    s_seq_base[n_sel] = base;
-  }
-  __syncthreads();
-  const int n_sel = s_n_sel;
-  const int m_kf = s_seq_base[n_sel];
-  const int m_all = m_kf + m.n_candidates;
-  // ---- a point is projected once: the first keyframe feature that refers to it (last_projected_kf_id_, :103-106)
-  for (int q = t; q < m_kf; q += nt) {
-    int r = 0;
-    while (r + 1 < n_sel && q >= s_seq_base[r + 1]) ++r;
-    const int p = m.kf_ftr_point[s_ftr_off[r] + (q - s_seq_base[r])];
-    if (p >= 0 && !m.pt_unlinked[p]) atomicMin(&pl.first_seq[p], q);
-  }
-  __syncthreads();
-  // ---- reprojectPoint (:246-259) for the keyframe points and the point candidates (:118-138)
-  for (int q = t; q < m_all; q += nt) {
-    int p, r = -1;
-    if (q < m_kf) {
-      r = 0;
-      while (r + 1 < n_sel && q >= s_seq_base[r + 1]) ++r;
-      p = m.kf_ftr_point[s_ftr_off[r] + (q - s_seq_base[r])];
-      if (p < 0) continue;
-      const int fs = pl.first_seq[p];                                        // (asked for together with the flag)
-      if (m.pt_unlinked[p] || fs != q) continue;
-    } else {
-      p = m.cand_point[q - m_kf];
-      if (p < 0 || m.pt_unlinked[p]) continue;
-    }
-    const int ptype = m.pt_type[p];                                          // (in flight during the projection)
-    double xyz_f[3], px[2];
-    se3_act(T, m.pt_pos + 3 * (size_t)p, xyz_f);
-    world2cam(cam, xyz_f, px);                                             // frame->w2c(point->pos_)
-    const int ix = (int)px[0], iy = (int)px[1];                            // px.cast<int>()
-    const bool in = px[0] == px[0] && px[1] == px[1] && ix >= 8 && ix < cam.width - 8 && iy >= 8 && iy < cam.height - 8;   // isInFrame(., 8)
-    if (in) {
-      const int cell = (int)(px[1] / pl.grid_size) * pl.grid_cols + (int)(px[0] / pl.grid_size);
-      const int idx = atomicAdd(&s_n_kept, 1);
-      if (idx < pl.cap) {
-        pl.item_point[idx] = p;
-        pl.item_px[2 * idx] = px[0]; pl.item_px[2 * idx + 1] = px[1];
-        pl.item_cell[idx] = cell;
-        pl.item_key[idx] = ((unsigned long long)(3 - ptype) << 32) | (unsigned)q;   // cell.sort: higher type first, stable
-        atomicAdd(&cell_count[cell], 1);
-      } else {
-        s_overflow = 1;
-      }
-      if (r >= 0) atomicAdd(&s_overlap[r], 1);                             // overlap_kfs.back().second++ (:112-113)
-    } else if (q >= m_kf) {
-      // a candidate that is not in the frame (:126-135); the point sits in no cell, nobody else touches it
-      const int nf = m.pt_n_failed[p] + 3;
-      m.pt_n_failed[p] = nf;
-      if (nf > 30) { m.pt_type[p] = TYPE_DELETED; m.pt_unlinked[p] = 1; s_changed = 1; }    // deleteCandidate + erase
-    }
-  }
-  __syncthreads();
-  const int n_kept = s_n_kept < pl.cap ? s_n_kept : pl.cap;
-  unsigned long long* const seg_key = n_kept <= TRK_LDS_ITEMS ? s_seg_key : pl.seg_key;
-  // ---- cell segments
-  block_exclusive_scan(cell_count, pl.n_cells, s_part);                    // cell_count[c] = start of cell c, [n_cells] = total
-  for (int c = t; c <= pl.n_cells; c += nt) pl.cell_offset[c] = cell_count[c];
-  for (int i = t; i < n_kept; i += nt) {
-    const int c = pl.item_cell[i];
-    const unsigned long long key = pl.item_key[i];
-    const int at = cell_count[c] + atomicAdd(&cell_fill[c], 1);
-    pl.seg[at] = i;
-    seg_key[at] = key;
-  }
-  __syncthreads();
-  // ---- trial order inside the cell, and the reference feature of every candidate
-  const double framepos[3] = {s_framepos[0], s_framepos[1], s_framepos[2]};
-  for (int s = t; s < n_kept; s += nt) {
-    const int i = pl.seg[s];
-    const unsigned long long key = seg_key[s];
-    const int c = pl.item_cell[i];
-    const int p = pl.item_point[i];
-    const double pxc[2] = {pl.item_px[2 * i], pl.item_px[2 * i + 1]};
-    const int c0 = cell_count[c], c1 = cell_count[c + 1];
-    int rank = 0;
-    for (int j = c0; j < c1; ++j) rank += seg_key[j] < key ? 1 : 0;
-    const int o = c0 + rank;
-    const bool deleted = m.pt_type[p] == TYPE_DELETED;
-    int obs = -1;
-    bool view_ok = false;
-    if (!deleted && m.pt_obs_offset[p + 1] > m.pt_obs_offset[p]) view_ok = close_view_obs(m, p, framepos, s_kf_pos, &obs);
-    pl.cand_point[o] = p;
-    pl.cand_obs[o] = view_ok ? obs : -1;
-    pl.cand_deleted[o] = deleted ? 1 : 0;
-    // the matcher's record of the candidate (Matcher::findMatchDirect up to the warp, svo_match_device.h): formed here,
-    // read by the warp / alignment stages and by the replay
-    if (view_ok) {
-      pl.cand_level_ref[o] = m.obs_level[obs];
-      recs[o] = md_geometry_item(mf, T_slot_w, m.kf_slot[m.obs_kf[obs]], m.obs_level[obs], m.obs_px + 2 * (size_t)obs, m.obs_f + 3 * (size_t)obs,
-                                 m.pt_pos + 3 * (size_t)p, m.obs_edgelet[obs] != 0, m.obs_grad + 2 * (size_t)obs, pxc);
-    } else {
-      // a deleted point is erased from its cell (:190-194), a point without a close view fails the match at once (matcher.cpp:161-162)
-      pl.cand_level_ref[o] = 0;
-      SeedRec rc = md_dead_record();
-      rc.uv0[0] = pxc[0]; rc.uv0[1] = pxc[1];
-      recs[o] = rc;
-    }
-  }
-  if (t == 0) {
-    pl.counters[0] = n_kept;
-    pl.counters[1] = s_overflow;
-    pl.counters[2] = s_changed;
-    pl.counters[3] = n_sel;
-  }
-  if (t < TRK_MAX_SEL) { pl.overlap_kf[t] = t < n_sel ? s_sel[t] : -1; pl.overlap_count[t] = t < n_sel ? s_overlap[t] : 0; }
-}
-
-// ---- the cell loop of Reprojector::reprojectMap (S/reprojector.cpp:149-166) with reprojectCell (:180-241) replayed over
-// the batch results: per cell the first successful candidate wins, the loop stops after the cell that takes n_matches
-// beyond max_fts; point bookkeeping (:202-215), the frame's new features (:217-231) and the inputs of the pose refinement.
-SVO_DEV void trk_replay_body(const TrkMap& m, const TrkPlan& pl, const TrkFeat& ft, const Cam& cam, const FrameState* __restrict__ sia_state,
-                             const SeedRec* __restrict__ recs, int* __restrict__ cell_winner,
-                             int* __restrict__ cell_cum, int max_fts, int quality_min_fts) {
-  __shared__ int s_part[TRK_THREADS];
-  __shared__ int s_cut, s_changed;
-  __shared__ unsigned long long s_trials;
-  const int t = threadIdx.x, nt = blockDim.x;
-  const int n_cells = pl.n_cells;
-  if (t == 0) { s_cut = n_cells - 1; s_changed = pl.counters[2]; s_trials = 0ull; }
-  // first success per cell
-  for (int c = t; c < n_cells; c += nt) {
-    int w = -1;
-    for (int i = pl.cell_offset[c]; i < pl.cell_offset[c + 1] && w < 0; ++i)
-      if (!pl.cand_deleted[i] && recs[i].path >= 0 && recs[i].matched) w = i;      // findMatchDirect returned true
-    cell_winner[c] = w;
-    cell_cum[c] = w >= 0 ? 1 : 0;
-  }
-  __syncthreads();
-  block_exclusive_scan(cell_cum, n_cells, s_part);                          // cell_cum[c] = matches before cell c
-  for (int c = t; c < n_cells; c += nt)
-    if (cell_cum[c] + (cell_winner[c] >= 0 ? 1 : 0) > max_fts) atomicMin(&s_cut, c);     // n_matches_ > maxFts after this cell (:164-165)
-  __syncthreads();
-  const int cut = s_cut;
-  double T[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) T[k] = sia_state->T_cur_w[k];
-  unsigned long long my_trials = 0ull;
-  for (int c = t; c <= cut && c < n_cells; c += nt) {
-    const int w = cell_winner[c];
-    const int end = w >= 0 ? w + 1 : pl.cell_offset[c + 1];
-    for (int i = pl.cell_offset[c]; i < end; ++i) {
-      ++my_trials;                                                          // ++n_trials_ (:188)
-      if (pl.cand_deleted[i]) continue;                                     // TYPE_DELETED: erased from the cell (:190-194)
-      const int p = pl.cand_point[i];
-      if (i != w) {                                                         // :202-209
-        const int nf = m.pt_n_failed[p] + 1;
-        m.pt_n_failed[p] = nf;
-        const int ty = m.pt_type[p];
-        if ((ty == TYPE_UNKNOWN && nf > 15) || (ty == TYPE_CANDIDATE && nf > 30)) {   // safeDeletePoint / deleteCandidatePoint
-          m.pt_type[p] = TYPE_DELETED; m.pt_unlinked[p] = 1; s_changed = 1;
-        }
-        continue;
-      }
-      const int ns = m.pt_n_succeeded[p] + 1;                               // :211-214
-      m.pt_n_succeeded[p] = ns;
-      if (m.pt_type[p] == TYPE_UNKNOWN && ns > 10) m.pt_type[p] = TYPE_GOOD;
-      const int fi = cell_cum[c];                                           // creation order = cell order
-      if (fi < ft.cap) {
-        const SeedRec& rc = recs[i];
-        const double u = rc.step[0], v = rc.step[1];                        // px_cur = px_scaled * (1 << search_level_) (matcher.cpp:200)
-        const double* pp = m.pt_pos + 3 * (size_t)p;
-        ft.px[2 * fi] = u; ft.px[2 * fi + 1] = v;
-        double fv[3];
-        cam2world(cam, u, v, fv);                                           // Feature(frame, px, level): f = cam2world(px) (I/feature.h:43-51)
-        ft.f[3 * fi] = fv[0]; ft.f[3 * fi + 1] = fv[1]; ft.f[3 * fi + 2] = fv[2];
-        ft.pos[3 * fi] = pp[0]; ft.pos[3 * fi + 1] = pp[1]; ft.pos[3 * fi + 2] = pp[2];
-        ft.level[fi] = rc.search_level;
-        ft.point[fi] = p;
-        ft.has_point[fi] = 1;
-        double g0 = 1.0, g1 = 0.0;
-        const int obs = pl.cand_obs[i];
-        const bool edge = m.obs_edgelet[obs] != 0;
-        if (edge) {                                                         // grad = (A_cur_ref_ * ref_ftr_->grad).normalized() (:224-229)
-          const double* Tr = m.T_kf_w + 7 * (size_t)m.obs_kf[obs];
-          double T_ref_inv[7], T_cur_ref[7], A[4];
-          se3_inverse(Tr, T_ref_inv);
-          se3_mul(T, T_ref_inv, T_cur_ref);
-          const double dx = T_ref_inv[0] - pp[0], dy = T_ref_inv[1] - pp[1], dz = T_ref_inv[2] - pp[2];
-          get_warp_matrix_affine(cam, m.obs_px + 2 * (size_t)obs, m.obs_f + 3 * (size_t)obs, sqrt(dx * dx + dy * dy + dz * dz), T_cur_ref, m.obs_level[obs], A);
-          const double gr0 = m.obs_grad[2 * (size_t)obs], gr1 = m.obs_grad[2 * (size_t)obs + 1];
-          g0 = A[0] * gr0 + A[1] * gr1;
-          g1 = A[2] * gr0 + A[3] * gr1;
-          const double n2 = g0 * g0 + g1 * g1;
-          if (n2 > 0.0) { const double nn = sqrt(n2); g0 = g0 / nn; g1 = g1 / nn; }
-        }
-        ft.edgelet[fi] = edge ? 1 : 0;
-        ft.grad[2 * fi] = g0; ft.grad[2 * fi + 1] = g1;
-      }
-    }
-  }
-  if (my_trials) atomicAdd(&s_trials, my_trials);
-  __syncthreads();
-  if (t == 0) {
-    const int last = cut < n_cells ? cut : n_cells - 1;
-    int n_matches = n_cells > 0 ? cell_cum[last] + (cell_winner[last] >= 0 ? 1 : 0) : 0;
-    const int n_feat = n_matches < ft.cap ? n_matches : ft.cap;
-    pl.counters[2] = s_changed;
-    pl.counters[4] = n_feat;
-    // processFrame returns before the pose refinement when the reprojector matched too few points (:208-215)
-    pl.counters[5] = n_matches < quality_min_fts ? 0 : n_feat;
-    pl.counters[6] = (int)(s_trials & 0xffffffffull);
-    pl.counters[7] = n_matches;
-  }
-}
-
-// The value of a feature for key-point slot j (0: distance from the centre, smaller is better; 1..4: the quadrant products,
-// larger is better, -inf outside the quadrant -- the two left quadrants test x against cv as the reference does,
-// S/frame.cpp:133,142).  Shared by the re-selection after deletions and by the selection for a promoted keyframe.
-SVO_DEV double key_slot_value(int cu, int cv, int j, double x, double y) {
-  if (j == 0) return fmax(fabs(x - cu), fabs(y - cv));
-  const bool in = j == 1 ? (x >= cu && y >= cv) : j == 2 ? (x >= cu && y < cv) : j == 3 ? (x < cv && y < cv) : (x < cv && y >= cv);
-  return in ? (x - cu) * (y - cv) : -HUGE_VAL;
-}
-// a thread's running best of the five slots over the features it visits in ascending index: the first best index is kept
-struct KeyBest { double v[5]; int i[5]; };
-SVO_DEV void key_best_init(KeyBest& b) {
-#pragma unroll
-  for (int j = 0; j < 5; ++j) { b.v[j] = j == 0 ? HUGE_VAL : -HUGE_VAL; b.i[j] = INT_MAX; }
-}
-SVO_DEV void key_best_offer(KeyBest& b, int cu, int cv, int idx, double x, double y) {
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const double v = key_slot_value(cu, cv, j, x, y);
-    const bool better = j == 0 ? v < b.v[j] : v > b.v[j];
-    if (better) { b.v[j] = v; b.i[j] = idx; }
-  }
-}
-// The five slots over the bests of the workgroup's first KEY_THREADS threads: thread j < 5 gets slot j's best value and, on
-// ties, the lowest feature index; false: no contender (a feature outside the quadrant is none) or not one of the five threads.
-// Block-uniform call with a barrier inside (between the threads' stores to LDS and the five threads' reads).
-constexpr int KEY_THREADS = 256;
-SVO_DEV bool key_best_select(const KeyBest& best, double* bv_out, int* bi_out) {
-  __shared__ int s_idx[5][KEY_THREADS];
-  __shared__ double s_val[5][KEY_THREADS];
-  const int t = threadIdx.x;
-  if (t < KEY_THREADS) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) { s_val[j][t] = best.v[j]; s_idx[j][t] = best.i[j]; }
-  }
-  __syncthreads();
-  if (t >= 5) return false;
-  double bv = t == 0 ? HUGE_VAL : -HUGE_VAL;
-  int bi = INT_MAX;
-  for (int q = 0; q < KEY_THREADS; ++q) {
-    const double v = s_val[t][q];
-    const int i = s_idx[t][q];
-    if (i == INT_MAX) continue;
-    const bool better = t == 0 ? v < bv : v > bv;
-    if (better || (v == bv && i < bi)) { bv = v; bi = i; }
-  }
-  *bv_out = bv; *bi_out = bi;
-  return bi != INT_MAX && (t == 0 || bv > -HUGE_VAL);
-}
-
-// ---- Frame::removeKeyPoint / setKeyPoints (S/frame.cpp:83-165) for the keyframes that lost a key feature to a point the
-// reprojector deleted in the previous frame (Map::safeDeletePoint, S/map.cpp:78-88): one workgroup per keyframe.
-// A keyframe none of whose key features lost its point keeps its key features untouched, as in the reference (they are
-// incumbents of the frame's history, not necessarily what a fresh selection would give).  In a keyframe that lost one,
-// every slot is contested again by every feature that still has a point, in fts_ order with strict improvement: the
-// incumbent stays on a tie, otherwise the first feature that reaches the best value wins.  A feature's pixel is the
-// observation of its point in this keyframe.
-__global__ __launch_bounds__(KEY_THREADS) void trk_rekey_kernel(TrkMap m, int* __restrict__ kf_key_point, Cam cam) {
-  const int k = blockIdx.x, t = threadIdx.x, nt = blockDim.x;        // (nt = KEY_THREADS)
-  __shared__ int s_found, s_inc[5];
-  __shared__ double s_inc_val[5];
-  const int cu = cam.width / 2, cv = cam.height / 2;
-  // pixel of point p's observation in keyframe k (false: none)
-  auto px_in_kf = [&](int p, double* x, double* y) {
-    for (int o = m.pt_obs_offset[p]; o < m.pt_obs_offset[p + 1]; ++o)
-      if (m.obs_kf[o] == k) { *x = m.obs_px[2 * (size_t)o]; *y = m.obs_px[2 * (size_t)o + 1]; return true; }
-    return false;
-  };
-  if (t == 0) s_found = 0;
-  __syncthreads();
-  if (t < 5) {
-    int p = kf_key_point[5 * k + t];
-    if (p >= 0 && m.pt_unlinked[p]) { p = -1; atomicOr(&s_found, 1); }       // the key feature's point is gone (:85-88, :157-162)
-    double x = 0, y = 0;
-    const bool has = p >= 0 && px_in_kf(p, &x, &y);
-    s_inc[t] = has ? p : -1;
-    s_inc_val[t] = has ? key_slot_value(cu, cv, t, x, y) : 0.0;
-  }
-  __syncthreads();
-  if (!s_found) return;                                                        // block-uniform
-  KeyBest best;
-  key_best_init(best);
-  const int f0 = m.kf_ftr_offset[k], f1 = m.kf_ftr_offset[k + 1];
-  for (int i = f0 + t; i < f1; i += nt) {                                      // ascending per thread: the first best index is kept
-    const int p = m.kf_ftr_point[i];
-    if (p < 0 || m.pt_unlinked[p]) continue;                                   // ftr->point == NULL
-    double x, y;
-    if (!px_in_kf(p, &x, &y)) continue;
-    key_best_offer(best, cu, cv, i, x, y);
-  }
-  double bv;
-  int bi;
-  const bool challenger = key_best_select(best, &bv, &bi);
-  if (t < 5) {
-    int winner = s_inc[t];
-    if (challenger && (winner < 0 || (t == 0 ? bv < s_inc_val[t] : bv > s_inc_val[t]))) winner = m.kf_ftr_point[bi];
-    kf_key_point[5 * k + t] = winner;
-  }
-}
-
-// ---- one observation (a keyframe's feature that refers to a point) as a value.  The field list of an observation is written
-// here, once for reading and once for writing, and once each for the two things a new observation is made from.
-struct TrkCandRec { double pos[3], px[2], f[3], grad[2]; int kf, level, edgelet, obs; };    // obs: where its observation goes
-struct ObsRow { int kf; double px[2], f[3]; int level; uint8_t edgelet; double grad[2]; };
-SVO_DEV ObsRow obs_load(const TrkMap& m, size_t o) {
-  return {m.obs_kf[o], {m.obs_px[2 * o], m.obs_px[2 * o + 1]}, {m.obs_f[3 * o], m.obs_f[3 * o + 1], m.obs_f[3 * o + 2]},
-          m.obs_level[o], m.obs_edgelet[o], {m.obs_grad[2 * o], m.obs_grad[2 * o + 1]}};
-}
-SVO_DEV void obs_store(const TrkTables& g, size_t d, const ObsRow& r) {
-  g.obs_kf[d] = r.kf;
-  g.obs_px[2 * d] = r.px[0]; g.obs_px[2 * d + 1] = r.px[1];
-  g.obs_f[3 * d] = r.f[0]; g.obs_f[3 * d + 1] = r.f[1]; g.obs_f[3 * d + 2] = r.f[2];
-  g.obs_level[d] = r.level; g.obs_edgelet[d] = r.edgelet;
-  g.obs_grad[2 * d] = r.grad[0]; g.obs_grad[2 * d + 1] = r.grad[1];
-}
-// feature i of the tracked frame, seen from keyframe k
-SVO_DEV ObsRow obs_of_feature(const TrkFeat& ft, int i, int k) {
-  return {k, {ft.px[2 * i], ft.px[2 * i + 1]}, {ft.f[3 * i], ft.f[3 * i + 1], ft.f[3 * i + 2]}, ft.level[i], ft.edgelet[i],
-          {ft.grad[2 * i], ft.grad[2 * i + 1]}};
-}
-SVO_DEV ObsRow obs_of_record(const TrkCandRec& r) {
-  return {r.kf, {r.px[0], r.px[1]}, {r.f[0], r.f[1], r.f[2]}, r.level, (uint8_t)(r.edgelet ? 1 : 0), {r.grad[0], r.grad[1]}};
-}
-
-// ---- the map grows in place.  New point candidates (DepthFilter::updateSeeds :310-331 + MapPointCandidates::newCandidatePoint,
-// S/map.cpp:226-231): n records from one staged block go to the tails of the point tables and of the current table set (tb);
-// no entry that existed before is written.
-__global__ void trk_add_candidates_kernel(int n, const TrkCandRec* __restrict__ rec, int n_points, int n_cand, double* __restrict__ pt_pos,
-                                          int* __restrict__ pt_type, int* __restrict__ pt_n_failed, int* __restrict__ pt_n_succeeded,
-                                          uint8_t* __restrict__ pt_unlinked, TrkTables tb) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const TrkCandRec r = rec[i];
-  const size_t p = (size_t)n_points + i;
-  pt_pos[3 * p] = r.pos[0]; pt_pos[3 * p + 1] = r.pos[1]; pt_pos[3 * p + 2] = r.pos[2];
-  pt_type[p] = TYPE_CANDIDATE; pt_n_failed[p] = 0; pt_n_succeeded[p] = 0; pt_unlinked[p] = 0;
-  if (p == 0) tb.pt_obs_offset[0] = 0;                                         // (a map without points has no offsets yet)
-  tb.pt_obs_offset[p + 1] = r.obs + (r.kf >= 0 ? 1 : 0);
-  tb.cand_point[n_cand + i] = (int)p;
-  if (r.kf >= 0) obs_store(tb, (size_t)r.obs, obs_of_record(r));
-}
-
-// ---- the rebuild kernels: a promotion, a removal, a renumbering.  Each is one workgroup of TRK_THREADS that reads the current
-// table set through m and writes the other set g (the pt_* rows, the keyframe tables and the last frame are edited where they
-// lie), with sc and the per-point array mark as scratch, and leaves its counts in sc.out (trk_rebuild_end).
-// The tracked frame becomes keyframe n_kf (FrameHandlerMono::processFrame :267-276, map_.addKeyframe :312): the observation CSR
-// (Point::addFrameRef pushes the new observation to the FRONT of Point::obs_, S/point.cpp:61-65), the keyframes' feature rows
-// (the new keyframe's row, and the seed features MapPointCandidates::addCandidatePointToFrame adds to the END of their
-// keyframes' rows, S/map.cpp:236-254) and the candidate list (compacted, order kept).  out[0]: promoted candidates.
-constexpr int TRK_MAX_FRAME_FEATURES = 2816;   // trk_check_config
-__global__ __launch_bounds__(TRK_THREADS) void trk_promote_kernel(TrkMap m, TrkTables g, TrkScratch sc, double* __restrict__ T_kf_w,
-                                                                  double* __restrict__ T_slot_w, int* __restrict__ kf_slot,
-                                                                  int* __restrict__ kf_key_point, int* __restrict__ mark, TrkFeat ft, TrkLast last,
-                                                                  int n_feat, int slot, Cam cam) {
-  __shared__ int s_part[TRK_THREADS];
-  __shared__ int s_fscan[TRK_MAX_FRAME_FEATURES + 1];
-  __shared__ int s_n_promoted;
-  const int t = threadIdx.x, nt = blockDim.x;
-  const int k = m.n_kf;
-  if (t == 0) s_n_promoted = 0;
-  // ---- the frame's features that still have a point (mark[p] = the feature), their rank in creation order
-  for (int p = t; p < m.n_points; p += nt) mark[p] = INT_MAX;
-  for (int i = t; i < n_feat; i += nt) s_fscan[i] = last.point[i] >= 0 ? 1 : 0;
-  __syncthreads();
-  for (int i = t; i < n_feat; i += nt) {
-    const int p = last.point[i];
-    if (p >= 0) atomicMin(&mark[p], i);
-  }
-  __syncthreads();
-  // ---- observations: every point's old range behind its new observation
-  for (int p = t; p < m.n_points; p += nt) g.pt_obs_offset[p] = m.pt_obs_offset[p + 1] - m.pt_obs_offset[p] + (mark[p] != INT_MAX ? 1 : 0);
-  __syncthreads();
-  block_exclusive_scan(g.pt_obs_offset, m.n_points, s_part);
-  block_exclusive_scan(s_fscan, n_feat, s_part);
-  for (int p = t; p < m.n_points; p += nt) {
-    size_t d = (size_t)g.pt_obs_offset[p];
-    const int i = mark[p];
-    if (i != INT_MAX) obs_store(g, d++, obs_of_feature(ft, i, k));
-    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o) obs_store(g, d++, obs_load(m, o));
-  }
-  // ---- MapPointCandidates::addCandidatePointToFrame: a candidate the frame observes becomes a map point; the others stay
-  for (int c = t; c < m.n_candidates; c += nt) {
-    const int p = m.cand_point[c];
-    int seed = -2;
-    if (p >= 0 && mark[p] != INT_MAX) {
-      const int o0 = m.pt_obs_offset[p], o1 = m.pt_obs_offset[p + 1];
-      seed = o1 > o0 ? m.obs_kf[o1 - 1] : -1;                                  // it->second->frame (none: that keyframe left the map)
-      m.pt_type[p] = TYPE_UNKNOWN; m.pt_n_failed[p] = 0;
-      atomicAdd(&s_n_promoted, 1);
-    }
-    sc.cand_seed[c] = seed;                                                    // (read back by this thread in the compaction, by all behind its barriers)
-  }
-  block_compact(m.n_candidates, sc.cand_scan, s_part, [&](int c) { return m.cand_point[c] >= 0 && sc.cand_seed[c] == -2; },
-                [&](int r, int c) { g.cand_point[r] = m.cand_point[c]; });
-  // ---- the keyframes' feature rows: the old row, then the promoted seeds of that keyframe in list order; the new keyframe's row
-  for (int kk = t; kk <= k; kk += nt) {
-    int cnt = s_fscan[n_feat];
-    if (kk < k) {
-      cnt = m.kf_ftr_offset[kk + 1] - m.kf_ftr_offset[kk];
-      for (int c = 0; c < m.n_candidates; ++c) cnt += sc.cand_seed[c] == kk ? 1 : 0;
-    }
-    g.kf_ftr_offset[kk] = cnt;
-  }
-  __syncthreads();
-  block_exclusive_scan(g.kf_ftr_offset, k + 1, s_part);
-  for (int kk = 0; kk < k; ++kk) {
-    const int src = m.kf_ftr_offset[kk], len = m.kf_ftr_offset[kk + 1] - src, dst = g.kf_ftr_offset[kk];
-    for (int j = t; j < len; j += nt) g.kf_ftr_point[dst + j] = m.kf_ftr_point[src + j];
-  }
-  for (int kk = t; kk < k; kk += nt) {
-    int at = g.kf_ftr_offset[kk] + m.kf_ftr_offset[kk + 1] - m.kf_ftr_offset[kk];
-    for (int c = 0; c < m.n_candidates; ++c)
-      if (sc.cand_seed[c] == kk) g.kf_ftr_point[at++] = m.cand_point[c];
-  }
-  const int row_k = g.kf_ftr_offset[k];
-  for (int i = t; i < n_feat; i += nt) {
-    const int p = last.point[i];
-    if (p >= 0) g.kf_ftr_point[row_k + s_fscan[i]] = p;
-  }
-  // ---- Frame::setKeyPoints (S/frame.cpp:84-146) from five empty slots over the features with a point, in fts_ order
-  const int cu = cam.width / 2, cv = cam.height / 2;
-  KeyBest best;
-  key_best_init(best);
-  if (t < KEY_THREADS)
-    for (int i = t; i < n_feat; i += KEY_THREADS)
-      if (last.point[i] >= 0) key_best_offer(best, cu, cv, i, ft.px[2 * i], ft.px[2 * i + 1]);
-  double bv;
-  int bi;
-  const bool challenger = key_best_select(best, &bv, &bi);
-  if (t < 5) kf_key_point[5 * k + t] = challenger ? last.point[bi] : -1;
-  if (t < 7) {                                                                  // the pose as the frame left it
-    const double v = last.T_f_w[t];
-    T_kf_w[7 * (size_t)k + t] = v;
-    T_slot_w[7 * (size_t)slot + t] = v;
-  }
-  if (t == 0) {
-    kf_slot[k] = slot;
-    sc.out[0] = s_n_promoted;
-    sc.out[1] = g.kf_ftr_offset[k + 1];
-    sc.out[2] = g.pt_obs_offset[m.n_points];
-    sc.out[3] = sc.cand_scan[m.n_candidates];
-  }
-}
-
-// rows first + 1 .. n_rows - 1 of an [n_rows][W] table move down by one row in place: every element is read, then -- behind
-// a barrier -- written.  A thread holds at most two (TRK_LDS_KF rows over TRK_THREADS threads).  Block-uniform call.
-template <typename T, int W>
-SVO_DEV void rows_move_down(T* a, int first, int n_rows) {
-  static_assert(TRK_LDS_KF * W <= 2 * TRK_THREADS, "two elements per thread cover the largest table");
-  const int t = threadIdx.x, nt = blockDim.x;
-  const int n = (n_rows - 1 - first) * W;
-  T* dst = a + (size_t)first * W;
-  T v0 = T(), v1 = T();
-  if (t < n) v0 = dst[t + W];
-  if (t + nt < n) v1 = dst[t + nt + W];
-  __syncthreads();
-  if (t < n) dst[t] = v0;
-  if (t + nt < n) dst[t + nt] = v1;
-}
-
-// feature i of the last frame loses its point (Map::safeDeletePoint clears ftr->point of every observation), and the solver
-// its copy of it: what it holds of a feature without a point
-SVO_DEV void last_feature_loses_point(const TrkLast& last, int i) {
-  last.point[i] = -1;
-  if (i < last.sia_max_n) {
-    last.sia_has_point[i] = 0;
-    last.sia_pos[3 * i] = 0.0; last.sia_pos[3 * i + 1] = 0.0; last.sia_pos[3 * i + 2] = 1.0;
-  }
-}
-
-// ---- keyframe k leaves the map: Map::safeDeleteFrame (S/map.cpp:41-64) on the tables.  removePtFrameRef (:66-80) over the
-// keyframe's features that have a point: a point with at most two observations is deleted (safeDeletePoint :82-93, deletePoint
-// :95-99), any other loses its observation in k (Point::deleteFrameRef, S/point.cpp:75-86).  A point has one feature per keyframe
-// at most, so the decisions are independent.  removeFrameCandidates / deleteCandidate (:271-285, :297-304): the candidates whose
-// seed feature (the last observation of their range) lies in k are deleted.  The second set receives the tables in the form a
-// host flatten gives them: an unlinked point -- by this call or by an earlier frame -- has no observations, is in no feature
-// row and not in the candidate list; row order and observation order are kept, keyframes above k move down by one.  The key
-// points of the other keyframes are left to trk_rekey_kernel (the deleted points are unlinked).  A feature of the last frame
-// whose point was deleted here loses it.  out[0]: deleted points, out[4]: deleted candidates.
-__global__ __launch_bounds__(TRK_THREADS) void trk_remove_kernel(TrkMap m, TrkTables g, TrkScratch sc, double* __restrict__ T_kf_w,
-                                                                 int* __restrict__ kf_slot, int* __restrict__ kf_key_point, int* __restrict__ mark,
-                                                                 TrkLast last, int k, int n_ftr) {
-  __shared__ int s_part[TRK_THREADS];
-  __shared__ int s_del_points, s_del_cands;
-  const int t = threadIdx.x, nt = blockDim.x;
-  const int K = m.n_kf, P = m.n_points;
-  if (t == 0) { s_del_points = 0; s_del_cands = 0; }
-  for (int p = t; p < P; p += nt) mark[p] = 0;
-  __syncthreads();
-  // ---- the decisions: mark[p] = 1 deleted as a map point, 2 deleted as a candidate
-  const int r0 = m.kf_ftr_offset[k], r1 = m.kf_ftr_offset[k + 1];
-  auto linked = [&](int p) { return p >= 0 && !m.pt_unlinked[p]; };             // ftr->point != NULL
-  for (int i = r0 + t; i < r1; i += nt) {
-    const int p = m.kf_ftr_point[i];
-    if (linked(p) && m.pt_obs_offset[p + 1] - m.pt_obs_offset[p] <= 2) mark[p] = 1;      // pt->obs_.size() <= 2
-  }
-  for (int c = t; c < m.n_candidates; c += nt) {
-    const int p = m.cand_point[c];
-    if (!linked(p)) continue;
-    const int o0 = m.pt_obs_offset[p], o1 = m.pt_obs_offset[p + 1];
-    if (o1 > o0 && m.obs_kf[o1 - 1] == k) mark[p] = 2;                           // it->second->frame == frame
-  }
-  __syncthreads();
-  // ---- the points: type and link, and what is left of every observation list
-  int n_dp = 0, n_dc = 0;
-  for (int p = t; p < P; p += nt) {
-    const int mk = mark[p];
-    bool gone = m.pt_unlinked[p] != 0;
-    if (mk) {
-      m.pt_type[p] = TYPE_DELETED; m.pt_unlinked[p] = 1;
-      gone = true;
-      if (mk == 1) ++n_dp; else ++n_dc;
-    }
-    int cnt = 0;
-    if (!gone)
-      for (int o = m.pt_obs_offset[p]; o < m.pt_obs_offset[p + 1]; ++o) cnt += m.obs_kf[o] != k ? 1 : 0;
-    g.pt_obs_offset[p] = cnt;
-  }
-  if (n_dp) atomicAdd(&s_del_points, n_dp);
-  if (n_dc) atomicAdd(&s_del_cands, n_dc);
-  __syncthreads();
-  block_exclusive_scan(g.pt_obs_offset, P, s_part);
-  for (int p = t; p < P; p += nt) {
-    if (m.pt_unlinked[p]) continue;
-    size_t d = (size_t)g.pt_obs_offset[p];
-    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o) {
-      ObsRow r = obs_load(m, o);
-      if (r.kf == k) continue;
-      if (r.kf > k) --r.kf;
-      obs_store(g, d++, r);
-    }
-  }
-  // ---- the feature rows: row k goes, the others keep the entries that still have a point
-  block_compact(n_ftr, sc.ftr_scan, s_part, [&](int i) { return (i < r0 || i >= r1) && linked(m.kf_ftr_point[i]); },
-                [&](int r, int i) { g.kf_ftr_point[r] = m.kf_ftr_point[i]; });
-  for (int j = t; j < K; j += nt) g.kf_ftr_offset[j] = sc.ftr_scan[m.kf_ftr_offset[j < k ? j : j + 1]];    // (K - 1 rows, K offsets)
-  // ---- the candidate list, compacted
-  block_compact(m.n_candidates, sc.cand_scan, s_part, [&](int c) { return linked(m.cand_point[c]); },
-                [&](int r, int c) { g.cand_point[r] = m.cand_point[c]; });
-  // ---- the keyframe tables
-  rows_move_down<double, 7>(T_kf_w, k, K);
-  rows_move_down<int, 5>(kf_key_point, k, K);
-  rows_move_down<int, 1>(kf_slot, k, K);
-  // ---- the last frame
-  const int n_last = *last.n;
-  for (int i = t; i < n_last; i += nt) {
-    const int p = last.point[i];
-    if (p >= 0 && p < P && mark[p]) last_feature_loses_point(last, i);
-  }
-  if (t == 0) {
-    sc.out[0] = s_del_points;
-    sc.out[1] = sc.ftr_scan[n_ftr];
-    sc.out[2] = g.pt_obs_offset[P];
-    sc.out[3] = sc.cand_scan[m.n_candidates];
-    sc.out[4] = s_del_cands;
-  }
-}
-
-// ---- the points are renumbered in place: the unlinked ones (pt_unlinked: deleted by a tracked frame or by a removal) leave
-// the tables, the others keep their order -- a living point's new index is the number of living points below it.  The tables
-// end in the form a host flatten under the new numbering writes, the one trk_remove_kernel leaves: no row, no observation, no
-// feature-row entry and no candidate entry of a dead point, -1 entries dropped, every order kept.
-// What holds a point index, and what becomes of it here:
-//   kf_key_point, kf_ftr_point, cand_point        rewritten (the pending re-selection of key points has run before the launch)
-//   TrkLast::point (the last frame's features)    rewritten; a feature whose point is dead loses it as in trk_remove_kernel
-//                                                 (none after a tracked frame)
-//   the solver's slot (sia_pos, sia_has_point)    holds positions and flags by feature, no index
-//   the pt_* rows, pt_unlinked, pt_obs_offset     the rows of the living points move down, the offsets are rebuilt
-//   TrkPlan::first_seq / item_point / cand_point, TrkFeat::point, TrkStructSel: scratch of one call, rebuilt by the next
-//   svo_hip_tracker::last_max_point               host side: set from out[4] (svo_hip_tracker_compact_points)
-//   svo_hip_tracker::track_n_points and the page-locked result block: NOT rewritten -- svo_hip_tracker_last_result keeps
-//                                                 returning the frame under the numbering it was tracked with
-// mark[p] receives old_to_new: the new index, -1 for a dead point; the host copies it out.  out[0]: the points afterwards.
-// The observation CSR, the feature rows and the candidate list go to the second set.  The pt_* rows have no second set: they
-// move down in place by an ascending walk in chunks of one block -- every thread reads the row of its point of the chunk into
-// registers, a barrier, then writes it to its new index.  A new index is never above the old one, so the writes of a chunk land
-// on rows of this chunk (read before the barrier) or of earlier chunks (read in earlier rounds), never on a row a later chunk
-// has yet to read: one barrier a chunk is enough.
-__global__ __launch_bounds__(TRK_THREADS) void trk_compact_kernel(TrkMap m, TrkTables g, TrkScratch sc, double* __restrict__ pt_pos,
-                                                                  int* __restrict__ kf_key_point, int* __restrict__ mark, TrkLast last, int n_ftr) {
-  __shared__ int s_part[TRK_THREADS];
-  __shared__ int s_last_max;
-  const int t = threadIdx.x, nt = blockDim.x;
-  const int K = m.n_kf, P = m.n_points;
-  if (t == 0) s_last_max = -1;
-  // ---- the new indices: an exclusive scan over "living" (in the second set's offsets: P + 1 entries)
-  for (int p = t; p < P; p += nt) g.pt_obs_offset[p] = m.pt_unlinked[p] ? 0 : 1;
-  __syncthreads();
-  block_exclusive_scan(g.pt_obs_offset, P, s_part);
-  const int N = g.pt_obs_offset[P];
-  for (int p = t; p < P; p += nt) mark[p] = m.pt_unlinked[p] ? -1 : g.pt_obs_offset[p];
-  __syncthreads();                                                               // (every thread holds N; the offsets are free again)
-  // ---- the observations of the living points, by new index
-  for (int p = t; p < P; p += nt) {
-    const int q = mark[p];
-    if (q >= 0) g.pt_obs_offset[q] = m.pt_obs_offset[p + 1] - m.pt_obs_offset[p];
-  }
-  __syncthreads();
-  block_exclusive_scan(g.pt_obs_offset, N, s_part);
-  for (int p = t; p < P; p += nt) {
-    const int q = mark[p];
-    if (q < 0) continue;
-    size_t d = (size_t)g.pt_obs_offset[q];
-    for (size_t o = (size_t)m.pt_obs_offset[p]; o < (size_t)m.pt_obs_offset[p + 1]; ++o) obs_store(g, d++, obs_load(m, o));
-  }
-  // ---- the feature rows and the candidate list keep the entries that still have a point, under its new index
-  auto living = [&](int p) { return p >= 0 && mark[p] >= 0; };
-  block_compact(n_ftr, sc.ftr_scan, s_part, [&](int i) { return living(m.kf_ftr_point[i]); },
-                [&](int r, int i) { g.kf_ftr_point[r] = mark[m.kf_ftr_point[i]]; });
-  if (K > 0)                                                                     // (a map without keyframes has no offsets)
-    for (int j = t; j <= K; j += nt) g.kf_ftr_offset[j] = sc.ftr_scan[m.kf_ftr_offset[j]];
-  block_compact(m.n_candidates, sc.cand_scan, s_part, [&](int c) { return living(m.cand_point[c]); },
-                [&](int r, int c) { g.cand_point[r] = mark[m.cand_point[c]]; });
-  // ---- the key points (none is dead after the re-selection; one that were would become -1)
-  for (int j = t; j < 5 * K; j += nt) {
-    const int p = kf_key_point[j];
-    if (p >= 0) kf_key_point[j] = mark[p];
-  }
-  // ---- the last frame
-  const int n_last = *last.n;
-  int last_max = -1;
-  for (int i = t; i < n_last; i += nt) {
-    const int p = last.point[i];
-    if (p < 0 || p >= P) continue;
-    const int q = mark[p];
-    if (q < 0) { last_feature_loses_point(last, i); continue; }
-    last.point[i] = q;
-    if (q > last_max) last_max = q;
-  }
-  if (last_max >= 0) atomicMax(&s_last_max, last_max);
-  // ---- the rows of the points move down in place (see above: read, barrier, write, chunk by chunk upwards).  From here on
-  // nothing reads pt_unlinked.
-  for (int base = 0; base < P; base += nt) {                                     // block-uniform
-    const int p = base + t;
-    const int q = p < P ? mark[p] : -1;
-    double x = 0.0, y = 0.0, z = 0.0;
-    int ty = 0, nf = 0, ns = 0;
-    if (q >= 0) {
-      x = pt_pos[3 * (size_t)p]; y = pt_pos[3 * (size_t)p + 1]; z = pt_pos[3 * (size_t)p + 2];
-      ty = m.pt_type[p]; nf = m.pt_n_failed[p]; ns = m.pt_n_succeeded[p];
-    }
-    __syncthreads();
-    if (q >= 0) {
-      pt_pos[3 * (size_t)q] = x; pt_pos[3 * (size_t)q + 1] = y; pt_pos[3 * (size_t)q + 2] = z;
-      m.pt_type[q] = ty; m.pt_n_failed[q] = nf; m.pt_n_succeeded[q] = ns;
-      m.pt_unlinked[q] = 0;
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    sc.out[0] = N;
-    sc.out[1] = sc.ftr_scan[n_ftr];
-    sc.out[2] = g.pt_obs_offset[N];
-    sc.out[3] = sc.cand_scan[m.n_candidates];
-    sc.out[4] = s_last_max;
-  }
-}
-
-// ---- FrameHandlerBase::optimizeStructure (S/frame_handler_base.cpp:190-210) on the points the host selected: Point::optimize
-// of each of them over its observations as the map tables hold them (keyframe pose + bearing, Point::obs_ order), the new
-// positions written into the point table, into the solver's copy of the last frame's points (the next SparseImgAlign::run reads
-// point->pos_) and into the page-locked result block.  One workgroup.
-struct TrkStructSel { int n; int point[TRK_MAX_STRUCT]; };
-// (the body of trk_structure_kernel up to its hand-over: trk_finish_frame_body runs it in front of the keyframe decision)
-SVO_DEV void trk_structure_body(const TrkMap& m, double* __restrict__ pt_pos, const TrkLast& last, const TrkStructSel& sel, int n_iter,
-                                double* __restrict__ out_pos, int* __restrict__ out_iters) {
-  __shared__ double s_new[TRK_MAX_STRUCT][3];
-  const int t = threadIdx.x, nt = blockDim.x, n_sel = sel.n;
-  if (t < n_sel) {
-    const int p = sel.point[t];
-    double P[3] = {pt_pos[3 * (size_t)p], pt_pos[3 * (size_t)p + 1], pt_pos[3 * (size_t)p + 2]};
-    const int done = point_refine_one(P, m.pt_obs_offset[p], m.pt_obs_offset[p + 1], n_iter, [&](int o, double* T, double* fo) {
-      const double* tk = m.T_kf_w + 7 * (size_t)m.obs_kf[o];
-      for (int i = 0; i < 7; ++i) T[i] = tk[i];
-      fo[0] = m.obs_f[3 * (size_t)o]; fo[1] = m.obs_f[3 * (size_t)o + 1]; fo[2] = m.obs_f[3 * (size_t)o + 2];
-    });
-    for (int i = 0; i < 3; ++i) { pt_pos[3 * (size_t)p + i] = P[i]; s_new[t][i] = P[i]; out_pos[3 * t + i] = P[i]; }
-    out_iters[t] = done;
-  }
-  __syncthreads();
-  const int n_last = *last.n < last.sia_max_n ? *last.n : last.sia_max_n;
-  for (int j = t; j < n_last; j += nt) {
-    const int p = last.point[j];
-    if (p < 0) continue;
-    for (int i = 0; i < n_sel; ++i)
-      if (sel.point[i] == p) { last.sia_pos[3 * j] = s_new[i][0]; last.sia_pos[3 * j + 1] = s_new[i][1]; last.sia_pos[3 * j + 2] = s_new[i][2]; }
-  }
-}
-__global__ __launch_bounds__(256) void trk_structure_kernel(TrkMap m, double* __restrict__ pt_pos, TrkLast last, TrkStructSel sel, int n_iter,
-                                                            double* __restrict__ out_pos, int* __restrict__ out_iters,
-                                                            unsigned long long* __restrict__ done_flag, unsigned long long seq) {
-  const int t = threadIdx.x;
-  trk_structure_body(m, pt_pos, last, sel, n_iter, out_pos, out_iters);
-  __threadfence_system();
-  __syncthreads();
-  if (t == 0) __hip_atomic_store(done_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// ---- the keyframe decision behind the structure step (FrameHandlerMono::processFrame, S/frame_handler_mono.cpp:258-260, :305):
-// frame_utils::getSceneDepth (S/frame.cpp:200-221), needNewKf (:391-403) and Map::getFurthestKeyframe (S/map.cpp:156-169) of the
-// device's last frame.  One workgroup of FIN_THREADS; block-uniform call.  pt_pos: the table the structure step has just written
-// (read through the same pointer, behind the caller's barrier).
-//   depths     every thread walks its features; the numbers become order-preserving 64-bit keys in LDS (any order: what is
-//              asked for is an order statistic), the minimum (and the maximum) an integer comparison of the keys
-//   median     radix select on the keys, 8 bits a pass from the first byte the keys differ in: a 256-bin histogram of the keys
-//              that share the prefix so far, its scan, and the bin that holds the rank extends the prefix -- exact, O(n), no
-//              floating-point atomics
-//   needNewKf  one thread per overlap keyframe, the first blocking one in list order
-//   furthest   one thread per keyframe (TRK_LDS_KF <= FIN_THREADS); "dist > maxdist from 0.0" in index order = the largest
-//              distance above zero, the lower index among equals, a NaN never: reduced with that order
-constexpr int FIN_THREADS = 256;
-constexpr int FIN_MAX_FEAT = 2816;             // svo_hip_tracker_config::max_frame_features <= this (trk_check_config)
-SVO_DEV unsigned long long depth_key(double z) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(z);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-SVO_DEV double depth_from_key(unsigned long long k) {
-  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)u);
-}
-SVO_DEV void trk_decision_body(const TrkMap& m, const double* pt_pos, const TrkLast& last, const int* __restrict__ overlap_kf,
-                               const int* __restrict__ counters, int overlap_valid, double min_dist, svo_hip_kf_decision* __restrict__ out) {
-  static_assert(TRK_LDS_KF <= FIN_THREADS, "one keyframe per thread");
-  static_assert(TRK_MAX_SEL <= FIN_THREADS, "one overlap keyframe per thread");
-  __shared__ unsigned long long s_key[FIN_MAX_FEAT];
-  __shared__ unsigned long long s_min_key, s_max_key, s_prefix;
-  __shared__ int s_hist[256], s_wave[FIN_THREADS / 64];
-  __shared__ int s_n, s_n_nan, s_rank, s_block[TRK_MAX_SEL];
-  __shared__ double s_T[7], s_pos[3], s_wdist[FIN_THREADS / 64];
-  __shared__ int s_wkf[FIN_THREADS / 64];
-  const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6;
-  if (t < 7) s_T[t] = last.T_f_w[t];
-  if (t == 0) { s_n = 0; s_n_nan = 0; s_min_key = ~0ull; s_max_key = 0ull; }
-  s_hist[t] = 0;
-  __syncthreads();
-  double T[7];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) T[i] = s_T[i];
-  if (t == 0) {
-    double Tinv[7];
-    se3_inverse(T, Tinv);                                                      // Frame::pos()
-    s_pos[0] = Tinv[0]; s_pos[1] = Tinv[1]; s_pos[2] = Tinv[2];
-  }
-  // ---- the depths: a wave appends its keys with one atomic (ranks inside the wave from the ballot) and keeps the smallest
-  // and the largest key and its NaN count in registers
-  const int n_last = *last.n < FIN_MAX_FEAT ? *last.n : FIN_MAX_FEAT;
-  unsigned long long kmin = ~0ull, kmax = 0ull;
-  int my_nan = 0;
-  for (int base = 0; base < n_last; base += nt) {                              // block-uniform
-    const int j = base + t;
-    const int p = j < n_last ? last.point[j] : -1;
-    bool have = false;
-    unsigned long long key = 0ull;
-    if (p >= 0 && p < m.n_points) {
-      double xyz_f[3];
-      se3_act(T, pt_pos + 3 * (size_t)p, xyz_f);
-      const double z = xyz_f[2];
-      if (z != z) ++my_nan;
-      else { have = true; key = depth_key(z); }
-    }
-    const unsigned long long bal = __ballot(have);
-    if (bal != 0ull) {                                                         // wave-uniform
-      const int first = __ffsll((long long)bal) - 1;
-      int slot = 0;
-      if (lane == first) slot = atomicAdd(&s_n, __popcll(bal));
-      slot = __shfl(slot, first, 64);
-      if (have) {
-        s_key[slot + __popcll(bal & ((1ull << lane) - 1ull))] = key;
-        kmin = key < kmin ? key : kmin; kmax = key > kmax ? key : kmax;
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long a = __shfl_xor(kmin, o, 64), b = __shfl_xor(kmax, o, 64);
-    kmin = a < kmin ? a : kmin; kmax = b > kmax ? b : kmax;
-    my_nan += __shfl_xor(my_nan, o, 64);
-  }
-  if (lane == 0) {
-    atomicMin(&s_min_key, kmin); atomicMax(&s_max_key, kmax);
-    if (my_nan) atomicAdd(&s_n_nan, my_nan);
-  }
-  __syncthreads();
-  const int n = s_n, n_nan = s_n_nan;
-  const bool have_median = n > 0 && n_nan == 0;
-  // ---- the median: the key of rank n / 2.  The bytes the smallest and the largest key share are every key's: the selection
-  // starts at the first byte in which they differ (none: all depths are equal).
-  const unsigned long long spread = s_min_key ^ s_max_key;
-  const int first_shift = spread == 0ull ? -8 : 56 - (__clzll((long long)spread) & ~7);
-  if (t == 0) { s_rank = n / 2; s_prefix = first_shift >= 56 ? 0ull : first_shift < 0 ? s_min_key : s_min_key & (~0ull << (first_shift + 8)); }
-  __syncthreads();
-  if (have_median) {                                                           // block-uniform
-    for (int shift = first_shift; shift >= 0; shift -= 8) {                    // (every bin is zero here)
-      const unsigned long long prefix = s_prefix;
-      const int rank = s_rank;
-      const unsigned long long above = shift == 56 ? 0ull : ~0ull << (shift + 8);
-      for (int j = t; j < n; j += nt) {
-        const unsigned long long k = s_key[j];
-        if ((k & above) == prefix) atomicAdd(&s_hist[(int)((k >> shift) & 255ull)], 1);
-      }
-      __syncthreads();
-      const int c = s_hist[t];
-      s_hist[t] = 0;                                                           // (nobody else reads this bin)
-      int incl = c;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-      }
-      if (lane == 63) s_wave[wave] = incl;
-      __syncthreads();
-      int before = 0;
-      for (int w = 0; w < wave; ++w) before += s_wave[w];
-      const int excl = before + incl - c;
-      if (rank >= excl && rank < excl + c) {                                   // exactly one bin holds the rank
-        s_prefix = prefix | ((unsigned long long)t << shift);
-        s_rank = rank - excl;
-      }
-      __syncthreads();
-    }
-  }
-  // ---- needNewKf: rel = T_f_w * kf->pos() of every overlap keyframe
-  const double depth_mean = have_median ? depth_from_key(s_prefix) : __longlong_as_double(0x7ff8000000000000ll);
-  const int n_overlap = overlap_valid ? (counters[3] < TRK_MAX_SEL ? counters[3] : TRK_MAX_SEL) : 0;
-  if (t < n_overlap) {
-    const int k = overlap_kf[t];
-    int block = 0;
-    if (k >= 0 && k < m.n_kf) {
-      const double* tk = m.T_kf_w + 7 * (size_t)k;
-      double Tk[7], Tinv[7], rel[3];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) Tk[i] = tk[i];
-      se3_inverse(Tk, Tinv);
-      se3_act(T, Tinv, rel);
-      block = fabs(rel[0]) / depth_mean < min_dist && fabs(rel[1]) / depth_mean < min_dist * 0.8 && fabs(rel[2]) / depth_mean < min_dist * 1.3;
-    }
-    s_block[t] = block;
-  }
-  // ---- Map::getFurthestKeyframe
-  double best_d = 0.0;
-  int best_k = INT_MAX;
-  if (t < m.n_kf && t < TRK_LDS_KF) {
-    const double* tk = m.T_kf_w + 7 * (size_t)t;
-    double Tk[7], Tinv[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) Tk[i] = tk[i];
-    se3_inverse(Tk, Tinv);
-    const double dx = Tinv[0] - s_pos[0], dy = Tinv[1] - s_pos[1], dz = Tinv[2] - s_pos[2];
-    const double d = sqrt(dx * dx + dy * dy + dz * dz);
-    if (d > 0.0) { best_d = d; best_k = t; }
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double od = __shfl_xor(best_d, o, 64);
-    const int ok = __shfl_xor(best_k, o, 64);
-    if (od > best_d || (od == best_d && ok < best_k)) { best_d = od; best_k = ok; }
-  }
-  if (lane == 0) { s_wdist[wave] = best_d; s_wkf[wave] = best_k; }
-  __syncthreads();
-  if (t == 0) {
-    for (int w = 1; w < FIN_THREADS / 64; ++w)
-      if (s_wdist[w] > best_d || (s_wdist[w] == best_d && s_wkf[w] < best_k)) { best_d = s_wdist[w]; best_k = s_wkf[w]; }
-    svo_hip_kf_decision r;
-    r.n_depths = n; r.n_nan_depths = n_nan;
-    r.depth_mean = depth_mean;
-    r.depth_min = n > 0 ? depth_from_key(s_min_key) : DBL_MAX;
-    r.overlap_valid = overlap_valid ? 1 : 0;
-    r.need_new_kf = overlap_valid ? 1 : -1;
-    r.blocking_kf = -1;
-    for (int i = 0; i < n_overlap; ++i)
-      if (s_block[i]) { r.need_new_kf = 0; r.blocking_kf = overlap_kf[i]; break; }
-    r.furthest_kf = best_k == INT_MAX ? -1 : best_k;
-    r.furthest_distance = best_k == INT_MAX ? 0.0 : best_d;
-    r.pos[0] = s_pos[0]; r.pos[1] = s_pos[1]; r.pos[2] = s_pos[2];
-    *out = r;                              // (out lies in host memory: written, never read back here)
-  }
-}
-
-// The structure step, a barrier, the decision, the hand-over.  st: the camera's page-locked block [pos 64 x 3][iters 64][flag]
-// [decision] (device address).
-constexpr size_t ST_O_ITERS = TRK_MAX_STRUCT * 24, ST_O_FLAG = ST_O_ITERS + TRK_MAX_STRUCT * 4, ST_O_DECISION = ST_O_FLAG + 64;
-constexpr size_t ST_BYTES = ST_O_DECISION + 128;
-static_assert(sizeof(svo_hip_kf_decision) <= 128, "the decision fits its part of the block");
-SVO_DEV void trk_finish_frame_body(const TrkMap& m, double* __restrict__ pt_pos, const TrkLast& last, const TrkStructSel& sel, int n_iter,
-                                   const int* __restrict__ overlap_kf, const int* __restrict__ counters, int overlap_valid, double min_dist,
-                                   char* st, unsigned long long seq) {
-  if (sel.n > 0) {                                                             // block-uniform
-    trk_structure_body(m, pt_pos, last, sel, n_iter, reinterpret_cast<double*>(st), reinterpret_cast<int*>(st + ST_O_ITERS));
-    __syncthreads();                                                           // the decision reads the new positions
-  }
-  trk_decision_body(m, pt_pos, last, overlap_kf, counters, overlap_valid, min_dist, reinterpret_cast<svo_hip_kf_decision*>(st + ST_O_DECISION));
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(st + ST_O_FLAG), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// (one workgroup per camera and nothing beside it: the occupancy bound leaves the structure step's per-thread arrays their place in LDS)
-__global__ __launch_bounds__(FIN_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) void trk_finish_frame_kernel(TrkMap m, double* __restrict__ pt_pos, TrkLast last, TrkStructSel sel, int n_iter,
-                                                                       const int* __restrict__ overlap_kf, const int* __restrict__ counters,
-                                                                       int overlap_valid, double min_dist, char* st, unsigned long long seq) {
-  trk_finish_frame_body(m, pt_pos, last, sel, n_iter, overlap_kf, counters, overlap_valid, min_dist, st, seq);
-}
-
-// ---- last_frame_ = new_frame_ (frame_handler_mono.cpp:91) and the result block.  One workgroup.
-SVO_DEV void trk_finish_body(const TrkMap& m, const TrkPlan& pl, const TrkFeat& ft, const TrkLast& last, const Cam& cam,
-                             const FrameState* __restrict__ sia_state,
-                             const svo_hip_pose_opt_result* __restrict__ po, svo_hip_track_result* __restrict__ res,
-                             double* __restrict__ out_px, double* __restrict__ out_f, int* __restrict__ out_level,
-                             int* __restrict__ out_point, uint8_t* __restrict__ out_edgelet, double* __restrict__ out_grad,
-                             int* __restrict__ out_pt_type, int* __restrict__ out_pt_failed, int* __restrict__ out_pt_succeeded,
-                             unsigned long long* __restrict__ done_flag, unsigned long long seq) {
-  __shared__ double s_Tnew[7];
-  const int t = threadIdx.x, nt = blockDim.x;
-  const int n_feat = pl.counters[4];
-  const int n_po = pl.counters[5];
-  const bool refined = n_po > 0 && po->ran != 0;
-  if (t == 0) {
-    svo_hip_track_result r;
-    for (int i = 0; i < 7; ++i) r.T_f_w_sia[i] = sia_state->T_cur_w[i];
-    r.sia_n_tracked = sia_state->n_meas / 16;
-    for (int i = 0; i < SVO_HIP_MAX_LEVELS; ++i) r.sia_iters[i] = sia_state->iters[i];
-    r.sia_stop = sia_state->stop;
-    r.n_features = n_feat;
-    r.n_matches = (uint64_t)pl.counters[7];
-    r.n_trials = (uint64_t)(unsigned)pl.counters[6];
-    r.n_overlap = pl.counters[3];
-    r.map_changed = pl.counters[2];
-    for (int i = 0; i < 16; ++i) { r.overlap_kf[i] = i < TRK_MAX_SEL ? pl.overlap_kf[i] : -1; r.overlap_count[i] = i < TRK_MAX_SEL ? pl.overlap_count[i] : 0; }
-    r.n_candidates = pl.counters[0];
-    r.items_overflow = pl.counters[1];
-    r.pose = *po;
-    if (!refined) {                        // the reference did not reach / did not run the refinement: nothing of it is valid
-      memset(&r.pose, 0, sizeof(r.pose));
-      for (int i = 0; i < 7; ++i) r.pose.T_f_w[i] = sia_state->T_cur_w[i];
-    }
-    // new_frame_->T_f_w_ when processFrame hands the frame over: the refined pose, or -- too few matches (:211) -- the last frame's
-    for (int i = 0; i < 7; ++i) { r.T_f_w[i] = n_po > 0 ? r.pose.T_f_w[i] : last.T_f_w[i]; s_Tnew[i] = r.T_f_w[i]; }
-    *res = r;                              // (res lies in host memory: written, never read back here)
-  }
-  __syncthreads();
-  for (int i = t; i < n_feat; i += nt) {
-    const int p = ft.has_point[i] ? ft.point[i] : -1;                       // pose_optimizer.cpp:154-157: (*it)->point = NULL
-    out_px[2 * i] = ft.px[2 * i]; out_px[2 * i + 1] = ft.px[2 * i + 1];
-    out_f[3 * i] = ft.f[3 * i]; out_f[3 * i + 1] = ft.f[3 * i + 1]; out_f[3 * i + 2] = ft.f[3 * i + 2];
-    out_level[i] = ft.level[i];
-    out_point[i] = p;
-    out_edgelet[i] = ft.edgelet[i];
-    out_grad[2 * i] = ft.grad[2 * i]; out_grad[2 * i + 1] = ft.grad[2 * i + 1];
-    last.px[2 * i] = ft.px[2 * i]; last.px[2 * i + 1] = ft.px[2 * i + 1];
-    last.f[3 * i] = ft.f[3 * i]; last.f[3 * i + 1] = ft.f[3 * i + 1]; last.f[3 * i + 2] = ft.f[3 * i + 2];
-    last.point[i] = p;
-    if (i < last.sia_max_n) {          // the next SparseImgAlign::run walks this frame's features (sparse_img_align.cpp:116-118)
-      last.sia_px[2 * i] = ft.px[2 * i]; last.sia_px[2 * i + 1] = ft.px[2 * i + 1];
-      last.sia_f[3 * i] = ft.f[3 * i]; last.sia_f[3 * i + 1] = ft.f[3 * i + 1]; last.sia_f[3 * i + 2] = ft.f[3 * i + 2];
-      last.sia_pos[3 * i] = ft.pos[3 * i]; last.sia_pos[3 * i + 1] = ft.pos[3 * i + 1]; last.sia_pos[3 * i + 2] = ft.pos[3 * i + 2];
-      last.sia_has_point[i] = p >= 0 ? 1 : 0;
-    }
-  }
-  for (int p = t; p < m.n_points; p += nt) {
-    out_pt_type[p] = m.pt_type[p]; out_pt_failed[p] = m.pt_n_failed[p]; out_pt_succeeded[p] = m.pt_n_succeeded[p];
-  }
-  __syncthreads();
-  if (t == 0) {
-    *last.n = n_feat;
-    FrameConst c;
-    c.cam = cam;
-    for (int i = 0; i < 7; ++i) { const double v = s_Tnew[i]; last.T_f_w[i] = v; c.T_ref_w[i] = v; c.T_cur_w_init[i] = v; }   // :175
-    double Tinv[7];
-    se3_inverse(c.T_ref_w, Tinv);                                            // Frame::pos()
-    c.ref_pos[0] = Tinv[0]; c.ref_pos[1] = Tinv[1]; c.ref_pos[2] = Tinv[2];
-    c.n_feat = n_feat < last.sia_max_n ? n_feat : last.sia_max_n; c.pad = 0;
-    last.sia_fc[0] = c;
-  }
-  // the result block lies in page-locked host memory: once every thread's stores have left for the host, the frame's
-  // sequence number goes after them and the waiting host thread reads the block
-  __threadfence_system();
-  __syncthreads();
-  if (t == 0) __hip_atomic_store(done_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// ---- the kernels of the chain: workgroup c of a launch takes camera c's arguments from a table in device memory (a lone
-// tracker is a group of one; trk_track_all uploads the table when it changes)
-struct TrkCamArgs {
-  TrkMap m;
-  TrkPlan pl;
-  TrkFeat ft;
-  TrkLast last;
-  MdFrame mf;
-  const double* T_slot_w;
-  SeedRec* recs;
-  const FrameState* sia_state;
-  int *cell_winner, *cell_cum;
-  const svo_hip_pose_opt_result* po;
-  char* res;                           // the camera's result block (device address of page-locked memory)
-  size_t o_px, o_f, o_level, o_point, o_edge, o_grad, o_pt, o_flag;
-};
-
-SVO_DEV void trk_plan_args(const TrkCamArgs& a) { trk_plan_body(a.m, a.pl, a.mf, a.T_slot_w, a.recs, a.sia_state); }
-SVO_DEV void trk_replay_args(const TrkCamArgs& a, int max_fts, int quality_min_fts) {
-  trk_replay_body(a.m, a.pl, a.ft, a.mf.cam, a.sia_state, a.recs, a.cell_winner, a.cell_cum, max_fts, quality_min_fts);
-}
-// seq: the frame's sequence number (every camera of the group advances with every call)
-SVO_DEV void trk_finish_args(const TrkCamArgs& a, unsigned long long seq) {
-  char* rd = a.res;
-  int* pt = reinterpret_cast<int*>(rd + a.o_pt);
-  trk_finish_body(a.m, a.pl, a.ft, a.last, a.mf.cam, a.sia_state, a.po, reinterpret_cast<svo_hip_track_result*>(rd),
-                  reinterpret_cast<double*>(rd + a.o_px), reinterpret_cast<double*>(rd + a.o_f), reinterpret_cast<int*>(rd + a.o_level),
-                  reinterpret_cast<int*>(rd + a.o_point), reinterpret_cast<uint8_t*>(rd + a.o_edge), reinterpret_cast<double*>(rd + a.o_grad),
-                  pt, pt + a.m.n_points, pt + 2 * (size_t)a.m.n_points, reinterpret_cast<unsigned long long*>(rd + a.o_flag), seq);
-}
-
-__global__ __launch_bounds__(TRK_THREADS) void trk_plan_cams_kernel(const TrkCamArgs* __restrict__ args) { trk_plan_args(args[blockIdx.x]); }
-__global__ __launch_bounds__(TRK_THREADS) void trk_replay_cams_kernel(const TrkCamArgs* __restrict__ args, int max_fts, int quality_min_fts) {
-  trk_replay_args(args[blockIdx.x], max_fts, quality_min_fts);
-}
-__global__ __launch_bounds__(256) void trk_finish_cams_kernel(const TrkCamArgs* __restrict__ args, unsigned long long seq) {
-  trk_finish_args(args[blockIdx.x], seq);
-}
-// ... and the same for a lone tracker with its one entry passed by value, not uploaded: the pointers inside a by-value kernel
-// argument address global memory by the ABI, those read from the table are generic pointers, and every memory access of the
-// bodies becomes a flat instruction (measured: the lone chain 3 us a frame slower through the table kernels)
-__global__ __launch_bounds__(TRK_THREADS) void trk_plan_one_kernel(TrkCamArgs a) { trk_plan_args(a); }
-__global__ __launch_bounds__(TRK_THREADS) void trk_replay_one_kernel(TrkCamArgs a, int max_fts, int quality_min_fts) {
-  trk_replay_args(a, max_fts, quality_min_fts);
-}
-__global__ __launch_bounds__(256) void trk_finish_one_kernel(TrkCamArgs a, unsigned long long seq) { trk_finish_args(a, seq); }
-
-// svo_hip_tracker_group_finish_frames: workgroup c finishes camera c's frame.  The tables come from the chain's argument table, what
-// changes with every call from a page-locked array the kernel reads directly (a camera that sits out: active == 0).
-struct TrkFinishReq {
-  TrkStructSel sel;
-  int n_iter, active, overlap_valid, pad;
-  char* st;                            // the camera's page-locked block (device address)
-  unsigned long long seq;
-};
-__global__ __launch_bounds__(FIN_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) void trk_finish_frames_cams_kernel(const TrkCamArgs* __restrict__ args, const TrkFinishReq* __restrict__ req,
-                                                                             double min_dist) {
-  // the request crosses the link once, into LDS (the structure step compares every feature of the last frame with the selection)
-  static_assert(sizeof(TrkFinishReq) % 4 == 0 && sizeof(TrkFinishReq) / 4 <= FIN_THREADS, "one word per thread");
-  __shared__ TrkFinishReq s_req;
-  if (threadIdx.x < sizeof(TrkFinishReq) / 4)
-    reinterpret_cast<unsigned*>(&s_req)[threadIdx.x] = reinterpret_cast<const unsigned*>(req + blockIdx.x)[threadIdx.x];
-  __syncthreads();
-  const TrkFinishReq& r = s_req;
-  if (!r.active) return;                                                       // block-uniform
-  const TrkCamArgs& a = args[blockIdx.x];
-  trk_finish_frame_body(a.m, const_cast<double*>(a.m.pt_pos), a.last, r.sel, r.n_iter, a.pl.overlap_kf, a.pl.counters, r.overlap_valid, min_dist,
-                        r.st, r.seq);
-}
-
-// Point::pos_ of n points after the host optimised them: one staged block in, one launch
-__global__ void trk_scatter_positions_kernel(int n, const int* __restrict__ idx, const double* __restrict__ pos, double* __restrict__ pt_pos) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const size_t p = (size_t)idx[i];
-  pt_pos[3 * p] = pos[3 * i]; pt_pos[3 * p + 1] = pos[3 * i + 1]; pt_pos[3 * p + 2] = pos[3 * i + 2];
-}
-
-// ---- relocalisation: Map::getClosestKeyframe (S/map.cpp:109-151) and last_frame_ = ref_keyframe
-// (FrameHandlerMono::relocalizeFrame, S/frame_handler_mono.cpp:337) on the tables.  One workgroup of RELOC_THREADS.
-//   choose: every keyframe one of whose key points is visible from T is close (the first visible one decides), its distance is
-//           (T.translation_vec() - T_kf_w.translation_vec()).norm(); the answer is the close keyframe other than `exclude` with the
-//           smallest distance, the lower index on a tie (std::list::sort is stable over keyframes_ order).  Otherwise kf is given.
-//   apply:  the last frame becomes that keyframe when it exists and its features fit: pose = row kf of T_kf_w; features = the
-//           entries of its feature row whose point is living and observed in it, in row order, with the px / f of the point's first
-//           observation there.  Counted first, written only when the count fits (a refused call changes nothing).  The solver's
-//           slot gets the same features with T_ref_w = the keyframe's pose and T_cur_w_init = T (gate) or the keyframe's pose.
-// T: the pose of the device's last frame (use_last_pose; read before anything is written) or the one passed by value.
-constexpr int RELOC_THREADS = 256;
-struct TrkRelocArgs {
-  int kf, exclude, choose, apply, gate, use_last_pose, max_feat, pad;
-  double T[7];
-};
-struct TrkRelocOut {
-  double distance;               // of the chosen keyframe (choose)
-  int kf;                        // the keyframe, -1: none
-  int n_close;                   // close keyframes before the exclusion (choose)
-  int n_feat;                    // its features (apply), -1: not counted
-  int applied;                   // 1: the last frame is the keyframe now
-  int max_point;                 // largest point index among the features, -1: none
-  int pad;
-};
-__global__ __launch_bounds__(RELOC_THREADS) void trk_reloc_kernel(TrkMap m, TrkLast last, Cam cam, TrkRelocArgs a, TrkRelocOut* __restrict__ out) {
-  static_assert(TRK_LDS_KF <= RELOC_THREADS, "one keyframe per thread");
-  __shared__ double s_T[7], s_dist[TRK_LDS_KF];
-  __shared__ int s_close[TRK_LDS_KF], s_wave[RELOC_THREADS / 64];
-  __shared__ int s_kf, s_n_close, s_count, s_max_point;
-  const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6;
-  if (t < 7) s_T[t] = a.use_last_pose ? last.T_f_w[t] : a.T[t];
-  if (t == 0) { s_kf = a.kf; s_n_close = 0; s_count = 0; s_max_point = -1; }
-  __syncthreads();
-  double T[7];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) T[i] = s_T[i];
-  if (a.choose) {                                                              // block-uniform
-    for (int k = t; k < m.n_kf; k += nt) {
-      int kp[5];
-#pragma unroll
-      for (int j = 0; j < 5; ++j) kp[j] = m.kf_key_point[5 * k + j];
-      bool close = false;
-#pragma unroll
-      for (int j = 0; j < 5; ++j)
-        if (!close && kp[j] >= 0) close = frame_is_visible(cam, T, m.pt_pos + 3 * (size_t)kp[j]);
-      const double* tk = m.T_kf_w + 7 * (size_t)k;
-      const double dx = T[0] - tk[0], dy = T[1] - tk[1], dz = T[2] - tk[2];
-      s_close[k] = close ? 1 : 0;
-      s_dist[k] = sqrt(dx * dx + dy * dy + dz * dz);
-    }
-    __syncthreads();
-    if (t == 0) {                                                              // at most TRK_LDS_KF keyframes: one walk in index order
-      int best = -1, n_close = 0;
-      for (int k = 0; k < m.n_kf; ++k) {
-        if (!s_close[k]) continue;
-        ++n_close;
-        if (k != a.exclude && (best < 0 || s_dist[k] < s_dist[best])) best = k;
-      }
-      s_kf = best; s_n_close = n_close;
-    }
-    __syncthreads();
-  }
-  const int k = s_kf;
-  int n_feat = -1;
-  bool apply = false;
-  if (a.apply && k >= 0) {                                                     // block-uniform
-    const int r0 = m.kf_ftr_offset[k], r1 = m.kf_ftr_offset[k + 1];
-    // the point's first observation in keyframe k (-1: none, or the point is not living)
-    auto obs_in_kf = [&](int i) {
-      const int p = m.kf_ftr_point[i];
-      if (p < 0 || m.pt_unlinked[p]) return -1;
-      for (int o = m.pt_obs_offset[p]; o < m.pt_obs_offset[p + 1]; ++o)
-        if (m.obs_kf[o] == k) return o;
-      return -1;
-    };
-    int mine = 0;
-    for (int i = r0 + t; i < r1; i += nt) mine += obs_in_kf(i) >= 0 ? 1 : 0;
-    if (mine) atomicAdd(&s_count, mine);
-    __syncthreads();
-    n_feat = s_count;
-    apply = n_feat <= a.max_feat;
-    if (apply) {
-      // ordered compaction of the row, a chunk of the workgroup's size at a time: ranks inside a wave from the ballot, across
-      // the waves through LDS, across the chunks in `base`
-      int base = 0;
-      for (int c0 = r0; c0 < r1; c0 += nt) {                                   // block-uniform
-        const int i = c0 + t;
-        const int o = i < r1 ? obs_in_kf(i) : -1;
-        const unsigned long long bal = __ballot(o >= 0);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < RELOC_THREADS / 64; ++w) { const int c = s_wave[w]; before += w < wave ? c : 0; total += c; }
-        if (o >= 0) {
-          const int r = base + before + __popcll(bal & ((1ull << lane) - 1ull));
-          const int p = m.kf_ftr_point[i];
-          const double x = m.obs_px[2 * (size_t)o], y = m.obs_px[2 * (size_t)o + 1];
-          const double f0 = m.obs_f[3 * (size_t)o], f1 = m.obs_f[3 * (size_t)o + 1], f2 = m.obs_f[3 * (size_t)o + 2];
-          last.px[2 * r] = x; last.px[2 * r + 1] = y;
-          last.f[3 * r] = f0; last.f[3 * r + 1] = f1; last.f[3 * r + 2] = f2;
-          last.point[r] = p;
-          if (r < last.sia_max_n) {
-            last.sia_px[2 * r] = x; last.sia_px[2 * r + 1] = y;
-            last.sia_f[3 * r] = f0; last.sia_f[3 * r + 1] = f1; last.sia_f[3 * r + 2] = f2;
-            last.sia_pos[3 * r] = m.pt_pos[3 * (size_t)p]; last.sia_pos[3 * r + 1] = m.pt_pos[3 * (size_t)p + 1];
-            last.sia_pos[3 * r + 2] = m.pt_pos[3 * (size_t)p + 2];
-            last.sia_has_point[r] = 1;
-          }
-          atomicMax(&s_max_point, p);
-        }
-        base += total;
-        __syncthreads();                                                       // (s_wave is rewritten by the next chunk)
-      }
-      if (t == 0) {
-        *last.n = n_feat;
-        FrameConst c;
-        c.cam = cam;
-        const double* tk = m.T_kf_w + 7 * (size_t)k;
-        for (int i = 0; i < 7; ++i) { const double v = tk[i]; last.T_f_w[i] = v; c.T_ref_w[i] = v; c.T_cur_w_init[i] = a.gate ? T[i] : v; }
-        double Tinv[7];
-        se3_inverse(c.T_ref_w, Tinv);                                          // Frame::pos()
-        c.ref_pos[0] = Tinv[0]; c.ref_pos[1] = Tinv[1]; c.ref_pos[2] = Tinv[2];
-        c.n_feat = n_feat < last.sia_max_n ? n_feat : last.sia_max_n; c.pad = 0;
-        last.sia_fc[0] = c;
-      }
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    TrkRelocOut r;
-    r.distance = a.choose && k >= 0 ? s_dist[k] : 0.0;
-    r.kf = k; r.n_close = s_n_close; r.n_feat = n_feat; r.applied = apply ? 1 : 0; r.max_point = s_max_point; r.pad = 0;
-    *out = r;
-  }
-}
 
 // device memory for count elements, recorded in got (whose owner frees it); a no-op once *rc holds an error
 template <typename T>
@@ -1510,6 +49,25 @@ void trk_alloc(svo_hip_ctx* ctx, std::vector<void*>* got, int* rc, T** p, size_t
   *rc = svo_hip_malloc(ctx, &d, (count ? count : 1) * sizeof(T));
   *p = (T*)d;
   if (*rc == SVO_HIP_OK) got->push_back(d);
+}
+
+// The one wait of a call: every listed flag (page-locked memory, a kernel's last store) shows its sequence number.  A spin on host
+// memory (no driver call on the way back; a few hundred milliseconds at most), then the stream's own synchronisation and the check.
+struct TrkFlagWait { const char* flag; unsigned long long seq; };
+int trk_wait_flags(svo_hip_ctx* ctx, const TrkFlagWait* w, int n, const char* who, const char* what) {
+  auto done = [&](int k) {
+    return __atomic_load_n(reinterpret_cast<const volatile unsigned long long*>(w[k].flag), __ATOMIC_ACQUIRE) == w[k].seq;
+  };
+  bool all = false;
+  for (long spins = 0; spins < 4000000L && !all; ++spins) {
+    all = true;
+    for (int k = 0; k < n && all; ++k) all = done(k);
+    if (!all) __builtin_ia32_pause();
+  }
+  if (!all) SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < n; ++k)
+    if (!done(k)) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, what);
+  return SVO_HIP_OK;
 }
 
 }  // namespace
@@ -1543,6 +101,7 @@ struct svo_hip_tracker_shared {
   TrkFinishReq* fin_dev = nullptr;
   unsigned long long seq = 0;               // frames tracked: the hand-over kernel stores it behind every camera's block (o_flag)
   std::vector<svo_hip_tracker*> members;
+  std::vector<TrkFlagWait> waits;           // [n_cams] the flags a call waits for (no allocation per frame)
   std::vector<void*> dev_allocs;
 };
 
@@ -1567,21 +126,61 @@ struct svo_hip_tracker {
   int n_kf = 0, n_points = 0, n_candidates = 0;
   int n_ftr = 0, n_obs = 0;                 // entries of kf_ftr_point / of the observation tables
   std::vector<int> kf_slot_host;            // kf_slot as the device holds it (svo_hip_tracker_promote_last_frame checks against it)
-  int track_n_points = 0;                   // n_points when the last frame was tracked: the layout of the counters in the result block
-  bool have_map = false, have_last = false;
-  bool overlap_valid = false;               // pl.overlap_kf / counters[3] are the last frame's and still name keyframes of the map (svo_hip_tracker_finish_frame)
-  bool rekey_pending = false;               // the last frame deleted points: keyframes that lost a key feature choose again before the next frame
-  int last_n_host = 0;
-  int last_max_point = -1;                  // largest map point index the last frame's features refer to (set_last_frame input)
-  bool last_from_track = false;             // ... or: the last frame is the previous call's new frame, its features are in the result block
-  bool last_renumbered = false;             // ... whose point indices a compaction has outdated since: last_max_point holds the bound again
+  bool have_map = false;
+  bool any_edgelet = false;                 // the map holds EDGELET reference features (align1D stage needed)
   // plan / replay scratch
   TrkPlan pl{};
   TrkFeat ft{};
   TrkLast last{};
   int *cell_winner = nullptr, *cell_cum = nullptr;
-  bool need_gather = true;                  // the solver's slot 0 does not hold the last frame yet (a host upload came in between)
-  bool any_edgelet = false;                 // the map holds EDGELET reference features (align1D stage needed)
+
+  // ---- What the host knows about the device's last frame.  Entry points read these fields; only the transitions below, each named
+  // after what happened, write them (behind every field: the transitions that set it / that clear it).
+  bool have_last = false;        // the device holds a last frame whose point indices fit the map.  host_set_last; map_accepted may clear it
+  int last_n_host = 0;           // its number of features.  host_set_last, frame_tracked
+  bool last_from_track = false;  // it is the previous call's new frame, its features are in the result block.  frame_tracked / host_set_last
+  bool last_renumbered = false;  // ... under the numbering a compaction has replaced since.  points_renumbered; cleared with last_from_track
+  int last_max_point = -1;       // largest map point it refers to where the block does not say it (last_point_bound).  host_set_last, points_renumbered
+  int track_n_points = 0;        // n_points when it was tracked: the layout of the counters in the result block.  frame_tracked
+  bool need_gather = true;       // the solver's slot holds something else.  host_set_last, map_replaced, positions_changed, call_failed / frame_tracked
+  bool overlap_valid = false;    // pl.overlap_kf / counters[3] are the last frame's and still name keyframes of the map (the keyframe decision).
+                                 // frame_tracked / frame_begins, host_set_last, map_replaced, keyframes_renumbered
+  bool rekey_pending = false;    // deleted points took key features along: the keyframes choose again before the tables are read.
+                                 // frame_tracked, keyframes_renumbered / rekeyed (trk_rekey_now), map_replaced
+  // the host gave the last frame, or made it from a keyframe: n features, none above map point max_point
+  void host_set_last(int n, int max_point) {
+    have_last = true; last_n_host = n; last_max_point = max_point; last_from_track = false; last_renumbered = false;
+    need_gather = true; overlap_valid = false;
+  }
+  void gate_refused() { host_set_last(0, -1); }    // a relocalisation's gate turned the keyframe down: the new image, no features
+  void frame_begins() { overlap_valid = false; }   // a chain is being enqueued: its plan rewrites the overlap list
+  // the chain has completed: the new frame is the last one, the hand-over kernel has written the solver's slot
+  void frame_tracked(const svo_hip_track_result& r) {
+    last_n_host = r.n_features; track_n_points = n_points; last_from_track = true; last_renumbered = false;
+    need_gather = false; overlap_valid = true;
+    if (r.map_changed) rekey_pending = true;
+  }
+  // largest map point the last frame refers to: from the features of a tracked frame while their numbering holds
+  int last_point_bound() const {
+    if (!last_from_track || last_renumbered) return last_max_point;
+    const int32_t* fp = reinterpret_cast<const int32_t*>(res_host + o_point);
+    int max_point = -1;
+    for (int i = 0; i < last_n_host; ++i) if (fp[i] > max_point) max_point = fp[i];
+    return max_point;
+  }
+  // svo_hip_tracker_set_map, before its uploads: the last frame's features keep referring to map points by index, so a map with
+  // fewer points than the largest of them needs svo_hip_tracker_set_last_frame again ...
+  void map_accepted(int n_points_new) { if (have_last && last_point_bound() >= n_points_new) have_last = false; }
+  // ... and behind them: the keyframes may be others now, point positions may have changed
+  void map_replaced() { need_gather = true; overlap_valid = false; rekey_pending = false; }
+  // a compaction: the device's last frame follows the new numbering; the result block (and track_n_points, its layout) keeps the old
+  void points_renumbered(int max_point) { last_max_point = max_point; last_renumbered = last_from_track; }
+  // a promotion (the frame is a keyframe of the map now) or a removal, which may delete points
+  void keyframes_renumbered(bool points_deleted) { overlap_valid = false; if (points_deleted) rekey_pending = true; }
+  void positions_changed() { need_gather = true; }   // the host wrote point positions: the solver's copy of the last frame's is stale
+  void call_failed() { need_gather = true; }         // a relocalisation failed midway: whatever the slot holds is gathered again
+  void rekeyed() { rekey_pending = false; }
+  // the other per-camera objects
   svo_hip_pose_opt_result* po = nullptr;    // (its entry of the shared array)
   TrkRelocOut* reloc_out = nullptr;         // what trk_reloc_kernel reports
   // result block: [svo_hip_track_result][px][f][level][point][edgelet][grad][pt_type][pt_failed][pt_succeeded]
@@ -1634,7 +233,34 @@ int trk_rekey_now(svo_hip_tracker* t) {
     hipLaunchKernelGGL(trk_rekey_kernel, dim3(t->n_kf), dim3(KEY_THREADS), 0, ctx->stream, make_map(t), t->kf_key_point, svo_make_cam(t->cam));
     SVO_CHECK_HIP(ctx, hipGetLastError());
   }
-  t->rekey_pending = false;
+  t->rekeyed();
+  return SVO_HIP_OK;
+}
+
+// SparseImgAlign(kltMaxLevel, kltMinLevel, 30, GaussNewton, false, false) (frame_handler_mono.cpp:186-187, :329-330)
+svo_hip_sia_params trk_sia_params(const svo_hip_tracker_config& c) {
+  svo_hip_sia_params sp;
+  sp.max_level = c.klt_max_level; sp.min_level = c.klt_min_level; sp.n_iter = c.sia_n_iter; sp.eps = c.sia_eps; sp.early_stop = 1;
+  return sp;
+}
+
+// the slot of the shared keyframe pyramids that holds this camera's keyframe slot
+int trk_kf_slot(const svo_hip_tracker* t, int slot) { return t->cam_index * t->cfg.max_keyframes + slot; }
+
+// the last frame's pyramid becomes a copy of that keyframe slot's
+int trk_last_pyramid_from_keyframe(svo_hip_tracker* t, int slot) {
+  svo_hip_pyramid* dst = t->sh->frame_pyr[t->sh->last_idx];
+  const svo_hip_pyramid* kf = t->sh->kf_pyr;
+  return svo_hip_copy_d2d(t->ctx, dst->base + (size_t)t->cam_index * dst->pyr_bytes, kf->base + (size_t)trk_kf_slot(t, slot) * kf->pyr_bytes,
+                          dst->pyr_bytes);
+}
+
+// the context's two staging areas at `bytes`, free to be filled: the stream is through with whatever it still read from them
+int trk_stage_upload(svo_hip_ctx* ctx, size_t bytes, char** dev, char** host) {
+  int rc = svo_ctx_staging(ctx, bytes, dev);
+  if (rc == SVO_HIP_OK) rc = svo_ctx_host_staging(ctx, bytes, host);
+  if (rc != SVO_HIP_OK) return rc;
+  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SVO_HIP_OK;
 }
 
@@ -1763,7 +389,7 @@ static int trk_shared_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const 
   D(&sh->args_dev, N);
   if (rc == SVO_HIP_OK && hipHostMalloc((void**)&sh->fin_host, N * sizeof(TrkFinishReq), hipHostMallocMapped) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
   if (rc == SVO_HIP_OK && hipHostGetDevicePointer((void**)&sh->fin_dev, sh->fin_host, 0) != hipSuccess) rc = SVO_HIP_ERR_DEVICE;
-  if (rc == SVO_HIP_OK) sh->args_next.resize(N);
+  if (rc == SVO_HIP_OK) { sh->args_next.resize(N); sh->waits.resize(N); }
   if (rc != SVO_HIP_OK) { trk_shared_destroy(sh); return rc; }
   *out = sh;
   return SVO_HIP_OK;
@@ -1813,9 +439,8 @@ static int trk_member_create(svo_hip_tracker_shared* sh, int index, const svo_hi
   if (rc == SVO_HIP_OK) memset(t->res_host, 0, t->res_bytes);
   t->img_host = sh->img_host + sh->img_stride * (size_t)index;
   t->img_dev = sh->img_dev + sh->img_stride * (size_t)index;
-  const size_t st_bytes = ST_BYTES;
-  if (rc == SVO_HIP_OK && hipHostMalloc((void**)&t->st_host, st_bytes, hipHostMallocMapped) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
-  if (rc == SVO_HIP_OK) memset(t->st_host, 0, st_bytes);
+  if (rc == SVO_HIP_OK && hipHostMalloc((void**)&t->st_host, ST_BYTES, hipHostMallocMapped) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
+  if (rc == SVO_HIP_OK) memset(t->st_host, 0, ST_BYTES);
   if (rc == SVO_HIP_OK && hipHostGetDevicePointer((void**)&t->st_dev, t->st_host, 0) != hipSuccess) rc = SVO_HIP_ERR_DEVICE;
   // staging area of svo_hip_tracker_set_map: every table at its capacity (T_kf_w and T_slot_w: two pose tables), 16 bytes of
   // alignment slack per table
@@ -1848,7 +473,7 @@ int svo_hip_tracker_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const sv
 int svo_hip_tracker_upload_keyframe(svo_hip_tracker* t, int slot, const uint8_t* level0) {
   if (!t || !level0) return SVO_HIP_ERR_INVALID;
   SVO_REQUIRE(t->ctx, slot >= 0 && slot < t->cfg.max_keyframes);
-  return svo_hip_pyramid_upload_level0_and_build(t->sh->kf_pyr, t->cam_index * t->cfg.max_keyframes + slot, level0);
+  return svo_hip_pyramid_upload_level0_and_build(t->sh->kf_pyr, trk_kf_slot(t, slot), level0);
 }
 
 int svo_hip_tracker_keyframe_from_last_frame(svo_hip_tracker* t, int slot) {
@@ -1858,8 +483,8 @@ int svo_hip_tracker_keyframe_from_last_frame(svo_hip_tracker* t, int slot) {
   if (!t->have_last) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_keyframe_from_last_frame", "no frame has been tracked or set yet");
   const svo_hip_pyramid* src = t->sh->frame_pyr[t->sh->last_idx];
   const svo_hip_pyramid* kf = t->sh->kf_pyr;
-  return svo_hip_copy_d2d(ctx, kf->base + ((size_t)t->cam_index * t->cfg.max_keyframes + slot) * kf->pyr_bytes,
-                          src->base + (size_t)t->cam_index * src->pyr_bytes, src->pyr_bytes);
+  return svo_hip_copy_d2d(ctx, kf->base + (size_t)trk_kf_slot(t, slot) * kf->pyr_bytes, src->base + (size_t)t->cam_index * src->pyr_bytes,
+                          src->pyr_bytes);
 }
 
 int svo_hip_tracker_set_map(svo_hip_tracker* t, const svo_hip_tracker_map* mp) {
@@ -1885,38 +510,22 @@ int svo_hip_tracker_set_map(svo_hip_tracker* t, const svo_hip_tracker_map* mp) {
   for (int p = 0; p < mp->n_points; ++p) SVO_REQUIRE(ctx, mp->pt_obs_offset[p] >= 0 && mp->pt_obs_offset[p] <= mp->pt_obs_offset[p + 1] && mp->pt_type[p] >= 0 && mp->pt_type[p] <= 3);
   for (int o = 0; o < n_obs; ++o) SVO_REQUIRE(ctx, mp->obs_kf[o] >= 0 && mp->obs_kf[o] < mp->n_kf && mp->obs_level[o] >= 0 && mp->obs_level[o] < c.n_levels);
   for (int i = 0; i < mp->n_candidates; ++i) SVO_REQUIRE(ctx, mp->cand_point[i] >= -1 && mp->cand_point[i] < mp->n_points);
-  {
-    // what the tables below take in the staging area (each starts on a 16-byte boundary): checked before anything is written
-    const size_t K_ = (size_t)mp->n_kf, P_ = (size_t)mp->n_points, O_ = (size_t)n_obs;
-    const size_t need = K_ * (56 + 4 + 20) + (K_ + 1) * 4 + (size_t)n_ftr * 4 + P_ * (24 + 12) + (P_ + 1) * 4 + O_ * (4 + 16 + 24 + 4 + 1 + 16) +
-                        (size_t)mp->n_candidates * 4 + (size_t)c.max_keyframes * 56 + 32 * 16;
-    if (need > t->map_host_bytes) return svo_fail(ctx, SVO_HIP_ERR_NOMEM, "svo_hip_tracker_set_map", "staging area too small");
-  }
-  if (t->have_last) {                       // (after the checks: a refused map changes nothing)
-    // the last frame's features keep referring to map points by index: a map with fewer points than the largest of them
-    // needs svo_hip_tracker_set_last_frame again (the result block still holds the features of a tracked frame)
-    int max_point = t->last_max_point;
-    if (t->last_from_track && !t->last_renumbered) {
-      const int32_t* fp = reinterpret_cast<const int32_t*>(t->res_host + t->o_point);
-      max_point = -1;
-      for (int i = 0; i < t->last_n_host; ++i) if (fp[i] > max_point) max_point = fp[i];
-    }
-    if (max_point >= mp->n_points) t->have_last = false;     // svo_hip_tracker_track will ask for svo_hip_tracker_set_last_frame
-  }
+  // what the tables below take in the staging area (each starts on a 16-byte boundary): checked before anything is written
+  const size_t K = mp->n_kf, P = mp->n_points, O = (size_t)n_obs;
+  const size_t need = K * (56 + 4 + 20) + (K + 1) * 4 + (size_t)n_ftr * 4 + P * (24 + 12) + (P + 1) * 4 + O * (4 + 16 + 24 + 4 + 1 + 16) +
+                      (size_t)mp->n_candidates * 4 + (size_t)c.max_keyframes * 56 + 32 * 16;
+  if (need > t->map_host_bytes) return svo_fail(ctx, SVO_HIP_ERR_NOMEM, "svo_hip_tracker_set_map", "staging area too small");
+  t->map_accepted(mp->n_points);            // (after the checks: a refused map changes nothing)
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
   // the staging area may still feed the copies of the previous upload
   SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   char* hs = t->map_host;
   size_t off = 0;
   hipError_t e = hipSuccess;
-  auto put = [&](void* dst, const void* src, size_t bytes) {
-    if (!bytes || e != hipSuccess) return;
-    off = (off + 15) & ~(size_t)15;
-    memcpy(hs + off, src, bytes);
-    e = hipMemcpyAsync(dst, hs + off, bytes, hipMemcpyHostToDevice, ctx->stream);
-    off += bytes;
-  };
-  const size_t K = mp->n_kf, P = mp->n_points;
+  // the next `bytes` of the staging area (on a 16-byte boundary) to be filled, then sent
+  auto stage = [&](size_t bytes) { off = (off + 15) & ~(size_t)15; char* p = hs + off; off += bytes; return p; };
+  auto send = [&](void* dst, const void* p, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, ctx->stream); };
+  auto put = [&](void* dst, const void* src, size_t bytes) { if (bytes) { char* p = stage(bytes); memcpy(p, src, bytes); send(dst, p, bytes); } };
   const TrkTables& tb = t->tables[t->cur];
   put(t->T_kf_w, mp->T_kf_w, K * 56); put(t->kf_slot, mp->kf_slot, K * 4); put(t->kf_key_point, mp->kf_key_point, K * 20);
   if (K) put(tb.kf_ftr_offset, mp->kf_ftr_offset, (K + 1) * 4);
@@ -1928,27 +537,19 @@ int svo_hip_tracker_set_map(svo_hip_tracker* t, const svo_hip_tracker_map* mp) {
   put(tb.obs_level, mp->obs_level, (size_t)n_obs * 4);
   put(tb.cand_point, mp->cand_point, (size_t)mp->n_candidates * 4);
   // T_slot_w: the keyframe poses indexed by pyramid slot (what the matcher's batch indexes)
-  {
-    off = (off + 15) & ~(size_t)15;
-    double* ts = reinterpret_cast<double*>(hs + off);
-    memset(ts, 0, (size_t)c.max_keyframes * 56);
-    for (int s = 0; s < c.max_keyframes; ++s) ts[7 * s + 6] = 1.0;
-    for (int k = 0; k < mp->n_kf; ++k) memcpy(ts + 7 * (size_t)mp->kf_slot[k], mp->T_kf_w + 7 * (size_t)k, 56);
-    if (e == hipSuccess) e = hipMemcpyAsync(t->T_slot_w, ts, (size_t)c.max_keyframes * 56, hipMemcpyHostToDevice, ctx->stream);
-    off += (size_t)c.max_keyframes * 56;
-  }
+  double* ts = reinterpret_cast<double*>(stage((size_t)c.max_keyframes * 56));
+  memset(ts, 0, (size_t)c.max_keyframes * 56);
+  for (int s = 0; s < c.max_keyframes; ++s) ts[7 * s + 6] = 1.0;
+  for (int k = 0; k < mp->n_kf; ++k) memcpy(ts + 7 * (size_t)mp->kf_slot[k], mp->T_kf_w + 7 * (size_t)k, 56);
+  send(t->T_slot_w, ts, (size_t)c.max_keyframes * 56);
   if (n_obs) {
-    off = (off + 15) & ~(size_t)15;
-    uint8_t* ed = reinterpret_cast<uint8_t*>(hs + off);
+    uint8_t* ed = reinterpret_cast<uint8_t*>(stage((size_t)n_obs));
     if (mp->obs_edgelet) memcpy(ed, mp->obs_edgelet, (size_t)n_obs); else memset(ed, 0, (size_t)n_obs);
-    if (e == hipSuccess) e = hipMemcpyAsync(tb.obs_edgelet, ed, (size_t)n_obs, hipMemcpyHostToDevice, ctx->stream);
-    off += (size_t)n_obs;
-    off = (off + 15) & ~(size_t)15;
-    double* gr = reinterpret_cast<double*>(hs + off);
+    send(tb.obs_edgelet, ed, (size_t)n_obs);
+    double* gr = reinterpret_cast<double*>(stage((size_t)n_obs * 16));
     if (mp->obs_grad) memcpy(gr, mp->obs_grad, (size_t)n_obs * 16);
     else for (int o = 0; o < n_obs; ++o) { gr[2 * o] = 1.0; gr[2 * o + 1] = 0.0; }
-    if (e == hipSuccess) e = hipMemcpyAsync(tb.obs_grad, gr, (size_t)n_obs * 16, hipMemcpyHostToDevice, ctx->stream);
-    off += (size_t)n_obs * 16;
+    send(tb.obs_grad, gr, (size_t)n_obs * 16);
   }
   if (e == hipSuccess && P) e = hipMemsetAsync(t->pt_unlinked, 0, P, ctx->stream);
   if (e != hipSuccess) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, "svo_hip_tracker_set_map", hipGetErrorString(e));
@@ -1957,9 +558,8 @@ int svo_hip_tracker_set_map(svo_hip_tracker* t, const svo_hip_tracker_map* mp) {
   t->kf_slot_host.assign(mp->kf_slot, mp->kf_slot + mp->n_kf);
   t->any_edgelet = false;
   if (mp->obs_edgelet) for (int o = 0; o < n_obs && !t->any_edgelet; ++o) t->any_edgelet = mp->obs_edgelet[o] != 0;
-  t->have_map = true; t->rekey_pending = false;
-  t->overlap_valid = false;                 // the keyframes may be others now
-  t->need_gather = true;                    // point positions may have changed
+  t->have_map = true;
+  t->map_replaced();
   return SVO_HIP_OK;
 }
 
@@ -1974,55 +574,15 @@ int svo_hip_tracker_update_point_positions(svo_hip_tracker* t, int n, const int3
   const size_t o_idx = (size_t)n * 24, bytes = o_idx + (size_t)n * 4;
   char* d = nullptr;
   char* hs = nullptr;
-  int rc = svo_ctx_staging(ctx, bytes, &d);
-  if (rc == SVO_HIP_OK) rc = svo_ctx_host_staging(ctx, bytes, &hs);
+  const int rc = trk_stage_upload(ctx, bytes, &d, &hs);
   if (rc != SVO_HIP_OK) return rc;
-  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the staging area may still feed an earlier transfer
   memcpy(hs, pos, (size_t)n * 24);
   memcpy(hs + o_idx, point, (size_t)n * 4);
   SVO_CHECK_HIP(ctx, hipMemcpyAsync(d, hs, bytes, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(trk_scatter_positions_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, reinterpret_cast<const int*>(d + o_idx),
                      reinterpret_cast<const double*>(d), t->pt_pos);
   SVO_CHECK_HIP(ctx, hipGetLastError());
-  t->need_gather = true;                    // the solver's copy of the last frame's point positions is stale
-  return SVO_HIP_OK;
-}
-
-int svo_hip_tracker_optimize_structure(svo_hip_tracker* t, int n, const int32_t* point, int n_iter, double* pos_out, int32_t* iters_out) {
-  if (!t) return SVO_HIP_ERR_INVALID;
-  svo_hip_ctx* ctx = t->ctx;
-  SVO_REQUIRE(ctx, n >= 0 && n <= TRK_MAX_STRUCT && n_iter >= 0 && (n == 0 || (point && pos_out)));
-  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_optimize_structure", "no map has been set");
-  if (n == 0) return SVO_HIP_OK;
-  TrkStructSel sel;
-  memset(&sel, 0, sizeof(sel));
-  sel.n = n;
-  for (int i = 0; i < n; ++i) {
-    SVO_REQUIRE(ctx, point[i] >= 0 && point[i] < t->n_points);
-    for (int j = 0; j < i; ++j) SVO_REQUIRE(ctx, point[j] != point[i]);         // a point is optimised once per call
-    sel.point[i] = point[i];
-  }
-  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t o_it = TRK_MAX_STRUCT * 24, o_flag = o_it + TRK_MAX_STRUCT * 4;
-  const unsigned long long seq = ++t->st_seq;
-  hipLaunchKernelGGL(trk_structure_kernel, dim3(1), dim3(256), 0, ctx->stream, make_map(t), t->pt_pos, t->last, sel, n_iter,
-                     reinterpret_cast<double*>(t->st_dev), reinterpret_cast<int*>(t->st_dev + o_it),
-                     reinterpret_cast<unsigned long long*>(t->st_dev + o_flag), seq);
-  SVO_CHECK_HIP(ctx, hipGetLastError());
-  {
-    volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(t->st_host + o_flag);
-    bool seen = false;
-    for (long spins = 0; spins < 4000000L; ++spins) {
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) { seen = true; break; }
-      __builtin_ia32_pause();
-    }
-    if (!seen) SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
-      return svo_fail(ctx, SVO_HIP_ERR_DEVICE, "svo_hip_tracker_optimize_structure", "the kernel did not complete");
-  }
-  memcpy(pos_out, t->st_host, (size_t)n * 24);
-  if (iters_out) memcpy(iters_out, t->st_host + o_it, (size_t)n * 4);
-  // (the point table and the solver's copy of the last frame's points were updated by the kernel: nothing to gather)
+  t->positions_changed();
   return SVO_HIP_OK;
 }
 
@@ -2037,12 +597,8 @@ int svo_hip_tracker_set_last_frame(svo_hip_tracker* t, const uint8_t* level0, in
     SVO_REQUIRE(ctx, point[i] >= -1 && point[i] < (t->have_map ? t->n_points : 0));
     if (point[i] > max_point) max_point = point[i];
   }
-  svo_hip_pyramid* dst = t->sh->frame_pyr[t->sh->last_idx];
-  const svo_hip_pyramid* kf = t->sh->kf_pyr;
-  int rc;
-  if (level0) rc = svo_hip_pyramid_upload_level0_and_build(dst, t->cam_index, level0);
-  else rc = svo_hip_copy_d2d(ctx, dst->base + (size_t)t->cam_index * dst->pyr_bytes,
-                             kf->base + ((size_t)t->cam_index * t->cfg.max_keyframes + kf_slot) * kf->pyr_bytes, dst->pyr_bytes);
+  const int rc = level0 ? svo_hip_pyramid_upload_level0_and_build(t->sh->frame_pyr[t->sh->last_idx], t->cam_index, level0)
+                        : trk_last_pyramid_from_keyframe(t, kf_slot);
   if (rc != SVO_HIP_OK) return rc;
   const int32_t n32 = n;
   SVO_CHECK_HIP(ctx, hipMemcpyAsync(t->last.n, &n32, 4, hipMemcpyHostToDevice, ctx->stream));
@@ -2052,13 +608,7 @@ int svo_hip_tracker_set_last_frame(svo_hip_tracker* t, const uint8_t* level0, in
     SVO_CHECK_HIP(ctx, hipMemcpyAsync(t->last.f, f, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
     SVO_CHECK_HIP(ctx, hipMemcpyAsync(t->last.point, point, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
   }
-  t->last_n_host = n;
-  t->last_max_point = max_point;
-  t->last_from_track = false;
-  t->last_renumbered = false;
-  t->have_last = true;
-  t->overlap_valid = false;
-  t->need_gather = true;
+  t->host_set_last(n, max_point);
   return SVO_HIP_OK;
 }
 
@@ -2134,7 +684,7 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
       return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "svo_hip_tracker_set_map and svo_hip_tracker_set_last_frame come first (every camera)");
   }
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  for (int k = 0; k < N; ++k) sh->members[(size_t)k]->overlap_valid = false;    // (until the chain has completed: its plan rewrites the list)
+  for (int k = 0; k < N; ++k) sh->members[(size_t)k]->frame_begins();
   const size_t l0 = (size_t)t0->cam.width * t0->cam.height;
   svo_hip_pyramid* ref = sh->frame_pyr[sh->last_idx];
   svo_hip_pyramid* cur = sh->frame_pyr[1 - sh->last_idx];
@@ -2156,25 +706,18 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
     else rc = svo_sia_note_device_slot(sh->sia, k, &t->cam, t->last_n_host);
     if (rc != SVO_HIP_OK) return rc;
   }
-  svo_hip_sia_params sp;
-  sp.max_level = c.klt_max_level; sp.min_level = c.klt_min_level; sp.n_iter = c.sia_n_iter; sp.eps = c.sia_eps; sp.early_stop = 1;
+  const svo_hip_sia_params sp = trk_sia_params(c);
   rc = svo_hip_sia_run(sh->sia, N, &sp);
   if (rc != SVO_HIP_OK) return rc;
   // ---- Reprojector::reprojectMap
-  const Cam cam = svo_make_cam(t0->cam);
   bool any_edgelet = false;
   for (int k = 0; k < N; ++k) {
     svo_hip_tracker* t = sh->members[(size_t)k];
-    if (t->rekey_pending && t->n_kf > 0) {    // Map::safeDeletePoint of the previous frame: Frame::removeKeyPoint on the keyframes
-      hipLaunchKernelGGL(trk_rekey_kernel, dim3(t->n_kf), dim3(KEY_THREADS), 0, ctx->stream, make_map(t), t->kf_key_point, cam);
-      SVO_CHECK_HIP(ctx, hipGetLastError());
-    }
-    t->rekey_pending = false;
+    rc = trk_rekey_now(t);                    // Map::safeDeletePoint of the previous frame: Frame::removeKeyPoint on the keyframes
+    if (rc != SVO_HIP_OK) return rc;
     any_edgelet = any_edgelet || t->any_edgelet;
   }
-  SeedRec* recs = nullptr;
-  uint32_t* pwb_t = nullptr;
-  int n_pad = 0;
+  SeedRec* recs = nullptr; uint32_t* pwb_t = nullptr; int n_pad = 0;           // the matcher's scratch
   const int stride = sh->rec_stride;
   rc = svo_match_scratch(ctx, N * stride, &recs, &pwb_t, &n_pad);
   if (rc != SVO_HIP_OK) return rc;
@@ -2204,37 +747,17 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
   if (N == 1) hipLaunchKernelGGL(trk_finish_one_kernel, dim3(1), dim3(256), 0, ctx->stream, an[0], seq);
   else hipLaunchKernelGGL(trk_finish_cams_kernel, dim3(N), dim3(256), 0, ctx->stream, ad, seq);
   SVO_CHECK_HIP(ctx, hipGetLastError());
-  // the one synchronisation of the frame: wait for every camera's sequence number (a spin on host memory: no driver call on the
-  // way back), with the stream's own synchronisation as the fall-back and the error check
-  {
-    bool all = false;
-    for (long spins = 0; spins < 4000000L && !all; ++spins) {                 // a few hundred milliseconds at most
-      all = true;
-      for (int k = 0; k < N && all; ++k) {
-        svo_hip_tracker* t = sh->members[(size_t)k];
-        volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(t->res_host + t->o_flag);
-        all = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq;
-      }
-      if (!all) __builtin_ia32_pause();
-    }
-    if (!all) SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < N; ++k) {
-      svo_hip_tracker* t = sh->members[(size_t)k];
-      volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(t->res_host + t->o_flag);
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "the frame's kernels did not complete");
-    }
+  // the one synchronisation of the frame: every camera's sequence number
+  for (int k = 0; k < N; ++k) {
+    const svo_hip_tracker* t = sh->members[(size_t)k];
+    sh->waits[(size_t)k] = {t->res_host + t->o_flag, seq};
   }
+  rc = trk_wait_flags(ctx, sh->waits.data(), N, who, "the frame's kernels did not complete");
+  if (rc != SVO_HIP_OK) return rc;
   sh->last_idx = 1 - sh->last_idx;          // the new frames' pyramids are the next call's references
   for (int k = 0; k < N; ++k) {
     svo_hip_tracker* t = sh->members[(size_t)k];
-    const svo_hip_track_result* r = reinterpret_cast<const svo_hip_track_result*>(t->res_host);
-    t->last_n_host = r->n_features;
-    t->track_n_points = t->n_points;
-    t->last_from_track = true;
-    t->last_renumbered = false;
-    t->need_gather = false;
-    t->overlap_valid = true;
-    if (r->map_changed) t->rekey_pending = true;
+    t->frame_tracked(*reinterpret_cast<const svo_hip_track_result*>(t->res_host));
   }
   return SVO_HIP_OK;
 }
@@ -2368,10 +891,8 @@ int svo_hip_tracker_add_candidates(svo_hip_tracker* t, int n, const double* pos,
   const size_t bytes = (size_t)n * sizeof(TrkCandRec);
   char* d = nullptr;
   char* hs = nullptr;
-  int rc = svo_ctx_staging(ctx, bytes, &d);
-  if (rc == SVO_HIP_OK) rc = svo_ctx_host_staging(ctx, bytes, &hs);
+  const int rc = trk_stage_upload(ctx, bytes, &d, &hs);
   if (rc != SVO_HIP_OK) return rc;
-  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the staging area may still feed an earlier transfer
   TrkCandRec* rec = reinterpret_cast<TrkCandRec*>(hs);
   int at = t->n_obs;
   for (int i = 0; i < n; ++i) {
@@ -2427,7 +948,7 @@ int svo_hip_tracker_promote_last_frame(svo_hip_tracker* t, int slot, int* kf_ind
   if (n_promoted_candidates) *n_promoted_candidates = out[0];
   t->kf_slot_host.push_back(slot);
   t->n_kf += 1;
-  t->overlap_valid = false;                 // the frame is a keyframe of the map now
+  t->keyframes_renumbered(false);
   if (!t->any_edgelet) {                    // the new observations carry the frame's edgelet flags
     const uint8_t* fe = reinterpret_cast<const uint8_t*>(t->res_host + t->o_edge);
     for (int i = 0; i < n_feat && !t->any_edgelet; ++i) t->any_edgelet = fp[i] >= 0 && fe[i] != 0;
@@ -2455,10 +976,9 @@ int svo_hip_tracker_remove_keyframe(svo_hip_tracker* t, int kf_index, int* slot_
   if (n_deleted_candidates) *n_deleted_candidates = out[4];
   t->kf_slot_host.erase(t->kf_slot_host.begin() + kf_index);
   t->n_kf -= 1;
-  t->overlap_valid = false;                 // the keyframes are renumbered
   // the keyframes that lost a key feature to a point deleted here choose again (Frame::removeKeyPoint), on the new rows,
   // before anything reads the key points
-  if (out[0] > 0) t->rekey_pending = true;
+  t->keyframes_renumbered(out[0] > 0);
   return SVO_HIP_OK;
 }
 
@@ -2477,10 +997,7 @@ int svo_hip_tracker_compact_points(svo_hip_tracker* t, int* n_points_after, int3
   rc = trk_rebuild_end(t, out, 5);
   if (rc != SVO_HIP_OK) return rc;
   t->n_points = out[0];
-  // the last frame's features refer to the new numbering on the device; the result block (and track_n_points, its layout)
-  // stays the tracked frame's under the old one
-  t->last_max_point = out[4];
-  t->last_renumbered = t->last_from_track;
+  t->points_renumbered(out[4]);
   if (n_points_after) *n_points_after = t->n_points;
   return SVO_HIP_OK;
 }
@@ -2514,17 +1031,8 @@ static TrkRelocArgs trk_reloc_args(const svo_hip_tracker* t, int kf, int exclude
 // the host's side of "the last frame is keyframe k now" (the kernel has written the device's): the keyframe's pyramid becomes
 // the last frame's, and the tracker is where svo_hip_tracker_set_last_frame leaves it
 static int trk_last_is_keyframe(svo_hip_tracker* t, int k, const TrkRelocOut& o) {
-  svo_hip_pyramid* dst = t->sh->frame_pyr[t->sh->last_idx];
-  const svo_hip_pyramid* kf = t->sh->kf_pyr;
-  const int rc = svo_hip_copy_d2d(t->ctx, dst->base + (size_t)t->cam_index * dst->pyr_bytes,
-                                  kf->base + ((size_t)t->cam_index * t->cfg.max_keyframes + t->kf_slot_host[(size_t)k]) * kf->pyr_bytes, dst->pyr_bytes);
-  t->last_n_host = o.n_feat;
-  t->last_max_point = o.max_point;
-  t->last_from_track = false;
-  t->last_renumbered = false;
-  t->have_last = true;
-  t->overlap_valid = false;
-  t->need_gather = true;
+  const int rc = trk_last_pyramid_from_keyframe(t, t->kf_slot_host[(size_t)k]);
+  t->host_set_last(o.n_feat, o.max_point);
   return rc;
 }
 
@@ -2580,7 +1088,7 @@ int svo_hip_tracker_relocalize(svo_hip_tracker* t, const uint8_t* level0, int kf
   memset(reloc, 0, sizeof(*reloc));
   reloc->kf_index = -1;
   // whatever fails from here on: the stream is through with the staging areas before the call returns
-  auto fail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); t->need_gather = true; return rc; };
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); t->call_failed(); return rc; };
   // ---- new Frame(cam, img, t): the image and its pyramid, as in svo_hip_tracker_track (the pyramid batch that is not the last frame's)
   svo_hip_pyramid* cur = sh->frame_pyr[1 - sh->last_idx];
   if (level0 != reinterpret_cast<const uint8_t*>(t->img_host)) memcpy(t->img_host, level0, (size_t)t->cam.width * t->cam.height);
@@ -2599,9 +1107,7 @@ int svo_hip_tracker_relocalize(svo_hip_tracker* t, const uint8_t* level0, int kf
   rc = trk_last_is_keyframe(t, o.kf, o);
   if (rc != SVO_HIP_OK) return fail(rc);
   // ---- SparseImgAlign(kltMaxLevel, kltMinLevel, 30, GaussNewton).run(ref_keyframe, new_frame) from T_f_w_init (:329-333)
-  const svo_hip_tracker_config& c = t->cfg;
-  svo_hip_sia_params sp;
-  sp.max_level = c.klt_max_level; sp.min_level = c.klt_min_level; sp.n_iter = c.sia_n_iter; sp.eps = c.sia_eps; sp.early_stop = 1;
+  const svo_hip_sia_params sp = trk_sia_params(t->cfg);
   svo_hip_sia_result gate;
   rc = svo_hip_sia_set_frames(sh->sia, sh->frame_pyr[sh->last_idx], cur);
   if (rc == SVO_HIP_OK) rc = svo_sia_note_device_slot(sh->sia, 0, &t->cam, o.n_feat);
@@ -2625,8 +1131,7 @@ int svo_hip_tracker_relocalize(svo_hip_tracker* t, const uint8_t* level0, int kf
   if (e == hipSuccess) e = hipMemcpyAsync(t->last.T_f_w, svo_sia_state_dev(sh->sia, 0)->T_cur_w, 7 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
   if (e != hipSuccess) return fail(svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, hipGetErrorString(e)));
   sh->last_idx = 1 - sh->last_idx;
-  t->last_n_host = 0;
-  t->last_max_point = -1;
+  t->gate_refused();
   return SVO_HIP_OK;
 }
 
@@ -2646,29 +1151,42 @@ static int trk_finish_check(svo_hip_tracker* t, int n, const int32_t* point, int
   return SVO_HIP_OK;
 }
 
-// the one wait: every listed camera's flag shows its sequence number (a spin on page-locked memory, the stream's own
-// synchronisation as the fall-back and the error check)
-static int trk_finish_wait(svo_hip_ctx* ctx, svo_hip_tracker* const* cams, int n_cams, const char* who) {
-  auto done = [&](int k) {
-    volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(cams[k]->st_host + ST_O_FLAG);
-    return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == cams[k]->st_seq;
-  };
-  bool all = false;
-  for (long spins = 0; spins < 4000000L && !all; ++spins) {
-    all = true;
-    for (int k = 0; k < n_cams && all; ++k) all = done(k);
-    if (!all) __builtin_ia32_pause();
-  }
-  if (!all) SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (int k = 0; k < n_cams; ++k)
-    if (!done(k)) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "the kernel did not complete");
-  return SVO_HIP_OK;
-}
-
+// the camera's block after the wait (decision: nullptr for the structure step alone)
 static void trk_finish_copy_out(const svo_hip_tracker* t, int n, double* pos_out, int32_t* iters_out, svo_hip_kf_decision* decision) {
   if (n > 0) memcpy(pos_out, t->st_host, (size_t)n * 24);
   if (n > 0 && iters_out) memcpy(iters_out, t->st_host + ST_O_ITERS, (size_t)n * 4);
-  memcpy(decision, t->st_host + ST_O_DECISION, sizeof(*decision));
+  if (decision) memcpy(decision, t->st_host + ST_O_DECISION, sizeof(*decision));
+}
+
+// trk_finish_frame_kernel for a lone camera (the tables by value: trk_plan_one_kernel says why)
+static void trk_finish_frame_launch(svo_hip_tracker* t, const TrkStructSel& sel, int n_iter, int overlap_valid, double min_dist, unsigned long long seq) {
+  hipLaunchKernelGGL(trk_finish_frame_kernel, dim3(1), dim3(FIN_THREADS), 0, t->ctx->stream, make_map(t), t->pt_pos, t->last, sel, n_iter,
+                     t->pl.overlap_kf, t->pl.counters, overlap_valid, min_dist, t->st_dev, seq);
+}
+
+int svo_hip_tracker_optimize_structure(svo_hip_tracker* t, int n, const int32_t* point, int n_iter, double* pos_out, int32_t* iters_out) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  const char* who = "svo_hip_tracker_optimize_structure";
+  // (the shape of the request, then the state, then the indices: the order this call has always refused in)
+  SVO_REQUIRE(ctx, n >= 0 && n <= TRK_MAX_STRUCT && n_iter >= 0 && (n == 0 || (point && pos_out)));
+  if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no map has been set");
+  if (n == 0) return SVO_HIP_OK;
+  TrkStructSel sel;
+  int rc = trk_finish_check(t, n, point, n_iter, pos_out, &sel);
+  if (rc != SVO_HIP_OK) return rc;
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  const unsigned long long seq = ++t->st_seq;
+  hipLaunchKernelGGL(trk_structure_kernel, dim3(1), dim3(256), 0, ctx->stream, make_map(t), t->pt_pos, t->last, sel, n_iter,
+                     reinterpret_cast<double*>(t->st_dev), reinterpret_cast<int*>(t->st_dev + ST_O_ITERS),
+                     reinterpret_cast<unsigned long long*>(t->st_dev + ST_O_FLAG), seq);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  const TrkFlagWait w = {t->st_host + ST_O_FLAG, t->st_seq};
+  rc = trk_wait_flags(ctx, &w, 1, who, "the kernel did not complete");
+  if (rc != SVO_HIP_OK) return rc;
+  trk_finish_copy_out(t, n, pos_out, iters_out, nullptr);
+  // (the point table and the solver's copy of the last frame's points were updated by the kernel: nothing to gather)
+  return SVO_HIP_OK;
 }
 
 int svo_hip_tracker_finish_frame(svo_hip_tracker* t, int n, const int32_t* point, int n_iter, double* pos_out, int32_t* iters_out,
@@ -2683,11 +1201,10 @@ int svo_hip_tracker_finish_frame(svo_hip_tracker* t, int n, const int32_t* point
   if (!t->have_map) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "no map has been set");
   if (!t->have_last) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "the device holds no last frame");
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  const unsigned long long seq = ++t->st_seq;
-  hipLaunchKernelGGL(trk_finish_frame_kernel, dim3(1), dim3(FIN_THREADS), 0, ctx->stream, make_map(t), t->pt_pos, t->last, sel, n_iter,
-                     t->pl.overlap_kf, t->pl.counters, t->overlap_valid ? 1 : 0, kf_select_min_dist, t->st_dev, seq);
+  trk_finish_frame_launch(t, sel, n_iter, t->overlap_valid ? 1 : 0, kf_select_min_dist, ++t->st_seq);
   SVO_CHECK_HIP(ctx, hipGetLastError());
-  rc = trk_finish_wait(ctx, &t, 1, who);
+  const TrkFlagWait w = {t->st_host + ST_O_FLAG, t->st_seq};
+  rc = trk_wait_flags(ctx, &w, 1, who, "the kernel did not complete");
   if (rc != SVO_HIP_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
   trk_finish_copy_out(t, n, pos_out, iters_out, decision);
   // (the point table and the solver's copy of the last frame's points were updated by the kernel: nothing to gather)
@@ -2702,64 +1219,53 @@ int svo_hip_tracker_group_finish_frames(svo_hip_tracker_group* g, const svo_hip_
   const char* who = "svo_hip_tracker_group_finish_frames";
   const int N = sh->n_cams;
   SVO_REQUIRE(ctx, decisions != nullptr && camera_ok != nullptr && kf_select_min_dist >= 0.0);
-  // every camera's request, before anything is enqueued or written
-  std::vector<TrkStructSel> sels((size_t)N);
-  std::vector<svo_hip_tracker*> active;
+  // every camera's request as the kernel takes it, before anything is enqueued or written
+  std::vector<TrkFinishReq> reqs((size_t)N);
+  int n_active = 0;
   for (int k = 0; k < N; ++k) {
     svo_hip_tracker* t = sh->members[(size_t)k];
     const svo_hip_structure_request none = {0, nullptr, 0, nullptr, nullptr};
     const svo_hip_structure_request& r = req ? req[k] : none;
+    TrkFinishReq& q = reqs[(size_t)k];
+    memset(&q, 0, sizeof(q));
     if (!t->have_map || !t->have_last) {                                       // the camera sits out
       SVO_REQUIRE(ctx, r.n == 0);
-      memset(&sels[(size_t)k], 0, sizeof(TrkStructSel));
       continue;
     }
-    const int rc = trk_finish_check(t, r.n, r.point, r.n_iter, r.pos_out, &sels[(size_t)k]);
+    const int rc = trk_finish_check(t, r.n, r.point, r.n_iter, r.pos_out, &q.sel);
     if (rc != SVO_HIP_OK) return rc;
-    active.push_back(t);
+    q.active = 1; q.n_iter = r.n_iter; q.overlap_valid = t->overlap_valid ? 1 : 0; q.st = t->st_dev;
+    ++n_active;
   }
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
   for (int k = 0; k < N; ++k) { camera_ok[k] = 0; memset(&decisions[k], 0, sizeof(svo_hip_kf_decision)); }
-  if (active.empty()) return SVO_HIP_OK;
+  if (n_active == 0) return SVO_HIP_OK;
   // (the previous call's kernel is through with the requests: the host waited for it)
-  for (int k = 0; k < N; ++k) {
+  for (int k = 0, w = 0; k < N; ++k) {
     svo_hip_tracker* t = sh->members[(size_t)k];
-    TrkFinishReq r;
-    memset(&r, 0, sizeof(r));
-    r.sel = sels[(size_t)k];
-    r.active = t->have_map && t->have_last ? 1 : 0;
-    if (r.active) {
-      r.n_iter = req ? req[k].n_iter : 0;
-      r.overlap_valid = t->overlap_valid ? 1 : 0;
-      r.st = t->st_dev;
-      r.seq = ++t->st_seq;
-    }
-    sh->fin_host[k] = r;
+    if (reqs[(size_t)k].active) { reqs[(size_t)k].seq = ++t->st_seq; sh->waits[(size_t)w++] = {t->st_host + ST_O_FLAG, t->st_seq}; }
+    sh->fin_host[k] = reqs[(size_t)k];
   }
   // a failure from here on: the stream is through with the staging areas before the call returns
   auto fail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; };
-  SeedRec* recs = nullptr;
-  uint32_t* pwb_t = nullptr;
-  int n_pad = 0;
+  SeedRec* recs = nullptr; uint32_t* pwb_t = nullptr; int n_pad = 0;           // the matcher's scratch
   int rc = svo_match_scratch(ctx, N * sh->rec_stride, &recs, &pwb_t, &n_pad);      // (the records' address is part of the table)
   if (rc == SVO_HIP_OK) rc = trk_args_table(sh, recs);
   if (rc != SVO_HIP_OK) return fail(rc);
   if (N == 1) {
-    svo_hip_tracker* t = sh->members[0];
     const TrkFinishReq& r = sh->fin_host[0];
-    hipLaunchKernelGGL(trk_finish_frame_kernel, dim3(1), dim3(FIN_THREADS), 0, ctx->stream, make_map(t), t->pt_pos, t->last, r.sel, r.n_iter,
-                       t->pl.overlap_kf, t->pl.counters, r.overlap_valid, kf_select_min_dist, r.st, r.seq);
+    trk_finish_frame_launch(sh->members[0], r.sel, r.n_iter, r.overlap_valid, kf_select_min_dist, r.seq);
   } else {
     hipLaunchKernelGGL(trk_finish_frames_cams_kernel, dim3(N), dim3(FIN_THREADS), 0, ctx->stream, sh->args_dev, sh->fin_dev, kf_select_min_dist);
   }
   if (hipGetLastError() != hipSuccess) return fail(svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "launch failed"));
-  rc = trk_finish_wait(ctx, active.data(), (int)active.size(), who);
+  rc = trk_wait_flags(ctx, sh->waits.data(), n_active, who, "the kernel did not complete");
   if (rc != SVO_HIP_OK) return fail(rc);
   for (int k = 0; k < N; ++k) {
     svo_hip_tracker* t = sh->members[(size_t)k];
     if (!sh->fin_host[k].active) continue;
     camera_ok[k] = 1;
-    trk_finish_copy_out(t, sels[(size_t)k].n, req ? req[k].pos_out : nullptr, req ? req[k].iters_out : nullptr, &decisions[k]);
+    trk_finish_copy_out(t, sh->fin_host[k].sel.n, req ? req[k].pos_out : nullptr, req ? req[k].iters_out : nullptr, &decisions[k]);
   }
   return SVO_HIP_OK;
 }
