@@ -1980,6 +1980,40 @@ static size_t sb_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static constexpr size_t kEvHeaderBytes = 64;
 static_assert(sizeof(svo_hip_seed_event) == 56, "event record layout (include/svo_hip.h)");
 
+// The arrays of a block laid out for N seeds: the uploaded part first (px f level a b mu z_range sigma2), then outputs and
+// bookkeeping
+struct SbLayout { size_t o_px, o_f, o_lvl, o_a, o_b, o_mu, o_zr, o_s2, upload_bytes, o_xyz, o_pc, o_st, o_al, o_bc, o_h, o_ev, total; };
+static SbLayout sb_layout(size_t N) {
+  SbLayout L;
+  size_t o = 0;
+  L.o_px = o; o = sb_align(o + 16 * N);
+  L.o_f = o; o = sb_align(o + 24 * N);
+  L.o_lvl = o; o = sb_align(o + 4 * N);
+  L.o_a = o; o = sb_align(o + 4 * N);
+  L.o_b = o; o = sb_align(o + 4 * N);
+  L.o_mu = o; o = sb_align(o + 4 * N);
+  L.o_zr = o; o = sb_align(o + 4 * N);
+  L.o_s2 = o; o = sb_align(o + 4 * N);
+  L.upload_bytes = o;
+  L.o_xyz = o; o = sb_align(o + 24 * N);
+  L.o_pc = o; o = sb_align(o + 16 * N);
+  L.o_st = o; o = sb_align(o + 4 * N);
+  L.o_al = o; o = sb_align(o + N);
+  L.o_bc = o; o = sb_align(o + 4 * ((N + 255) / 256));
+  L.o_h = o; o = sb_align(o + 64);
+  L.o_ev = o; o = sb_align(o + N * sizeof(svo_hip_seed_event));
+  L.total = o;
+  return L;
+}
+static void sb_point(svo_hip_seed_batch* sb, const SbLayout& L) {
+  char* d = sb->dev;
+  sb->px = (double*)(d + L.o_px); sb->f = (double*)(d + L.o_f); sb->level = (int32_t*)(d + L.o_lvl);
+  sb->a = (float*)(d + L.o_a); sb->b = (float*)(d + L.o_b); sb->mu = (float*)(d + L.o_mu); sb->z_range = (float*)(d + L.o_zr);
+  sb->sigma2 = (float*)(d + L.o_s2); sb->xyz = (double*)(d + L.o_xyz); sb->px_cur = (double*)(d + L.o_pc);
+  sb->status = (int32_t*)(d + L.o_st); sb->alive = (uint8_t*)(d + L.o_al); sb->block_count = (int*)(d + L.o_bc); sb->hist = (int*)(d + L.o_h);
+  sb->events_dev = (svo_hip_seed_event*)(d + L.o_ev);
+}
+
 // Capacity classes of the context's seed-batch pool: powers of two from 256 seeds (the drop-in's batches are <= 4096 seeds).
 static int sb_capacity_class(int n) {
   int c = 256;
@@ -2026,6 +2060,34 @@ static int sb_take_block(svo_hip_ctx* ctx, int n, size_t dev_need, size_t host_n
   return SVO_HIP_OK;
 }
 
+// a block goes back to the pool (svo_hip_seed_batch_destroy; a detection that found nothing)
+static void sb_return_block(svo_hip_ctx* ctx, const svo_seed_block& b) {
+  ctx->seed_pool.push_back(b);
+  --ctx->seed_blocks_in_use;
+}
+
+namespace {
+
+// DepthFilter::updateSeeds on a keyframe (S/depth_filter.cpp:302-306): feature_detector_->setGridOccpuancy(matcher_.px_cur_)
+// for every seed the pass updated -- status UPDATED, CONVERGED or NaN, the seeds a report_updated pass reports.  The status
+// is the gate: px_cur of a seed without a match is not finite, that of an erased seed is stale.  Batch j owns the blocks
+// [first_block, first_block + ceil(n / 256)) of the launch, as in the grouped pass.
+struct MarkJob { const int32_t* status; const double* px_cur; int n, first_block; };
+struct MarkGroup { MarkJob job[DF_GROUP_MAX]; int n_jobs; };
+__global__ __launch_bounds__(256) void seed_mark_updated_kernel(MarkGroup g, int cell_size, int grid_cols, int n_cells,
+                                                                uint8_t* __restrict__ occupancy) {
+  int j = 0;
+#pragma unroll
+  for (int k = 1; k < DF_GROUP_MAX; ++k) if (k < g.n_jobs && (int)blockIdx.x >= g.job[k].first_block) j = k;
+  const MarkJob& J = g.job[j];
+  const int i = ((int)blockIdx.x - J.first_block) * 256 + threadIdx.x;
+  if (i >= J.n) return;
+  if (J.status[i] < SVO_HIP_SEED_UPDATED) return;
+  grid_mark_cell(J.px_cur[2 * (size_t)i], J.px_cur[2 * (size_t)i + 1], cell_size, grid_cols, n_cells, occupancy);
+}
+
+}  // namespace
+
 
 extern "C" {
 
@@ -2039,33 +2101,14 @@ int svo_hip_seed_batch_create(svo_hip_ctx* ctx, int n, const double* px, const d
   if (!sb) return svo_fail(ctx, SVO_HIP_ERR_NOMEM, "svo_hip_seed_batch_create", "out of host memory");
   sb->ctx = ctx; sb->n = n; sb->n_alive = n; sb->n_blocks = (n + 255) / 256;
   const size_t N = (size_t)n;
-  // layout: uploaded part first (px f level a b mu z_range sigma2), then outputs and bookkeeping
-  size_t o = 0;
-  const size_t o_px = o; o = sb_align(o + 16 * N);
-  const size_t o_f = o; o = sb_align(o + 24 * N);
-  const size_t o_lvl = o; o = sb_align(o + 4 * N);
-  const size_t o_a = o; o = sb_align(o + 4 * N);
-  const size_t o_b = o; o = sb_align(o + 4 * N);
-  const size_t o_mu = o; o = sb_align(o + 4 * N);
-  const size_t o_zr = o; o = sb_align(o + 4 * N);
-  const size_t o_s2 = o; o = sb_align(o + 4 * N);
-  const size_t upload_bytes = o;
-  const size_t o_xyz = o; o = sb_align(o + 24 * N);
-  const size_t o_pc = o; o = sb_align(o + 16 * N);
-  const size_t o_st = o; o = sb_align(o + 4 * N);
-  const size_t o_al = o; o = sb_align(o + N);
-  const size_t o_bc = o; o = sb_align(o + 4 * (size_t)sb->n_blocks);
-  const size_t o_h = o; o = sb_align(o + 64);
-  const size_t o_ev = o; o = sb_align(o + N * sizeof(svo_hip_seed_event));
-  int rc = sb_take_block(ctx, n, o, kEvHeaderBytes + N * sizeof(svo_hip_seed_event), &sb->blk);
+  const SbLayout L = sb_layout(N);
+  const size_t o_px = L.o_px, o_f = L.o_f, o_lvl = L.o_lvl, o_a = L.o_a, o_b = L.o_b, o_mu = L.o_mu, o_zr = L.o_zr, o_s2 = L.o_s2;
+  const size_t upload_bytes = L.upload_bytes;
+  int rc = sb_take_block(ctx, n, L.total, kEvHeaderBytes + N * sizeof(svo_hip_seed_event), &sb->blk);
   sb->dev = sb->blk.dev; sb->host = sb->blk.host; sb->host_dev = sb->blk.host_dev;
   if (rc == SVO_HIP_OK) {
+    sb_point(sb, L);
     char* d = sb->dev;
-    sb->px = (double*)(d + o_px); sb->f = (double*)(d + o_f); sb->level = (int32_t*)(d + o_lvl);
-    sb->a = (float*)(d + o_a); sb->b = (float*)(d + o_b); sb->mu = (float*)(d + o_mu); sb->z_range = (float*)(d + o_zr);
-    sb->sigma2 = (float*)(d + o_s2); sb->xyz = (double*)(d + o_xyz); sb->px_cur = (double*)(d + o_pc);
-    sb->status = (int32_t*)(d + o_st); sb->alive = (uint8_t*)(d + o_al); sb->block_count = (int*)(d + o_bc); sb->hist = (int*)(d + o_h);
-    sb->events_dev = (svo_hip_seed_event*)(d + o_ev);
     memset(sb->host, 0, kEvHeaderBytes);
     // the uploaded arrays gathered in the context's page-locked staging area: one transfer
     char* hs = nullptr;
@@ -2293,6 +2336,94 @@ int svo_hip_seed_batch_arrays(svo_hip_seed_batch* sb, float** a_dev, float** b_d
   if (mu_dev) *mu_dev = sb->mu;
   if (sigma2_dev) *sigma2_dev = sb->sigma2;
   if (status_dev) *status_dev = sb->status;
+  return SVO_HIP_OK;
+}
+
+int svo_hip_seed_batch_mark_updated(int n_batches, svo_hip_seed_batch* const* batches, int cell_size, int grid_cols, int grid_rows,
+                                    uint8_t* occupancy_dev) {
+  if (n_batches < 1 || !batches || !batches[0]) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = batches[0]->ctx;
+  // everything is checked before anything is enqueued
+  for (int k = 0; k < n_batches; ++k) SVO_REQUIRE(ctx, batches[k] && batches[k]->ctx == ctx);
+  SVO_REQUIRE(ctx, occupancy_dev && cell_size > 0 && grid_cols > 0 && grid_rows > 0);
+  SVO_REQUIRE(ctx, (long long)grid_cols * grid_rows < (1ll << 31));
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  for (int first = 0; first < n_batches; first += DF_GROUP_MAX) {
+    MarkGroup g;
+    memset(&g, 0, sizeof(g));
+    g.n_jobs = n_batches - first < DF_GROUP_MAX ? n_batches - first : DF_GROUP_MAX;
+    int n_blocks = 0;
+    for (int j = 0; j < g.n_jobs; ++j) {
+      const svo_hip_seed_batch* sb = batches[first + j];
+      g.job[j].status = sb->status; g.job[j].px_cur = sb->px_cur; g.job[j].n = sb->n; g.job[j].first_block = n_blocks;
+      n_blocks += sb->n_blocks;
+    }
+    hipLaunchKernelGGL(seed_mark_updated_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, g, cell_size, grid_cols, grid_cols * grid_rows,
+                       occupancy_dev);
+  }
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  return SVO_HIP_OK;
+}
+
+int svo_hip_seed_batch_create_detected(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam, int n_pyr_levels,
+                                       int cell_size, uint8_t* occupancy_dev, int clear_occupancy, double detection_threshold,
+                                       double depth_mean, double depth_min, svo_hip_seed_batch** out, int32_t* n_out, double* px,
+                                       double* f, int32_t* level, float* score) {
+  if (!ctx || !out) return SVO_HIP_ERR_INVALID;
+  *out = nullptr;
+  SVO_REQUIRE(ctx, n_out != nullptr);
+  *n_out = 0;
+  {
+    // the detection's refusals come first: a refused call takes no block
+    const int rc = svo_detect_check_args(ctx, pyr, slot, cam, n_pyr_levels, cell_size, detection_threshold);
+    if (rc != SVO_HIP_OK) return rc;
+  }
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  int gc = 0, gr = 0;
+  svo_hip_detect_grid(pyr->width, pyr->height, cell_size, &gc, &gr);
+  const size_t NC = (size_t)gc * gr;                       // one feature per cell at most: the block is laid out for NC seeds
+  svo_hip_seed_batch* sb = new (std::nothrow) svo_hip_seed_batch;
+  if (!sb) return svo_fail(ctx, SVO_HIP_ERR_NOMEM, "svo_hip_seed_batch_create_detected", "out of host memory");
+  sb->ctx = ctx;
+  const SbLayout L = sb_layout(NC);
+  int rc = sb_take_block(ctx, (int)NC, L.total, kEvHeaderBytes + NC * sizeof(svo_hip_seed_event), &sb->blk);
+  if (rc != SVO_HIP_OK) { delete sb; return rc; }
+  sb->dev = sb->blk.dev; sb->host = sb->blk.host; sb->host_dev = sb->blk.host_dev;
+  sb_point(sb, L);
+  memset(sb->host, 0, kEvHeaderBytes);
+  // The features for the host go into the batch's page-locked event area, which nothing uses before the first pass:
+  // [px NC x 2 f64][f NC x 3 f64][level NC i32][score NC f32] = 48 bytes a cell of the 56 an event takes; the count into the header
+  const size_t o_hpx = kEvHeaderBytes, o_hf = o_hpx + 16 * NC, o_hl = o_hf + 24 * NC, o_hs = o_hl + 4 * NC;
+  svo_detect_seed_out o;
+  o.px = sb->px; o.f = sb->f; o.level = sb->level; o.a = sb->a; o.b = sb->b; o.mu = sb->mu; o.z_range = sb->z_range; o.sigma2 = sb->sigma2;
+  o.alive = sb->alive; o.status = sb->status;
+  o.n_host = reinterpret_cast<int32_t*>(sb->host_dev);
+  o.px_host = reinterpret_cast<double*>(sb->host_dev + o_hpx); o.f_host = reinterpret_cast<double*>(sb->host_dev + o_hf);
+  o.level_host = reinterpret_cast<int32_t*>(sb->host_dev + o_hl); o.score_host = reinterpret_cast<float*>(sb->host_dev + o_hs);
+  rc = svo_detect_into_seeds(ctx, pyr, slot, cam, n_pyr_levels, cell_size, occupancy_dev, detection_threshold, depth_mean, depth_min, &o);
+  hipError_t e = hipSuccess;
+  // resetGrid() (feature_detection.cpp:121), behind the detection on the stream
+  if (rc == SVO_HIP_OK && occupancy_dev && clear_occupancy) e = hipMemsetAsync(occupancy_dev, 0, NC, ctx->stream);
+  const hipError_t e_sync = hipStreamSynchronize(ctx->stream);                 // the one wait; also before the block may go back
+  if (e == hipSuccess) e = e_sync;
+  if (rc == SVO_HIP_OK && e != hipSuccess) rc = svo_fail(ctx, SVO_HIP_ERR_DEVICE, "svo_hip_seed_batch_create_detected", hipGetErrorString(e));
+  const int n = rc == SVO_HIP_OK ? *reinterpret_cast<const int32_t*>(sb->host) : 0;
+  if (rc == SVO_HIP_OK && n > 0) {
+    const size_t N = (size_t)n;
+    if (px) memcpy(px, sb->host + o_hpx, 16 * N);
+    if (f) memcpy(f, sb->host + o_hf, 24 * N);
+    if (level) memcpy(level, sb->host + o_hl, 4 * N);
+    if (score) memcpy(score, sb->host + o_hs, 4 * N);
+  }
+  memset(sb->host, 0, kEvHeaderBytes);                     // the header as svo_hip_seed_batch_create leaves it
+  if (rc != SVO_HIP_OK || n == 0) {                        // no seeds: no batch, the block back in the pool
+    sb_return_block(ctx, sb->blk);
+    delete sb;
+    return rc;
+  }
+  sb->n = n; sb->n_alive = n; sb->n_blocks = (n + 255) / 256;
+  *n_out = n;
+  *out = sb;
   return SVO_HIP_OK;
 }
 

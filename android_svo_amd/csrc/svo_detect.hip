@@ -173,29 +173,85 @@ __global__ void seed_init_kernel(int n, float depth_mean, float depth_min, float
   sigma2[i] = zr * zr / 36;
 }
 
-}  // namespace
+// ---- a keyframe's seeds created where they are detected (svo_hip_seed_batch_create_detected) ------------------------
+// detect_compact_kernel's ordered compaction writing a seed batch's block: px / f / level of the new Feature, the Seed
+// constructor's state (seed_init_kernel's arithmetic), alive = 1, status = SVO_HIP_SEED_ERASED (no pass yet), and the
+// features once more into the batch's page-locked block for the host, which creates the Feature / Seed objects from them.
+__global__ __launch_bounds__(256) void detect_compact_seeds_kernel(const unsigned long long* __restrict__ cells, int n_cells,
+                                                                   double threshold, LevelDims dims, Cam cam, float depth_mean,
+                                                                   float depth_min, svo_detect_seed_out o) {
+  __shared__ int s_wave[4];
+  __shared__ int s_base;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) s_base = 0;
+  __syncthreads();
+  const float m = (float)(1.0 / depth_mean);
+  const float zr = (float)(1.0 / depth_min);
+  for (int k0 = 0; k0 < n_cells; k0 += 256) {
+    const int k = k0 + threadIdx.x;
+    unsigned long long key = 0;
+    bool keep = false;
+    if (k < n_cells) {
+      key = cells[k];
+      keep = (double)__uint_as_float((unsigned)(key >> 32)) > threshold;       // (the phantom features of detect_compact_kernel too)
+    }
+    const unsigned long long mask = __ballot(keep);
+    const int before = __popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0) s_wave[wave] = __popcll(mask);
+    __syncthreads();
+    int off = s_base;
+    for (int w = 0; w < wave; ++w) off += s_wave[w];
+    if (keep) {
+      const size_t i = (size_t)(off + before);                                  // < n_cells: one feature per cell at most
+      const unsigned order = 0xffffffffu - (unsigned)(key & 0xffffffffull);
+      const int level = (int)(order >> 24);
+      const int idx = (int)(order & 0xffffffu);
+      const int w = dims.w[level];
+      const int scale = 1 << level;
+      const double u = (double)((idx % w) * scale), v = (double)((idx / w) * scale);
+      double f[3];
+      cam2world(cam, u, v, f);
+      o.px[2 * i] = u; o.px[2 * i + 1] = v;
+      o.f[3 * i] = f[0]; o.f[3 * i + 1] = f[1]; o.f[3 * i + 2] = f[2];
+      o.level[i] = level;
+      o.a[i] = 10; o.b[i] = 10; o.mu[i] = m; o.z_range[i] = zr;
+      o.sigma2[i] = zr * zr / 36;
+      o.alive[i] = 1;
+      o.status[i] = SVO_HIP_SEED_ERASED;
+      o.px_host[2 * i] = u; o.px_host[2 * i + 1] = v;
+      o.f_host[3 * i] = f[0]; o.f_host[3 * i + 1] = f[1]; o.f_host[3 * i + 2] = f[2];
+      o.level_host[i] = level;
+      o.score_host[i] = __uint_as_float((unsigned)(key >> 32));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *o.n_host = s_base;
+}
 
-extern "C" {
+// AbstractDetector::setExistingFeatures (S/feature_detection.cpp:47-56) over n level-0 pixels: grid-stride, a launch is at
+// most MARK_MAX_BLOCKS workgroups
+constexpr int MARK_MAX_BLOCKS = 32;
+__global__ __launch_bounds__(256) void grid_mark_px_kernel(int n, const double* __restrict__ px, int cell_size, int grid_cols,
+                                                           int n_cells, uint8_t* __restrict__ occupancy) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+    grid_mark_cell(px[2 * (size_t)i], px[2 * (size_t)i + 1], cell_size, grid_cols, n_cells, occupancy);
+}
 
-int svo_hip_detect_grid(int width, int height, int cell_size, int* grid_cols, int* grid_rows) {
-  if (width <= 0 || height <= 0 || cell_size <= 0 || !grid_cols || !grid_rows) return SVO_HIP_ERR_INVALID;
-  *grid_cols = (width + cell_size - 1) / cell_size;            // ceil(width / cell_size), feature_detection.cpp:31-32
-  *grid_rows = (height + cell_size - 1) / cell_size;
+// the refusals of the detection, before anything is taken or launched
+int detect_check(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, int n_pyr_levels, int cell_size, double detection_threshold) {
+  SVO_REQUIRE(ctx, pyr && slot >= 0 && slot < pyr->batch);
+  SVO_REQUIRE(ctx, n_pyr_levels > 0 && n_pyr_levels <= pyr->n_levels && cell_size > 0);
+  SVO_REQUIRE(ctx, (size_t)pyr->width * pyr->height < (1u << 24));
+  SVO_REQUIRE(ctx, !(detection_threshold < 0.0));               // the cells' keys order non-negative floats only (NaN: no feature)
   return SVO_HIP_OK;
 }
 
-int svo_hip_detect_features_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam,
-                                int n_pyr_levels, int cell_size, const uint8_t* occupancy_dev,
-                                double detection_threshold, int32_t* n_out_dev, double* px_dev, double* f_dev,
-                                int32_t* level_dev, float* score_dev) {
-  if (!ctx) return SVO_HIP_ERR_INVALID;
-  SVO_REQUIRE(ctx, pyr && slot >= 0 && slot < pyr->batch);
-  SVO_REQUIRE(ctx, n_pyr_levels > 0 && n_pyr_levels <= pyr->n_levels && cell_size > 0);
-  SVO_REQUIRE(ctx, n_out_dev && px_dev && level_dev);
-  SVO_REQUIRE(ctx, !f_dev || cam);
-  SVO_REQUIRE(ctx, (size_t)pyr->width * pyr->height < (1u << 24));
-  SVO_REQUIRE(ctx, !(detection_threshold < 0.0));               // the cells' keys order non-negative floats only (NaN: no feature)
-  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+// FAST, suppression and the per-cell maxima of the first n_pyr_levels levels: the cells' keys in the context's scratch
+int detect_enqueue_cells(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, int n_pyr_levels, int cell_size,
+                         const uint8_t* occupancy_dev, double detection_threshold, unsigned long long** cells_out, int* n_cells_out,
+                         LevelDims* dims_out) {
   int gc = 0, gr = 0;
   svo_hip_detect_grid(pyr->width, pyr->height, cell_size, &gc, &gr);
   const int n_cells = gc * gr;
@@ -222,6 +278,62 @@ int svo_hip_detect_features_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, in
     hipLaunchKernelGGL(fast_score_kernel, grd, blk, 0, ctx->stream, img, w, h, 10, sc);       // cv::FAST(img, kp, 10, true) (:93-96)
     hipLaunchKernelGGL(fast_nms_grid_kernel, grd, blk, 0, ctx->stream, img, sc, w, h, l, cell_size, gc, occupancy_dev, thr, cells);
     sc += ((size_t)w * h + 15) & ~(size_t)15;
+  }
+  *cells_out = cells; *n_cells_out = n_cells; *dims_out = dims;
+  return SVO_HIP_OK;
+}
+
+}  // namespace
+
+int svo_detect_check_args(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam, int n_pyr_levels,
+                          int cell_size, double detection_threshold) {
+  SVO_REQUIRE(ctx, cam != nullptr);                                // every seed needs its bearing
+  return detect_check(ctx, pyr, slot, n_pyr_levels, cell_size, detection_threshold);
+}
+
+int svo_detect_into_seeds(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam, int n_pyr_levels,
+                          int cell_size, const uint8_t* occupancy_dev, double detection_threshold, double depth_mean, double depth_min,
+                          const svo_detect_seed_out* out) {
+  int rc = svo_detect_check_args(ctx, pyr, slot, cam, n_pyr_levels, cell_size, detection_threshold);
+  if (rc != SVO_HIP_OK) return rc;
+  unsigned long long* cells = nullptr;
+  int n_cells = 0;
+  LevelDims dims;
+  rc = detect_enqueue_cells(ctx, pyr, slot, n_pyr_levels, cell_size, occupancy_dev, detection_threshold, &cells, &n_cells, &dims);
+  if (rc != SVO_HIP_OK) return rc;
+  hipLaunchKernelGGL(detect_compact_seeds_kernel, dim3(1), dim3(256), 0, ctx->stream, cells, n_cells, detection_threshold, dims,
+                     svo_make_cam(*cam), (float)depth_mean, (float)depth_min, *out);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  return SVO_HIP_OK;
+}
+
+extern "C" {
+
+int svo_hip_detect_grid(int width, int height, int cell_size, int* grid_cols, int* grid_rows) {
+  if (width <= 0 || height <= 0 || cell_size <= 0 || !grid_cols || !grid_rows) return SVO_HIP_ERR_INVALID;
+  *grid_cols = (width + cell_size - 1) / cell_size;            // ceil(width / cell_size), feature_detection.cpp:31-32
+  *grid_rows = (height + cell_size - 1) / cell_size;
+  return SVO_HIP_OK;
+}
+
+int svo_hip_detect_features_dev(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam,
+                                int n_pyr_levels, int cell_size, const uint8_t* occupancy_dev,
+                                double detection_threshold, int32_t* n_out_dev, double* px_dev, double* f_dev,
+                                int32_t* level_dev, float* score_dev) {
+  if (!ctx) return SVO_HIP_ERR_INVALID;
+  {
+    const int rc = detect_check(ctx, pyr, slot, n_pyr_levels, cell_size, detection_threshold);
+    if (rc != SVO_HIP_OK) return rc;
+  }
+  SVO_REQUIRE(ctx, n_out_dev && px_dev && level_dev);
+  SVO_REQUIRE(ctx, !f_dev || cam);
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  unsigned long long* cells = nullptr;
+  int n_cells = 0;
+  LevelDims dims;
+  {
+    const int rc = detect_enqueue_cells(ctx, pyr, slot, n_pyr_levels, cell_size, occupancy_dev, detection_threshold, &cells, &n_cells, &dims);
+    if (rc != SVO_HIP_OK) return rc;
   }
   Cam c;
   memset(&c, 0, sizeof(c));
@@ -296,6 +408,44 @@ int svo_hip_seed_init_batch_dev(svo_hip_ctx* ctx, int n, double depth_mean, doub
                      a_dev, b_dev, mu_dev, z_range_dev, sigma2_dev);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   return SVO_HIP_OK;
+}
+
+int svo_hip_grid_mark_px_dev(svo_hip_ctx* ctx, int n, const double* px_dev, int cell_size, int grid_cols, int grid_rows,
+                             uint8_t* occupancy_dev) {
+  if (!ctx) return SVO_HIP_ERR_INVALID;
+  SVO_REQUIRE(ctx, n >= 0 && cell_size > 0 && grid_cols > 0 && grid_rows > 0 && occupancy_dev);
+  SVO_REQUIRE(ctx, (long long)grid_cols * grid_rows < (1ll << 31));
+  if (n == 0) return SVO_HIP_OK;
+  SVO_REQUIRE(ctx, px_dev != nullptr);
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  const int blocks = (n + 255) / 256 < MARK_MAX_BLOCKS ? (n + 255) / 256 : MARK_MAX_BLOCKS;
+  hipLaunchKernelGGL(grid_mark_px_kernel, dim3(blocks), dim3(256), 0, ctx->stream, n, px_dev, cell_size, grid_cols, grid_cols * grid_rows,
+                     occupancy_dev);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  return SVO_HIP_OK;
+}
+
+int svo_hip_grid_mark_px(svo_hip_ctx* ctx, int n, const double* px_host, int cell_size, int grid_cols, int grid_rows,
+                         uint8_t* occupancy_dev) {
+  if (!ctx) return SVO_HIP_ERR_INVALID;
+  SVO_REQUIRE(ctx, n >= 0 && cell_size > 0 && grid_cols > 0 && grid_rows > 0 && occupancy_dev);
+  SVO_REQUIRE(ctx, (long long)grid_cols * grid_rows < (1ll << 31));
+  if (n == 0) return SVO_HIP_OK;
+  SVO_REQUIRE(ctx, px_host != nullptr);
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)n * 16;
+  char* d = nullptr;
+  char* hs = nullptr;
+  int rc = svo_ctx_staging(ctx, bytes, &d);
+  if (rc == SVO_HIP_OK) rc = svo_ctx_host_staging(ctx, bytes, &hs);
+  if (rc != SVO_HIP_OK) return rc;
+  memcpy(hs, px_host, bytes);
+  SVO_CHECK_HIP(ctx, hipMemcpyAsync(d, hs, bytes, hipMemcpyHostToDevice, ctx->stream));
+  // the transfer out of the page-locked area stays in flight: its next user waits for this event (svo_ctx_host_staging)
+  if (!ctx->host_staging_ev) SVO_CHECK_HIP(ctx, hipEventCreateWithFlags(&ctx->host_staging_ev, hipEventDisableTiming));
+  SVO_CHECK_HIP(ctx, hipEventRecord(ctx->host_staging_ev, ctx->stream));
+  ctx->host_staging_in_flight = true;
+  return svo_hip_grid_mark_px_dev(ctx, n, reinterpret_cast<const double*>(d), cell_size, grid_cols, grid_rows, occupancy_dev);
 }
 
 }  // extern "C"

@@ -241,6 +241,21 @@ SVO_DEV void gn_control_step(FrameState& s, const double* r, int level, int n_it
   if (iter + 1 >= n_iter) done = 1;
   if (done) s.level_done = 1;
 }
+
+// AbstractDetector::setGridOccpuancy (S/feature_detection.cpp:58-64): the cell of a level-0 pixel is marked occupied; shared by
+// the marking kernels of svo_detect.hip, svo_depth.hip and svo_track.hip.
+// k = (int)(px[1] / cell_size) * grid_cols + (int)(px[0] / cell_size): a double divided by an int, truncated towards zero; the
+// flat index is the only range test (a pixel beyond the width whose index is valid marks the next row's cell).  Where the
+// reference's cast is undefined or its .at() throws -- a non-finite coordinate, a quotient beyond int, k outside the grid --
+// nothing is marked.  The only byte ever stored is 1, so concurrent marks of one cell need no atomic.
+SVO_DEV void grid_mark_cell(double u, double v, int cell_size, int grid_cols, int n_cells, uint8_t* __restrict__ occupancy) {
+  const double qx = u / cell_size, qy = v / cell_size;
+  // (a NaN fails every comparison)
+  if (!(qx > -2147483649.0 && qx < 2147483648.0 && qy > -2147483649.0 && qy < 2147483648.0)) return;
+  const long long k = (long long)(int)qy * grid_cols + (long long)(int)qx;
+  if (k < 0 || k >= (long long)n_cells) return;
+  occupancy[k] = 1;
+}
 }  // namespace svo_dev
 
 // internal entries of svo_sia.hip for the device-resident tracking chain (svo_track.hip): a slot of the solver is filled
@@ -279,6 +294,27 @@ svo_nlls_ext** svo_sia_nlls_slot(svo_hip_sia* s);
 int svo_nlls_run(svo_hip_sia* s, int n_slots, const svo_hip_sia_params* prm, int method, int scale_estimator, int weight_function);
 int svo_nlls_scale(svo_hip_sia* s, int slot, float* scale, double* mu, double* nu);
 void svo_nlls_free(svo_nlls_ext* e);
+
+// ---- svo_depth.hip -> svo_detect.hip: a detection written straight into a seed batch's block (svo_hip_seed_batch_create_detected).
+// Device arrays of the block laid out for one seed per grid cell, and device addresses of the block's page-locked part.
+struct svo_detect_seed_out {
+  double *px, *f;
+  int32_t* level;
+  float *a, *b, *mu, *z_range, *sigma2;
+  uint8_t* alive;
+  int32_t* status;
+  int32_t* n_host;                      // the number of features
+  double *px_host, *f_host;
+  int32_t* level_host;
+  float* score_host;
+};
+// the refusals of svo_hip_detect_features_dev (a camera is required: every seed has a bearing), nothing enqueued
+int svo_detect_check_args(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam, int n_pyr_levels,
+                          int cell_size, double detection_threshold);
+// the detection's launches on the context stream, the compaction writing `out`
+int svo_detect_into_seeds(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam, int n_pyr_levels,
+                          int cell_size, const uint8_t* occupancy_dev, double detection_threshold, double depth_mean, double depth_min,
+                          const svo_detect_seed_out* out);
 
 namespace svo_dev { struct SeedRec; }
 int svo_match_scratch(svo_hip_ctx* ctx, int n_cap, svo_dev::SeedRec** recs, uint32_t** pwb_t, int* n_pad);

@@ -70,6 +70,17 @@ int trk_wait_flags(svo_hip_ctx* ctx, const TrkFlagWait* w, int n, const char* wh
   return SVO_HIP_OK;
 }
 
+// feature_detector_->setExistingFeatures(frame->fts_) (S/depth_filter.cpp:132, feature_detection.cpp:47-56) for the device's last
+// frame: every feature's cell, with or without a point (the pose refinement drops points, not features: pose_optimizer.cpp:154-157).
+// The count is the one the device holds; one workgroup strides over it.
+__global__ __launch_bounds__(256) void trk_mark_last_kernel(const int* __restrict__ n_last, const double* __restrict__ px, int cap,
+                                                            int cell_size, int grid_cols, int n_cells, uint8_t* __restrict__ occupancy) {
+  int n = n_last[0];
+  if (n > cap) n = cap;
+  for (int i = threadIdx.x; i < n; i += 256)
+    svo_dev::grid_mark_cell(px[2 * (size_t)i], px[2 * (size_t)i + 1], cell_size, grid_cols, n_cells, occupancy);
+}
+
 }  // namespace
 
 // What the cameras of a tracker group share (a lone tracker is a group of one): the pyramid batches, the SparseImgAlign solver
@@ -1305,6 +1316,22 @@ int svo_hip_tracker_download_map(svo_hip_tracker* t, svo_hip_tracker_map_out* ou
   get(out->obs_edgelet, tb.obs_edgelet, O); get(out->obs_grad, tb.obs_grad, O * 16);
   get(out->cand_point, tb.cand_point, (size_t)t->n_candidates * 4);
   if (e != hipSuccess) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, "svo_hip_tracker_download_map", hipGetErrorString(e));
+  SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_mark_last_frame(svo_hip_tracker* t, int cell_size, int grid_cols, int grid_rows, uint8_t* occupancy_dev) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = t->ctx;
+  const char* who = "svo_hip_tracker_mark_last_frame";
+  SVO_REQUIRE(ctx, occupancy_dev && cell_size > 0 && grid_cols > 0 && grid_rows > 0);
+  SVO_REQUIRE(ctx, (long long)grid_cols * grid_rows < (1ll << 31));
+  if (!t->have_last) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "the device holds no last frame");
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(trk_mark_last_kernel, dim3(1), dim3(256), 0, ctx->stream, t->last.n, t->last.px, t->cfg.max_frame_features, cell_size,
+                     grid_cols, grid_cols * grid_rows, occupancy_dev);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
+  // the grid usually belongs to the depth filter's context: its stream may read the marks once this call has returned
   SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SVO_HIP_OK;
 }

@@ -600,6 +600,34 @@ class ResidentSeeds:
         ctx.check(ctx.lib.svo_hip_seed_batch_create(ctx.h, self.n, _ptr(px, C.c_double), _ptr(f, C.c_double), _ptr(lvl, C.c_int32),
                                                     *[_ptr(v, C.c_float) for v in st], C.byref(self.h)), "seed_batch_create")
 
+    @classmethod
+    def from_detection(cls, ctx: Context, pyr: Pyramid, slot: int, cam, depth_mean: float, depth_min: float, n_pyr_levels: int = 3,
+                       cell_size: int = 20, grid: Optional["DetectorGrid"] = None, clear_grid: bool = True,
+                       detection_threshold: float = 10.0):
+        """svo_hip_seed_batch_create_detected: DepthFilter::initializeSeeds as one device call.  Returns (batch or None when
+        nothing was detected, {"px", "f", "level", "score"} of the new features in grid-cell order)."""
+        gc, gr = detect_grid(pyr.width, pyr.height, cell_size)
+        nc = gc * gr
+        if grid is not None:
+            assert (grid.cell_size, grid.cols, grid.rows) == (cell_size, gc, gr)
+        px, f = np.zeros((nc, 2)), np.zeros((nc, 3))
+        lvl, sc = np.zeros(nc, dtype=np.int32), np.zeros(nc, dtype=np.float32)
+        n = C.c_int32(0)
+        h = C.c_void_p()
+        c = make_camera(cam) if cam is not None else None
+        ctx.check(ctx.lib.svo_hip_seed_batch_create_detected(
+            ctx.h, pyr.h if pyr is not None else None, slot, C.byref(c) if c is not None else None, n_pyr_levels, cell_size,
+            C.c_void_p(grid.ptr) if grid is not None else None, 1 if clear_grid else 0, C.c_double(detection_threshold),
+            C.c_double(depth_mean), C.c_double(depth_min), C.byref(h), C.byref(n), _ptr(px, C.c_double), _ptr(f, C.c_double),
+            _ptr(lvl, C.c_int32), _ptr(sc, C.c_float)), "seed_batch_create_detected")
+        k = n.value
+        feats = {"px": px[:k].copy(), "f": f[:k].copy(), "level": lvl[:k].copy(), "score": sc[:k].copy()}
+        if not h.value:
+            return None, feats
+        self = cls.__new__(cls)
+        self.ctx, self.n, self.h = ctx, k, h
+        return self, feats
+
     def update_async(self, ref: Pyramid, ref_slot: int, cur: Pyramid, cur_slot: int, cam, T_ref_w, T_cur_w, prm=None, report_updated=False):
         prm = prm or depth_filter_params()
         c = make_camera(cam)
@@ -867,6 +895,56 @@ def seed_init_batch(ctx: Context, n: int, depth_mean: float, depth_min: float):
     return out
 
 
+class DetectorGrid:
+    """The detector's occupancy grid (AbstractDetector::grid_occupancy_) as a device buffer of cols * rows bytes: marked by
+    pixels, by the seeds a pass updated and by a tracker's last frame, read and cleared by ResidentSeeds.from_detection.
+    `ptr` wraps somebody else's allocation (never freed through the grid)."""
+
+    def __init__(self, ctx: Context, width: int, height: int, cell_size: int, ptr: Optional[int] = None):
+        self.ctx, self.cell_size = ctx, int(cell_size)
+        self.cols, self.rows = detect_grid(width, height, cell_size)
+        self.n_cells = self.cols * self.rows
+        self._own = ptr is None
+        self.ptr = ctx.malloc(self.n_cells) if ptr is None else ptr
+        if self._own:
+            self.clear()
+
+    def _dims(self):
+        return self.cell_size, self.cols, self.rows, C.c_void_p(self.ptr)
+
+    def mark_px(self, px):
+        """setExistingFeatures over level-0 pixels: a host array [n,2], or a DeviceArray / DeviceView of that shape"""
+        if isinstance(px, (DeviceArray, DeviceView)):
+            n = int(np.prod(px.shape)) // 2
+            self.ctx.check(self.ctx.lib.svo_hip_grid_mark_px_dev(self.ctx.h, n, C.c_void_p(px.ptr), *self._dims()), "grid_mark_px_dev")
+        else:
+            a = _f64(px).reshape(-1, 2)
+            self.ctx.check(self.ctx.lib.svo_hip_grid_mark_px(self.ctx.h, len(a), _ptr(a, C.c_double), *self._dims()), "grid_mark_px")
+
+    def mark_updated(self, batches):
+        """the px_cur of every seed the batches' last pass updated (depth_filter.cpp:302-306); enqueued, no wait"""
+        hs = (C.c_void_p * len(batches))(*[b.h for b in batches])
+        rc = self.ctx.lib.svo_hip_seed_batch_mark_updated(len(batches), hs, *self._dims())
+        self.ctx.check(rc, "seed_batch_mark_updated")
+
+    def mark_tracker(self, tracker):
+        tracker.mark_last_frame(self)
+
+    def download(self) -> np.ndarray:
+        return DeviceView(self.ctx, self.ptr, (self.rows, self.cols), np.uint8).download()
+
+    def upload(self, occ):
+        DeviceView(self.ctx, self.ptr, (self.rows, self.cols), np.uint8).upload(np.asarray(occ, dtype=np.uint8).reshape(self.rows, self.cols))
+
+    def clear(self):
+        self.upload(np.zeros((self.rows, self.cols), np.uint8))
+
+    def free(self):
+        if self._own and self.ptr:
+            self.ctx.free(self.ptr)
+        self.ptr = 0
+
+
 # ---- next row f-2: the cell loop of Reprojector::reprojectMap --------------------------------------------------------
 def reproject_cells(ctx: Context, ref: Pyramid, cur: Pyramid, cur_slot: int, cam, T_kf_w, T_cur_w, cell_offset, kf_slot,
                     px_ref, f_ref, level_ref, pt_pos, deleted, px_cur, edgelet=None, grad=None, max_fts: int = 1200,
@@ -1061,6 +1139,12 @@ class Tracker:
         k, n = C.c_int(-1), C.c_int(-1)
         self.ctx.check(self.ctx.lib.svo_hip_tracker_promote_last_frame(self.h, int(slot), C.byref(k), C.byref(n)), "tracker_promote_last_frame")
         return k.value, n.value
+
+    def mark_last_frame(self, grid: "DetectorGrid"):
+        """svo_hip_tracker_mark_last_frame: setExistingFeatures over every feature of the device's last frame; synchronises the
+        tracker's stream"""
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_mark_last_frame(self.h, grid.cell_size, grid.cols, grid.rows, C.c_void_p(grid.ptr)),
+                       "tracker_mark_last_frame")
 
     def remove_keyframe(self, kf_index: int) -> dict:
         """svo_hip_tracker_remove_keyframe: keyframe kf_index leaves the device's map in place (Map::safeDeleteFrame on the

@@ -7,6 +7,8 @@
 //        svo_host_demo <case_dir> <out_dir> trackgroup [n]   the same tracking chain for n (default 2) copies of the world at once through
 //                                                   svo::FrameTrackerGroup (hip_bridge::FrameTrackerGroupT, svo_hip_tracker_group): outputs of
 //                                                   world w under <out_dir>/g<w>/, each equal to the lone tracker's
+//        svo_host_demo <case_dir> <out_dir> keyframes [device_seeds] [threaded]   keyframes whose seeds the filter detects and creates
+//                                                   on the device, or (without device_seeds) are detected by the caller and handed in
 //        svo_host_demo <case_dir> <out_dir> churn   SURVEY 8(b) "Threading": latency of SparseImgAlign::run on the tracking
 //                                                   thread while a second thread (own context) creates seed batches, runs a
 //                                                   pass and drops them at keyframe rate -- and with that thread idle
@@ -527,8 +529,140 @@ static int churn_demo(const std::string& dir, const std::string& out) {
   return 0;
 }
 
+// ---- keyframes [device_seeds] [threaded]: N frames through the DepthFilter protocol, some of them keyframes, each keyframe with a
+// list of existing features.  With device_seeds the filter makes a keyframe's seeds itself (enableDeviceSeedInit, addKeyframe
+// without features: grid marks, detection and seed construction on the device, nothing uploaded).  Without it the demo does what
+// a host has to do today: on the threaded path the keyframe's update comes first (it marks the host DetectorGrid), then the
+// existing features are marked, svo_hip_detect_features runs on that grid, and the features are handed in.
+// Inputs: manifest.bin, frame_<k>_*.bin, depth_mean_min.bin, kf_params.bin (n_pyr_levels, cell_size, detection_threshold),
+// kf_list.bin (frame indices, ascending, the first one 0), kf_existing_<j>.bin (px of keyframe j's existing features).
+// Outputs: kf<j>_grid.bin (the grid as the detector saw it), kf<j>_px.bin / kf<j>_level.bin (the new seeds), kf_counts.bin;
+// conv.bin, per convergence callback: seed id, xyz_world (bits), sigma2; frames.bin, per frame that is not a keyframe: its
+// index, seeds on the device, seeds uploaded by its update.
+struct KeyframeDemoFilter : DepthFilter {
+  using DepthFilter::DepthFilter;
+  /// the features of a keyframe whose update has already run (the threaded path of the leg without device_seeds)
+  void seedKeyframe(FramePtr frame, double depth_mean, double depth_min, const std::vector<Feature*>& fts) {
+    new_keyframe_min_depth_ = depth_min;
+    new_keyframe_mean_depth_ = depth_mean;
+    initializeSeeds(frame, fts);
+  }
+};
+
+static int keyframes_demo(const std::string& dir, const std::string& out, bool device_seeds, bool threaded) {
+  const std::vector<double> m = read_bin<double>(dir + "/manifest.bin");
+  PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
+  const int n_levels = (int)m[6], n_frames = (int)m[7];
+  const auto dm = read_bin<double>(dir + "/depth_mean_min.bin");
+  const auto prm = read_bin<double>(dir + "/kf_params.bin");
+  const int n_pyr_levels = (int)prm[0], cell = (int)prm[1];
+  const double threshold = prm[2];
+  const auto kf_list = read_bin<double>(dir + "/kf_list.bin");
+  std::vector<FramePtr> frames;
+  for (int k = 0; k < n_frames; ++k) frames.push_back(load_frame(dir, &cam, k, n_levels));
+  Seed::batch_counter = 0;
+  Seed::seed_counter = 0;
+  std::map<Feature*, int> seed_id;
+  std::vector<double> conv, frame_rows, counts;
+  std::vector<Feature*> seed_features;
+  DetectorGrid grid(cam.width, cam.height, cell);
+  // the detector of the leg without device_seeds: the main thread's own context and pyramid
+  svo_hip_ctx* dctx = nullptr;
+  svo_hip_pyramid* dpyr = nullptr;
+  hip_bridge::check(svo_hip_ctx_create(&dctx, 0, nullptr), nullptr, "ctx_create");
+  hip_bridge::check(svo_hip_pyramid_create(dctx, cam.width, cam.height, n_levels, 1, &dpyr), dctx, "pyramid_create");
+  {
+    KeyframeDemoFilter df([&](Point* p, double s2) {
+      double row[5] = {(double)seed_id.at(p->obs_.front()), p->pos_[0], p->pos_[1], p->pos_[2], s2};
+      conv.insert(conv.end(), row, row + 5);
+      delete p;
+    }, &grid);
+    if (device_seeds) { df.enableDeviceSeedInit(n_pyr_levels, cell, threshold); df.record_detector_grid_ = true; }
+    auto wait_idle = [&]() { while (threaded && !df.idle()) std::this_thread::yield(); };
+    if (threaded) df.startThread();
+    size_t j = 0;
+    for (int k = 0; k < n_frames; ++k) {
+      FramePtr fr = frames[(size_t)k];
+      if (j < kf_list.size() && (int)kf_list[j] == k) {
+        const auto ex = read_bin<double>(dir + "/kf_existing_" + std::to_string(j) + ".bin");
+        for (size_t i = 0; i + 1 < ex.size(); i += 2)
+          fr->addFeature(new Feature(fr.get(), Vector2d{{ex[i], ex[i + 1]}}, Vector3d{{0.0, 0.0, 1.0}}, 0));
+        fr->setKeyframe();
+        std::vector<Feature*> fts;
+        std::vector<uint8_t> seen;
+        if (device_seeds) {
+          df.addKeyframe(fr, dm[0], dm[1]);
+          wait_idle();
+          fts = df.takeDeviceFeatures();
+          seen = df.last_detector_grid_;
+        } else {
+          if (threaded) { df.addFrame(fr); wait_idle(); }                       // updateSeeds(kf): the grid marks of :302-306
+          for (const Feature* f : fr->fts_) grid.setGridOccpuancy(f->px);       // setExistingFeatures
+          seen.assign(grid.grid_occupancy_.begin(), grid.grid_occupancy_.end());
+          const uint8_t* lv[SVO_HIP_MAX_LEVELS] = {nullptr};
+          for (size_t l = 0; l < fr->img_pyr_.size(); ++l) lv[l] = fr->img_pyr_[l].data();
+          hip_bridge::check(svo_hip_pyramid_upload(dpyr, 0, lv), dctx, "pyramid_upload");
+          hip_bridge::check(svo_hip_ctx_sync(dctx), dctx, "sync");
+          const size_t nc = seen.size();
+          std::vector<double> px(2 * nc), f(3 * nc);
+          std::vector<int32_t> level(nc);
+          int32_t n = 0;
+          const svo_hip_camera c = cam.toC();
+          hip_bridge::check(svo_hip_detect_features(dctx, dpyr, 0, &c, n_pyr_levels, cell, seen.data(), threshold, &n, px.data(), f.data(),
+                                                    level.data(), nullptr), dctx, "detect_features");
+          grid.resetGrid();
+          for (int32_t i = 0; i < n; ++i)
+            fts.push_back(new Feature(fr.get(), Vector2d{{px[2 * (size_t)i], px[2 * (size_t)i + 1]}},
+                                      Vector3d{{f[3 * (size_t)i], f[3 * (size_t)i + 1], f[3 * (size_t)i + 2]}}, level[(size_t)i]));
+          if (threaded) df.seedKeyframe(fr, dm[0], dm[1], fts);
+          else df.addKeyframe(fr, dm[0], dm[1], fts);
+        }
+        std::vector<double> px;
+        std::vector<int32_t> level;
+        for (Feature* f : fts) {
+          seed_id[f] = (int)seed_features.size();                             // = Seed::id: seeds are numbered as they are made
+          seed_features.push_back(f);
+          px.push_back(f->px[0]); px.push_back(f->px[1]); level.push_back(f->level);
+        }
+        write_bin(out + "/kf" + std::to_string(j) + "_grid.bin", seen);
+        write_bin(out + "/kf" + std::to_string(j) + "_px.bin", px);
+        write_bin(out + "/kf" + std::to_string(j) + "_level.bin", level);
+        counts.push_back((double)fts.size());
+        ++j;
+      } else {
+        df.addFrame(fr);
+        wait_idle();
+        const svo::hip_bridge::SeedBatchStats& ls = df.last_stats_;
+        frame_rows.insert(frame_rows.end(), {(double)k, (double)ls.n_seeds, (double)ls.n_uploaded});
+      }
+    }
+    if (threaded) df.stopThread();
+  }
+  write_bin(out + "/kf_counts.bin", counts);
+  write_bin(out + "/conv.bin", conv);
+  write_bin(out + "/frames.bin", frame_rows);
+  for (Feature* f : seed_features) delete f;
+  svo_hip_pyramid_destroy(dpyr);
+  svo_hip_ctx_destroy(dctx);
+  std::printf("svo_host_demo OK\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n|churn]\n", argv[0]); return 2; }
+  if (argc > 3 && std::string(argv[3]) == "keyframes") {
+    try {
+      bool device_seeds = false, threaded = false;
+      for (int a = 4; a < argc; ++a) {
+        device_seeds = device_seeds || std::string(argv[a]) == "device_seeds";
+        threaded = threaded || std::string(argv[a]) == "threaded";
+      }
+      return keyframes_demo(argv[1], argv[2], device_seeds, threaded);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "svo_host_demo FAILED: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n|churn|keyframes [device_seeds] [threaded]]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {

@@ -592,7 +592,20 @@ class DepthFilter {
     kf_pyr_.reset(new hip_bridge::PyramidCache(ctx_, 8));
     cur_pyr_.reset(new hip_bridge::PyramidCache(ctx_, 2));
   }
-  virtual ~DepthFilter() { stopThread(); mirror_.clear(); kf_pyr_.reset(); cur_pyr_.reset(); svo_hip_ctx_destroy(ctx_); }
+  virtual ~DepthFilter() {
+    stopThread(); mirror_.clear(); kf_pyr_.reset(); cur_pyr_.reset();
+    if (grid_dev_) svo_hip_free(ctx_, grid_dev_);
+    svo_hip_ctx_destroy(ctx_);
+  }
+
+  /// initializeSeeds on the device (svo_hip_seed_batch_create_detected) for the keyframes queued with
+  /// addKeyframe(frame, depth_mean, depth_min): FastDetector(img_width, img_height, cell_size, n_pyr_levels) and
+  /// Config::triangMinCornerScore() of the reference's constructor arguments (depth_filter.cpp:129-151)
+  void enableDeviceSeedInit(int n_pyr_levels, int cell_size, double detection_threshold) {
+    if (n_pyr_levels < 1 || cell_size < 1) throw std::invalid_argument("enableDeviceSeedInit");
+    dev_n_pyr_levels_ = n_pyr_levels; dev_cell_size_ = cell_size; dev_detection_threshold_ = detection_threshold;
+    device_seed_init_ = true;
+  }
 
   void startThread() { thread_stop_ = false; thread_ = new std::thread(&DepthFilter::updateSeedsLoop, this); }
   void stopThread() {
@@ -625,12 +638,39 @@ class DepthFilter {
       lock_t lock(frame_queue_mut_);
       new_keyframe_ = frame;
       new_keyframe_features_ = std::move(new_features);
+      new_keyframe_on_device_ = false;
       new_keyframe_set_ = true;
       seeds_updating_halt_ = true;
       frame_queue_cond_.notify_one();
     } else {
       initializeSeeds(frame, new_features);
     }
+  }
+  /// :109-123 with the detector inside the filter, as in the reference: no feature list.  The keyframe's existing features
+  /// (frame->fts_) and, on the threaded path, the seeds its update has just matched occupy the grid; the new features are detected
+  /// on the filter's own copy of the keyframe's pyramid and their seeds are born on the device.  The Feature objects the filter
+  /// creates belong to the caller, like handed-in ones: takeDeviceFeatures() returns those made since its last call.
+  void addKeyframe(FramePtr frame, double depth_mean, double depth_min) {
+    if (!device_seed_init_) throw std::logic_error("addKeyframe without features: enableDeviceSeedInit comes first");
+    new_keyframe_min_depth_ = depth_min;
+    new_keyframe_mean_depth_ = depth_mean;
+    if (thread_ != nullptr) {
+      lock_t lock(frame_queue_mut_);
+      new_keyframe_ = frame;
+      new_keyframe_features_.clear();
+      new_keyframe_on_device_ = true;
+      new_keyframe_set_ = true;
+      seeds_updating_halt_ = true;
+      frame_queue_cond_.notify_one();
+    } else {
+      initializeSeedsOnDevice(frame);
+    }
+  }
+  std::vector<Feature*> takeDeviceFeatures() {
+    lock_t lock(seeds_mut_);
+    std::vector<Feature*> out;
+    out.swap(device_features_);
+    return out;
   }
   void removeKeyframe(FramePtr frame) {                                        // :153-170
     seeds_updating_halt_ = true;
@@ -671,11 +711,67 @@ class DepthFilter {
     seeds_updating_halt_ = false;
   }
 
+  /// initializeSeeds (:129-151) as one device call: setExistingFeatures(frame->fts_) on the device grid, detection and seed
+  /// construction into a pool block, the grid reset behind it; one Feature and one list entry per returned feature; the batch
+  /// joins the mirror without an upload
+  void initializeSeedsOnDevice(FramePtr frame) {
+    seeds_updating_halt_ = true;
+    lock_t lock(seeds_mut_);
+    const hip_bridge::DeviceGrid grid = deviceGrid(*frame);
+    std::vector<double> px;
+    for (const Feature* ftr : frame->fts_) { px.push_back(ftr->px[0]); px.push_back(ftr->px[1]); }
+    hip_bridge::check(svo_hip_grid_mark_px(ctx_, (int)(px.size() / 2), px.data(), grid.cell_size, grid.grid_cols, grid.grid_rows,
+                                           grid.occupancy_dev), ctx_, "grid_mark_px");
+    if (record_detector_grid_) {
+      last_detector_grid_.resize((size_t)grid.grid_cols * grid.grid_rows);
+      hip_bridge::check(svo_hip_memcpy_d2h(ctx_, last_detector_grid_.data(), grid.occupancy_dev, last_detector_grid_.size()), ctx_, "grid d2h");
+    }
+    const int slot = kf_pyr_->slotOf(*frame);
+    const svo_hip_camera cam = frame->cam_->toC();
+    const size_t n_cells = (size_t)grid.grid_cols * grid.grid_rows;
+    std::vector<double> fpx(2 * n_cells), ff(3 * n_cells);
+    std::vector<int32_t> level(n_cells);
+    svo_hip_seed_batch* batch = nullptr;
+    int32_t n = 0;
+    hip_bridge::check(svo_hip_seed_batch_create_detected(ctx_, kf_pyr_->pyramid(), slot, &cam, dev_n_pyr_levels_, grid.cell_size,
+                                                         grid.occupancy_dev, 1, dev_detection_threshold_, (float)new_keyframe_mean_depth_,
+                                                         (float)new_keyframe_min_depth_, &batch, &n, fpx.data(), ff.data(), level.data(),
+                                                         nullptr), ctx_, "seed_batch_create_detected");
+    ++Seed::batch_counter;
+    std::list<Seed>::iterator first = seeds_.end();
+    for (int32_t i = 0; i < n; ++i) {
+      Feature* ftr = new Feature(frame.get(), Vector2d{{fpx[2 * (size_t)i], fpx[2 * (size_t)i + 1]}},
+                                 Vector3d{{ff[3 * (size_t)i], ff[3 * (size_t)i + 1], ff[3 * (size_t)i + 2]}}, level[(size_t)i]);
+      device_features_.push_back(ftr);
+      seeds_.push_back(Seed(ftr, (float)new_keyframe_mean_depth_, (float)new_keyframe_min_depth_));
+      if (i == 0) first = std::prev(seeds_.end());
+    }
+    mirror_.adopt(batch, first, (size_t)n, Seed::batch_counter, frame.get());
+    seeds_updating_halt_ = false;
+  }
+
+  /// the device grid of enableDeviceSeedInit for this frame's image size (allocated and zeroed when first needed)
+  hip_bridge::DeviceGrid deviceGrid(const Frame& frame) {
+    int gc = 0, gr = 0;
+    hip_bridge::check(svo_hip_detect_grid(frame.cam_->width, frame.cam_->height, dev_cell_size_, &gc, &gr), ctx_, "detect_grid");
+    if (grid_dev_ == nullptr || gc != grid_cols_ || gr != grid_rows_) {
+      if (grid_dev_) { hip_bridge::check(svo_hip_ctx_sync(ctx_), ctx_, "sync"); svo_hip_free(ctx_, grid_dev_); grid_dev_ = nullptr; }
+      void* p = nullptr;
+      hip_bridge::check(svo_hip_malloc(ctx_, &p, (size_t)gc * gr), ctx_, "malloc");
+      grid_dev_ = static_cast<uint8_t*>(p);
+      grid_cols_ = gc; grid_rows_ = gr;
+      const std::vector<uint8_t> zero((size_t)gc * gr, 0);
+      hip_bridge::check(svo_hip_memcpy_h2d(ctx_, grid_dev_, zero.data(), zero.size()), ctx_, "grid h2d");
+      hip_bridge::check(svo_hip_ctx_sync(ctx_), ctx_, "sync");
+    }
+    return hip_bridge::DeviceGrid{dev_cell_size_, grid_cols_, grid_rows_, grid_dev_};
+  }
+
   void updateSeedsLoop() {                                                      // :191-229
     while (true) {
       FramePtr frame;
       std::vector<Feature*> feats;
-      bool is_kf = false;
+      bool is_kf = false, on_device = false;
       {
         lock_t lock(frame_queue_mut_);
         while (frame_queue_.empty() && !new_keyframe_set_ && !thread_stop_) frame_queue_cond_.wait(lock);
@@ -687,14 +783,19 @@ class DepthFilter {
           frame = new_keyframe_;
           feats = std::move(new_keyframe_features_);
           is_kf = true;
+          on_device = new_keyframe_on_device_;
         } else {
           frame = frame_queue_.front();
           frame_queue_.pop();
         }
         busy_ = true;
       }
+      // (a keyframe whose seeds are made on the device: its update marks the device grid, :302-306)
+      grid_pass_ = is_kf && on_device;
       updateSeeds(frame);
-      if (is_kf) initializeSeeds(frame, feats);
+      grid_pass_ = false;
+      if (is_kf && on_device) initializeSeedsOnDevice(frame);
+      else if (is_kf) initializeSeeds(frame, feats);
       { lock_t lock(frame_queue_mut_); busy_ = false; }
     }
   }
@@ -734,7 +835,10 @@ class DepthFilter {
     if (seeds_.empty()) return;
     svo_hip_df_params prm{3, 10, 1000, options_.seed_convergence_sigma2_thresh};
     BatchHost host{this};
-    last_stats_ = mirror_.update(host, ctx_, seeds_, *frame, prm, Seed::batch_counter, options_.max_n_kfs, seeds_updating_halt_, sub_batch_);
+    hip_bridge::DeviceGrid grid{0, 0, 0, nullptr};
+    if (grid_pass_) grid = deviceGrid(*frame);
+    last_stats_ = mirror_.update(host, ctx_, seeds_, *frame, prm, Seed::batch_counter, options_.max_n_kfs, seeds_updating_halt_, sub_batch_,
+                                 grid_pass_ ? &grid : nullptr);
     total_uploaded_ += last_stats_.n_uploaded;
     if (last_stats_.n_device_errors) throw std::runtime_error(std::string("depth_filter_update: ") + svo_hip_last_error(ctx_));
   }
@@ -742,7 +846,9 @@ class DepthFilter {
  public:
   int sub_batch_ = 4096;                         ///< seeds per device batch (the halt flag is polled in between)
   hip_bridge::SeedBatchStats last_stats_;
-  long total_uploaded_ = 0;                      ///< seeds ever mirrored on the device: every seed exactly once
+  long total_uploaded_ = 0;                      ///< seeds ever uploaded to the device mirror (seeds born on the device: never)
+  bool record_detector_grid_ = false;            ///< tests: keep the grid as the device detector saw it (one more transfer a keyframe)
+  std::vector<uint8_t> last_detector_grid_;
  protected:
   DetectorGrid* feature_detector_ = nullptr;
   callback_t seed_converged_cb_;
@@ -758,6 +864,13 @@ class DepthFilter {
   FramePtr new_keyframe_;
   std::vector<Feature*> new_keyframe_features_;
   bool new_keyframe_set_ = false, busy_ = false;
+  bool new_keyframe_on_device_ = false;          // the queued keyframe came without features (enableDeviceSeedInit)
+  bool device_seed_init_ = false, grid_pass_ = false;
+  int dev_n_pyr_levels_ = 3, dev_cell_size_ = 30;
+  double dev_detection_threshold_ = 10.0;
+  uint8_t* grid_dev_ = nullptr;                  // the detector grid on the filter's context
+  int grid_cols_ = 0, grid_rows_ = 0;
+  std::vector<Feature*> device_features_;        // made by initializeSeedsOnDevice, not yet taken by the caller
   double new_keyframe_min_depth_ = 0.0, new_keyframe_mean_depth_ = 0.0;
   svo_hip_ctx* ctx_ = nullptr;
   std::unique_ptr<hip_bridge::PyramidCache> kf_pyr_, cur_pyr_;

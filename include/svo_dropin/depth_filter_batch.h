@@ -24,6 +24,12 @@
 // next call -- the list's size or its last seed id no longer match -- and the mirror is re-built from the list: seeds
 // still there keep their device state, the others are erased on the device too.
 //
+// A keyframe's seeds may also be BORN on the device (svo_hip_seed_batch_create_detected: DepthFilter::initializeSeeds as one
+// device call).  The host then pushes one list entry per returned feature and hands the batch over with adopt(): nothing is
+// uploaded for those seeds.  With a DeviceGrid given to update(), a keyframe's pass does not report its updated seeds
+// (report_updated = 0): svo_hip_seed_batch_mark_updated marks the device grid behind the pass on the stream instead of
+// Host::setGridOccupancy (:302-306); convergence and NaN events are handled as ever.
+//
 // Host policy (duck-typed; see the two users):
 //   Frame*  keyframeOf(const Seed&)                       it->ftr->frame
 //   void    feature(const Seed&, double px[2], double f[3], int* level)
@@ -57,6 +63,12 @@ struct SeedBatchStats {
   bool halted = false;
 };
 
+/// The detector's occupancy grid as a device buffer (svo_hip_detect_grid, svo_hip_malloc) of the depth filter's context
+struct DeviceGrid {
+  int cell_size, grid_cols, grid_rows;
+  uint8_t* occupancy_dev;
+};
+
 /// The device mirror of a std::list<Seed>: owned by the depth filter object, used under its seeds mutex.
 template <class SeedList>
 class DeviceSeedMirror {
@@ -81,6 +93,28 @@ class DeviceSeedMirror {
   template <class Host, class Frame>
   SeedBatchStats update(Host& host, svo_hip_ctx* ctx, SeedList& seeds, Frame& frame, const svo_hip_df_params& prm, int batch_counter,
                         int max_n_kfs, const volatile bool& halt, int sub_batch = 4096) {
+    return updateImpl(NoGrid(), host, ctx, seeds, frame, prm, batch_counter, max_n_kfs, halt, sub_batch, NULL);
+  }
+  /// The device-grid mode: on a keyframe the pass runs with report_updated = 0, svo_hip_seed_batch_mark_updated marks
+  /// *device_grid behind it on the stream, and Host::setGridOccupancy is not called.  (An overload of its own, so that users of
+  /// the plain form need not link svo_hip_seed_batch_mark_updated.)  device_grid == NULL: the plain form.
+  template <class Host, class Frame>
+  SeedBatchStats update(Host& host, svo_hip_ctx* ctx, SeedList& seeds, Frame& frame, const svo_hip_df_params& prm, int batch_counter,
+                        int max_n_kfs, const volatile bool& halt, int sub_batch, const DeviceGrid* device_grid) {
+    return updateImpl(WithGrid(), host, ctx, seeds, frame, prm, batch_counter, max_n_kfs, halt, sub_batch, device_grid);
+  }
+
+ private:
+  struct NoGrid {};
+  struct WithGrid {};
+  static int markUpdated(NoGrid, const std::vector<svo_hip_seed_batch*>&, const DeviceGrid*) { return SVO_HIP_OK; }
+  static int markUpdated(WithGrid, const std::vector<svo_hip_seed_batch*>& passed, const DeviceGrid* g) {
+    return svo_hip_seed_batch_mark_updated((int)passed.size(), passed.data(), g->cell_size, g->grid_cols, g->grid_rows, g->occupancy_dev);
+  }
+
+  template <class Mode, class Host, class Frame>
+  SeedBatchStats updateImpl(Mode mode, Host& host, svo_hip_ctx* ctx, SeedList& seeds, Frame& frame, const svo_hip_df_params& prm,
+                            int batch_counter, int max_n_kfs, const volatile bool& halt, int sub_batch, const DeviceGrid* device_grid) {
     SeedBatchStats st;
     if (sub_batch < 1) sub_batch = 1;
     if (halt) { st.halted = true; return st; }
@@ -112,6 +146,7 @@ class DeviceSeedMirror {
     double T_cur[7];
     host.pose7(frame, T_cur);
     const bool is_keyframe = host.isKeyframe(frame);
+    const bool mark_on_device = is_keyframe && device_grid != NULL;    // the grid marks of :302-306 stay on the device
 
     // ---- device: the batches of the frame through ONE set of launches (svo_hip_seed_batch_update_group_async), awaited in
     // list order
@@ -143,11 +178,18 @@ class DeviceSeedMirror {
         st.n_device_calls += (int)devs.size();
         const int rc = svo_hip_seed_batch_update_group_async((int)devs.size(), devs.data(), host.keyframePyramids(), slots.data(),
                                                              host.currentPyramids(), cur_slot, &cam, T_refs.data(), T_cur, &prm,
-                                                             is_keyframe ? 1 : 0);
+                                                             is_keyframe && !mark_on_device ? 1 : 0);
         // A failure leaves up to 8 batches at a time either enqueued or not (svo_hip.h): the collect loop below takes
         // every batch that has a pass pending -- its seeds WERE updated -- and skips the others, so nothing stays
         // pending into the next frame.
         if (rc != SVO_HIP_OK) ++st.n_device_errors;
+        if (mark_on_device) {
+          // behind the pass on the stream, one call for the frame's set: the batches whose pass was enqueued
+          std::vector<svo_hip_seed_batch*> passed;
+          for (size_t j = 0; j < devs.size(); ++j)
+            if (svo_hip_seed_batch_pending(devs[j])) passed.push_back(devs[j]);
+          if (!passed.empty() && markUpdated(mode, passed, device_grid) != SVO_HIP_OK) ++st.n_device_errors;
+        }
       }
     }
     // ---- the events, in list order: grid marks, callbacks, erasures (:302-337)
@@ -164,7 +206,7 @@ class DeviceSeedMirror {
         const svo_hip_seed_event& x = ev[j];
         if (x.index < 0 || (size_t)x.index >= b.its.size() || !b.alive[(size_t)x.index]) continue;
         It it = b.its[(size_t)x.index];
-        if (is_keyframe) host.setGridOccupancy(x.px_cur);           // :302-306
+        if (is_keyframe && !mark_on_device) host.setGridOccupancy(x.px_cur);   // :302-306
         if (x.status == SVO_HIP_SEED_CONVERGED) {                   // :310-331
           it->mu = x.mu; it->sigma2 = x.sigma2;
           host.converged(*it, x.xyz_world);
@@ -183,6 +225,37 @@ class DeviceSeedMirror {
     }
     remember(seeds);
     return st;
+  }
+
+ public:
+  /// A batch that was created on the device from a detection (svo_hip_seed_batch_create_detected) joins the mirror: the n
+  /// list entries the host has just pushed for it, `first` onwards, are its seeds 0..n-1 (batch id `batch_id`, keyframe `kf`).
+  /// The mirror owns the batch from here on.  As after reconcile(): the entries are known (where_), the batch stands at the end
+  /// of the batches -- the entries stand at the end of the list -- and the list's size and last id are remembered, so the next
+  /// update() finds nothing fresh and uploads nothing.  To be called with the mirror in line with the list as it was before
+  /// the n entries were pushed (update() leaves it so; an erasure behind the mirror's back in between is still noticed by the
+  /// next update(), which then re-reads the list).
+  template <class FramePtrT>
+  void adopt(svo_hip_seed_batch* batch, It first, size_t n, int batch_id, FramePtrT kf) {
+    if (batch == NULL) return;
+    if (n == 0) { svo_hip_seed_batch_destroy(batch); return; }
+    Batch nb;
+    nb.serial = next_serial_++;
+    nb.batch_id = batch_id;
+    nb.kf = kf;
+    nb.dev = batch;
+    nb.its.reserve(n);
+    It it = first;
+    for (size_t i = 0; i < n; ++i, ++it) {
+      nb.its.push_back(it);
+      Where w; w.batch_serial = nb.serial; w.index = (int)i; w.id = it->id;
+      where_[&*it] = w;
+    }
+    nb.alive.assign(n, 1);
+    nb.n_alive = (int)n;
+    known_size_ += n;
+    known_back_id_ = nb.its.back()->id;
+    batches_.push_back(nb);
   }
 
   /// Copy the device state (a, b, mu, sigma2) of every live seed into its list entry: before the host reads the list

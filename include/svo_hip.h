@@ -1067,6 +1067,60 @@ int svo_hip_detect_features(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int sl
 int svo_hip_seed_init_batch_dev(svo_hip_ctx* ctx, int n, double depth_mean, double depth_min, float* a_dev, float* b_dev,
                                 float* mu_dev, float* z_range_dev, float* sigma2_dev);
 
+/* ---- a new keyframe's seeds, detected and created on the device ------------------------------------------------
+ * What DepthFilter does when a keyframe is queued (depth_filter.cpp:191-229): updateSeeds(kf) marks the detector grid
+ * with the px_cur of every seed it updated (:302-306), initializeSeeds(kf) (:129-151) marks the keyframe's own features
+ * (setExistingFeatures, feature_detection.cpp:47-56), detects, creates one Seed per new feature (:36-45) and the
+ * detector resets its grid (feature_detection.cpp:121).  Here the grid is a plain device buffer of grid_cols * grid_rows
+ * bytes (svo_hip_detect_grid, svo_hip_malloc) -- what svo_hip_detect_features_dev reads as occupancy_dev -- and every
+ * step marks, reads or clears it where it lies.
+ *
+ * Marking is AbstractDetector::setGridOccpuancy (feature_detection.cpp:58-64): cell
+ *   k = (int)(px[1] / cell_size) * grid_cols + (int)(px[0] / cell_size),
+ * a double divided by an int and truncated towards zero; the flat index is the only range test, as in the reference
+ * (a pixel beyond the width whose k is valid marks the next row's cell).  Where the reference's .at() would throw or
+ * its cast is undefined -- k outside [0, grid_cols * grid_rows), a non-finite coordinate, a quotient beyond int --
+ * nothing is marked.  The only byte marking ever writes is 1. */
+
+/* setExistingFeatures over n level-0 pixels px[n][2]: enqueued on the context stream, does not wait; n = 0 is a no-op */
+int svo_hip_grid_mark_px_dev(svo_hip_ctx* ctx, int n, const double* px_dev, int cell_size, int grid_cols, int grid_rows,
+                             uint8_t* occupancy_dev);
+/* the same from a host array: the pixels are staged through the context's page-locked area (the call returns with that
+ * one transfer in flight; the area's next user waits for it) and svo_hip_grid_mark_px_dev runs behind it */
+int svo_hip_grid_mark_px(svo_hip_ctx* ctx, int n, const double* px_host, int cell_size, int grid_cols, int grid_rows,
+                         uint8_t* occupancy_dev);
+/* depth_filter.cpp:302-306 for a keyframe pass: the cell of px_cur of every seed whose status in the batch's last pass is
+ * >= SVO_HIP_SEED_UPDATED (updated, converged, NaN) -- the seeds a report_updated = 1 pass reports, without the events.
+ * The gate is the status, never px_cur: SVO_HIP_SEED_NO_MATCH seeds hold a non-finite px_cur, erased seeds a stale one.
+ * Enqueued behind whatever the batches' stream holds: legal while the pass is pending and after its collect, until the
+ * batch's next update.  One launch per set of up to 8 batches.  SVO_HIP_ERR_INVALID before anything is enqueued for
+ * batches of different contexts, a NULL batch or grid, non-positive sizes. */
+int svo_hip_seed_batch_mark_updated(int n_batches, svo_hip_seed_batch* const* batches, int cell_size, int grid_cols,
+                                    int grid_rows, uint8_t* occupancy_dev);
+/* setExistingFeatures(new_frame->fts_) from what the device holds: all features of the tracker's last frame, those
+ * whose point the pose refinement dropped included (they stay in fts_, pose_optimizer.cpp:154-157).  A lone tracker's
+ * or a group camera's handle; before or after svo_hip_tracker_promote_last_frame, after a removal or a compaction
+ * (pixels do not move).  Reads tracker state only.  SVO_HIP_ERR_STATE without a last frame.  SYNCHRONISES the
+ * tracker's stream before it returns, so that a grid owned by another context (the depth filter's) may be read or
+ * marked there next. */
+int svo_hip_tracker_mark_last_frame(svo_hip_tracker* trk, int cell_size, int grid_cols, int grid_rows,
+                                    uint8_t* occupancy_dev);
+/* initializeSeeds (depth_filter.cpp:129-151) as one device call: the detection of svo_hip_detect_features_dev -- same
+ * kernels, same refusals, same threshold quirk, same rules for f (cam is required here: every seed has a bearing) --
+ * written straight into a block of the context's seed-batch pool: px / f / level of the new features, the Seed
+ * constructor's a, b, mu, z_range, sigma2 (:36-45, as svo_hip_seed_init_batch_dev), alive = 1, status =
+ * SVO_HIP_SEED_ERASED until the first pass.  The block is laid out for the grid's cell count, the upper bound of n, and
+ * is taken from the pool's capacity class of the CELL COUNT, not of n (n is not known when the block is taken).
+ * occupancy_dev may be NULL (no cell is occupied); with clear_occupancy the grid is zeroed behind the detection
+ * (resetGrid(), feature_detection.cpp:121).  One synchronisation.  *n = number of new seeds; the host outputs px[n][2],
+ * f[n][3], level[n], score[n] (capacity: the cell count) may each be NULL.  n = 0 returns SVO_HIP_OK with *batch = NULL
+ * and the block back in the pool; a refused call takes no block.  The batch is an ordinary svo_hip_seed_batch. */
+int svo_hip_seed_batch_create_detected(svo_hip_ctx* ctx, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam,
+                                       int n_pyr_levels, int cell_size, uint8_t* occupancy_dev, int clear_occupancy,
+                                       double detection_threshold, double depth_mean, double depth_min,
+                                       svo_hip_seed_batch** batch, int32_t* n, double* px, double* f, int32_t* level,
+                                       float* score);
+
 #ifdef __cplusplus
 }
 #endif
