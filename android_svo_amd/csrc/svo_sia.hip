@@ -570,7 +570,10 @@ __global__ void sia_finish_kernel(const FrameConst* __restrict__ fc, FrameState*
 //     and constant over a level or an evaluation (camera, pose, doubled quaternion, image base, stride, scale, bounds) sits in
 //     scalar registers and none of it is spilled inside the loop (per-tile conditions are bits of one scalar, tested where they
 //     are used: prio_plan, n_have), row addresses are 32-bit offsets on the scalar image base, the in-image test is four
-//     f32 comparisons on the floors, and the usual division path is straight-line code;
+//     f32 comparisons on the floors, and the usual division path is straight-line code.  Its scalar bookkeeping is one bit
+//     test and one branch per event -- the priority is raised once and dropped once per evaluation, not set per tile -- and
+//     behind the loop the usual evaluation (no outside-the-image set changed) falls through to the wave reduction, whose
+//     sign-and-scale factor is a select on the factor's words and whose H rows are read without exec masks;
 //   * the Gauss-Newton state lives in LDS; the solve runs between two barriers: H^-1 by columns on six lanes when H
 //     changed, a 6x6 matrix-vector product otherwise, SE3::exp and the pose product on one lane.
 // Data-dependent exits are real `break`s here, so a converged frame costs nothing further.
@@ -984,23 +987,39 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
   const int favoured_tiles = (5 * my_tiles) / 8;                        // whole tiles at raised priority
   const int favoured_half = (5 * my_tiles) % 8 >= 4 ? favoured_tiles : -1;   // then the first half of this one
   auto tile_of = [&](int k) -> int { return k < my_tiles ? simd + 4 * (first_j + k) : n_tiles; };
-  // the priority schedule of a younger wave as ONE scalar (an older wave: 0): bit k = tile k starts at raised priority, bit
-  // 8 + k = at normal priority, bit 16 + k = it drops to normal half-way through tile k.  (Written as conditions on k, wave and
-  // favoured_* in the tile loop, the compiler kept one 64-bit lane mask per tile and condition alive across the whole
-  // kernel -- sixteen scalar registers that it spilled and restored inside the loop.)
   // how many of the wave's tiles exist (they are the first ones): one scalar, compared with k in the loops
   int n_have = 0;
 #pragma unroll
   for (int k = 0; k < TPW; ++k) n_have += tile_of(k) < n_tiles ? 1 : 0;
   n_have = __builtin_amdgcn_readfirstlane(n_have);
+  // The priority schedule of a younger wave as ONE scalar (an older wave: 0).  (Written as conditions on k, wave and
+  // favoured_* in the tile loop, the compiler kept one 64-bit lane mask per tile and condition alive across the whole
+  // kernel -- sixteen scalar registers that it spilled and restored inside the loop.)  The favoured tiles are the wave's
+  // first ones and the priority is normal when an evaluation begins, so the schedule is three events: bit 0 = raise at the
+  // head of tile 0, bit 8 + k = drop at the head of tile k (the first tile that is not favoured, when no tile is favoured
+  // by half), bit 16 + k = drop half-way through tile k.  Each event is one bit test and one branch; setting the priority
+  // again at the head of every later tile, as a per-tile schedule does, changes nothing.  One difference to such a schedule,
+  // none for the results: when the tile that carries the half-way drop does not exist in this frame (a short frame riding in
+  // a larger frame's launch; a tile's head runs either way, its pixel loop does not), the wave stays raised through the heads of
+  // its remaining tiles -- a projection and row loads each, no evaluation -- and drops behind the loop, so the older wave of
+  // its SIMD is held back that little longer.
   unsigned prio_plan = 0;
-  if (NW == 8 && wave >= 4) {
+  if (NW == 8 && wave >= 4 && (favoured_tiles > 0 || favoured_half == 0)) {
+    prio_plan = 1u;
 #pragma unroll
     for (int k = 0; k < TPW; ++k)
-      prio_plan |= ((k < favoured_tiles || k == favoured_half) ? 1u : 0x100u) << k | (k == favoured_half ? 0x10000u << k : 0u);
+      prio_plan |= (k > 0 && favoured_half < 0 && k == favoured_tiles ? 0x100u << k : 0u) | (k == favoured_half ? 0x10000u << k : 0u);
   }
   // per-tile H row of this wave (lane e keeps entry e): in LDS, read once per tile and evaluation
   auto th_get = [&](int k) -> double { return lane < 21 ? s_th[(wave * TPW + k) * ROWW + lane] : 0.0; };
+  // The same row for the sum of which only lanes 0..20 are ever stored: every lane reads, with a clamped index, so that no
+  // exec mask is saved and restored around each read and each addition.  Used behind the tile loop by the one- to four-tile
+  // shapes; the exact-rows instances keep the masked read there and the register-bound shapes in their loop: the clamped
+  // index cost <8,3,2,1>, <8,5,2,0> and <8,5,2,1> one to four spilled VGPRs.
+  const int th_lane = lane < 21 ? lane : 0;
+  auto th_get_all = [&](int k) -> double {
+    return VARIANT == FUSED_EXACT_ROWS ? th_get(k) : s_th[(wave * TPW + k) * ROWW + th_lane];
+  };
   auto th_set = [&](int k, double v) { if (lane < 21) s_th[(wave * TPW + k) * ROWW + lane] = v; };
 
   if (threadIdx.x == 0) {
@@ -1233,7 +1252,10 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         // the younger wave of a SIMD is favoured by the arbiter during its first tiles (see tile_of)
         unsigned prio = prio_plan;
         if (TPW > 1) asm volatile("" : "+s"(prio));          // opaque: tested bit by bit here, nothing derived from it is kept
-        if (NW == 8) { if (prio & (1u << k)) __builtin_amdgcn_s_setprio(1); else if (prio & (0x100u << k)) __builtin_amdgcn_s_setprio(0); }
+        // (one `if` per event, never an if / else on two bits: that form the compiler turned into lane masks and three to four
+        // branches per tile.  A drop is expected not to happen, so that the tile's code falls through.)
+        if (NW == 8 && k == 0 && (prio & 1u) != 0) __builtin_amdgcn_s_setprio(1);
+        if (NW == 8 && k > 0 && __builtin_expect((prio & (0x100u << k)) != 0, 0)) __builtin_amdgcn_s_setprio(0);
 
         // this tile's interpolated patches: from LDS, or what was asked for while the previous tile was computed
         float4 Wq[8];
@@ -1299,7 +1321,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
           }
 #pragma unroll
           for (int y = 0; y < 4; ++y) {
-            if (NW == 8 && y == 2 && (prio & (0x10000u << k))) __builtin_amdgcn_s_setprio(0);
+            if (NW == 8 && y == 2 && __builtin_expect((prio & (0x10000u << k)) != 0, 0)) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
               const float refv = W[y + 1][x + 1];                                  // half the reference value
@@ -1414,7 +1436,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
             th_set(k, t);
           }
         }
-        if (LEAN && !TORD) { const double thk = th_get(k); if (lane < 21) accH += thk; }
+        if (LEAN && !TORD) accH += th_get(k);                  // (every lane adds, lanes 21.. a zero: only lanes 0..20 are stored)
       }
 
       __builtin_amdgcn_s_setprio(0);
@@ -1423,7 +1445,10 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
       // wave reduces: ~350 instructions per tile whatever the number of patches; walking the patches one after the
       // other -- a dependent load and a rank update each -- cost ~500 cycles per patch, and a coarse level can have 45
       // of a tile's 64 outside: the slowest of 64 scenes spent 9 % of its time there)
-      if (!CORR_IN_LOOP && gone_changed) {                     // wave-uniform
+      // wave-uniform; marked unlikely, so that the usual evaluation falls through -- in the per-wave instances only: in the
+      // tile-order ones the mark cost <8,5,2,0,true> 19 spilled VGPRs and the six-tile shape 0.7 % of its time
+      const bool any_gone_changed = gone_changed != 0u;
+      if (!CORR_IN_LOOP && (TORD ? any_gone_changed : (bool)__builtin_expect(any_gone_changed, 0))) {
 #pragma unroll
         for (int k = 0; k < TPW; ++k) {
           if (!((gone_changed >> k) & 1u)) continue;
@@ -1442,11 +1467,10 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         }
       }
       if (!LEAN && !TORD) {
+        // rows of tiles that do not exist are zero.  Every lane adds (lanes 21.. entry 0 again, or zeros): only lanes 0..20 are
+        // stored below, and theirs are the same additions in the same order
 #pragma unroll
-        for (int k = 0; k < TPW; ++k) {                        // rows of tiles that do not exist are zero
-          const double thk = th_get(k);
-          if (lane < 21) accH += thk;
-        }
+        for (int k = 0; k < TPW; ++k) accH += th_get_all(k);
       }
 
       pf_off = off0;
@@ -1464,7 +1488,21 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         const double t = wave_reduce8(v8);
         const int j = lane >> 3;
         // undo the halved weights: Jres moments x2, chi2 x4 (exact)
-        const double sgn = (j == 0 || j == 1 || j == 4) ? 2.0 * jscale : (j < 6 ? -2.0 * jscale : (j == 6 ? 4.0 : 1.0));
+        double sgn;
+        if constexpr (LEAN) {
+          // the register-bound shapes keep the chain of conditionals: the words below cost <8,5,2,0> a spilled VGPR.  (So did a
+          // helper shared with row_scale further down: <8,5,2,0> 66 -> 67, <8,5,2,1> 85 -> 89.  The chain stays written out.)
+          sgn = (j == 0 || j == 1 || j == 4) ? 2.0 * jscale : (j < 6 ? -2.0 * jscale : (j == 6 ? 4.0 : 1.0));
+        } else {
+          // the same factor selected on its two words: as a chain of f64 conditionals it was five branches on lane masks, most
+          // of them taken, in every evaluation.  -(2 jscale) is 2 jscale with the sign bit flipped and the same low word, so
+          // the factor keeps its bits.
+          const double pos2 = 2.0 * jscale;
+          const unsigned flip = ((0x2cu >> j) & 1u) << 31;                                  // j = 2, 3, 5: negative
+          const unsigned sgn_hi = j < 6 ? (unsigned)__double2hiint(pos2) ^ flip : (j == 6 ? 0x40100000u : 0x3ff00000u);   // 4.0, 1.0
+          const unsigned sgn_lo = j < 6 ? (unsigned)__double2loint(pos2) : 0u;
+          sgn = __hiloint2double((int)sgn_hi, (int)sgn_lo);
+        }
         if (lane < 21) red[wave][lane] = accH;
         if ((lane & 7) == 0) red[wave][21 + j] = t * sgn;
       }
