@@ -919,6 +919,14 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
   // of a tile's patches at once with the factored rows) round differently.  The tile-order instances all take the second
   // one, whatever their shape: a frame's H rows must not depend on the shape class of the launch either.
   constexpr bool CORR_IN_LOOP = LEAN && !TORD;
+  // Two changes to the serial part between an evaluation's barriers (see there) are taken by the shapes whose register
+  // allocation they leave alone (-Rpass-analysis=kernel-resource-usage: no spilled VGPR, no byte of scratch or LDS more than
+  // before in any instance); the register-bound shapes, the 4-wave shape with four tiles per wave and the instances named here
+  // keep the earlier code.  WIN_DECIDE: the H-unchanged test and the |x| <= eps exit as one compare per lane and a scalar
+  // test of the mask.  WIN_COEF_FIRST: wave 0's exp series coefficients asked for ahead of the prefetched image rows.
+  constexpr bool WIN_FOUR = TPW == 4 && (VARIANT != FUSED_PLAIN || TORD);
+  constexpr bool WIN_DECIDE = !LEAN && !(TPW == 4 && NW == 4) && !(TPW == 3 && VARIANT == FUSED_EXACT_ROWS && !TORD);
+  constexpr bool WIN_COEF_FIRST = !LEAN && !(TPW == 4 && NW == 4) && !WIN_FOUR;
   const bool extra_lds = wave_of_thread() < n_extra;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   // The interpolated reference patch of every feature -- the 32 values W from which reference value, dx and dy of its
@@ -1206,6 +1214,8 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
 #pragma unroll
     for (int j = 0; j < 5; ++j) pf[j] = make_uint2(0u, 0u);
     for (int iter = 0; iter < prm.n_iter; ++iter) {
+      // (Nothing may be declared in this loop ahead of the `break`: a variable in scope there changes the block order the
+      // compiler starts from, and with it the register allocation of every instance -- five of them spilled more for a bool.)
       if (s_done) break;                                     // block-uniform (read after a barrier)
 #ifdef SVO_STAMPS
       const long long t0 = __builtin_amdgcn_s_memtime();
@@ -1473,6 +1483,15 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         for (int k = 0; k < TPW; ++k) accH += th_get_all(k);
       }
 
+      // Wave 0's column of the exp series table, for the solve between the barriers.  Loads return in order, so these go
+      // out AHEAD of the image rows below: wherever the compiler then puts a wait that covers one of them, it covers no
+      // image row.  (Asked for behind the rows, a wait on the first of them -- which one build placed at the head of the
+      // serial part, for a register it reused there -- was a wait on all five rows, on the critical path of all waves.)
+      double coef[8];
+      if (WIN_COEF_FIRST && wave == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) coef[k] = kExpSeries[k * 4 + (lane & 3)];
+      }
       pf_off = off0;
 #pragma unroll
       for (int j = 0; j < 5; ++j) pf[j] = load_row8(cur_img + (unsigned)(off0 + j * stride));
@@ -1515,7 +1534,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
       // is one of the older waves and gets there early), and everything nobody waits for (counters, chi2, the
       // rollback copy of the pose) is written AFTER the second one.
       double chi2_old = 0.0, nres_old = 0.0, hc_prev = 0.0;
-      double coef[8], inv_row[6], cur[7];
+      double inv_row[6], cur[7];
       double row_scale = 1.0;                // TORD, wave 0: what the frame's sum on this lane is multiplied by (1 for H)
       int it = 0, stop_old = 0, iters_l = 0, fac_valid = 0;
       if (wave == 0) {
@@ -1528,8 +1547,10 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         for (int i = 0; i < 7; ++i) cur[i] = s_model[i];        // (= T, which lives in scalar registers that are needed elsewhere by now)
         chi2_old = s_chi2; nres_old = s_nres; hc_prev = s_Hc[lane < 21 ? lane : 0];   // H of the previous evaluation
         it = s_iter; stop_old = s_stop; iters_l = s_iters[level]; fac_valid = s_fac_valid;
+        if (!WIN_COEF_FIRST) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) coef[k] = kExpSeries[k * 4 + (lane & 3)];      // this lane's column of the exp series table
+          for (int k = 0; k < 8; ++k) coef[k] = kExpSeries[k * 4 + (lane & 3)];    // this lane's column of the exp series table
+        }
 #pragma unroll
         for (int j = 0; j < 6; ++j) inv_row[j] = s_inv[(lane < 6 ? lane : 0) * 6 + j];   // lanes 0..5: their row of H^-1
       }
@@ -1570,8 +1591,16 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
         // H is the sum of the per-level tile rows minus the patches outside the image at this evaluation: as long as
         // that set does not change it is bit for bit the H of the previous evaluation, and what was derived from it
         // is reused (a deterministic function of H, so the result is the same number)
-        const bool h_same = lane >= 21 || __double_as_longlong(v) == __double_as_longlong(hc_prev);
-        const bool reuse = fac_valid != 0 && __ballot(!h_same) == 0ull;            // wave-uniform
+        // (one compare on all lanes and the mask of the 21 that hold H, tested by the scalar unit: the lanes above hold
+        // Jres and the counts, which differ at every evaluation)
+        bool reuse;                                                                // wave-uniform
+        if (WIN_DECIDE) {
+          const unsigned long long h_diff = __ballot(__double_as_longlong(v) != __double_as_longlong(hc_prev)) & 0x1fffffull;
+          reuse = fac_valid != 0 && h_diff == 0ull;
+        } else {
+          const bool h_same = lane >= 21 || __double_as_longlong(v) == __double_as_longlong(hc_prev);
+          reuse = fac_valid != 0 && __ballot(!h_same) == 0ull;
+        }
 #ifdef SVO_STAMPS
         const long long q0 = __builtin_amdgcn_s_memtime();
         if (lane == 0) s_stamp[5] += q0 - t2;
@@ -1608,10 +1637,18 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
 #endif
         // solve()/update() of S/sparse_img_align.cpp:291-308 inside the loop of I/nlls_solver_impl.hpp:35-99
         const bool stop_now = stop_old != 0 || x[0] != x[0];                       // NaN -> stop_ (:52-59)
-        bool worse = false;
+        bool worse = false, eps_done = false;
         if (prm.early_stop) {                                                      // the reference's exits need chi2 now
           new_chi2 = (double)((float)readlane_f64(v, 27) / (float)readlane_f64(v, 28));   // (:285)
           worse = it > 0 && new_chi2 > chi2_old;
+          if (WIN_DECIDE) {
+            // |x| <= eps (:97-98) where the whole wave still runs, on the six lanes that formed x.  The reference's test is "the
+            // maximum of the |x_i| that are not NaN, starting from -1, is <= eps"; a maximum is <= eps exactly when each of
+            // its terms is, so lane i < 6 tests |x_i| and lane 6 the -1 (which decides for a negative or NaN eps and for an
+            // all-NaN x): one compare per lane and a scalar test of the mask, instead of a chain of selects on scalars.
+            const double w = lane < 6 ? fabs(xi) : -1.0;
+            eps_done = (__ballot(!(w <= prm.eps) && w == w) & 0x7full) == 0ull;
+          }
         }
         rollback = worse || stop_now;                                              // wave-uniform
         if (lane == 0) {
@@ -1624,10 +1661,14 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
             // (the exits first: behind the cold call below nothing is left to do, so no scalar has to outlive it)
             bool done = it + 1 >= prm.n_iter;
             if (prm.early_stop) {                                                  // :97-98
-              double mxn = -1;
+              if (WIN_DECIDE) {
+                done = done || eps_done;
+              } else {
+                double mxn = -1;
 #pragma unroll
-              for (int i = 0; i < 6; ++i) { double a = fabs(x[i]); if (a > mxn) mxn = a; }
-              if (mxn <= prm.eps) done = true;
+                for (int i = 0; i < 6; ++i) { double a = fabs(x[i]); if (a > mxn) mxn = a; }
+                if (mxn <= prm.eps) done = true;
+              }
             }
             if (done) s_done = 1;
 #ifdef SVO_STAMPS
