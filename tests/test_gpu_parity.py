@@ -1356,6 +1356,49 @@ def test_converged_seed_records_packed_on_device(ctx):
     sb.free(); kf.destroy(); cf.destroy()
 
 
+# 262 144 seeds = 1024 blocks of 256 = one chunk of the block scan: the sizes around it carry a total from chunk to chunk
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 262144, 262145, 2 * 262144 + 77])
+def test_converged_seed_compaction_across_scan_chunks(ctx, n):
+    """svo_hip_seed_compact_converged_dev on its own, over status arrays with runs of 256-seed blocks without a converged
+    seed, runs of blocks with nothing else, and random blocks; the blocks on both sides of a chunk boundary hold converged
+    seeds.  Expected records and count from numpy: ascending index, id_offset + i, mu and sigma2 widened to f64, xyz."""
+    import ctypes as C
+    import torch
+    rng = np.random.default_rng(20260 + n)
+    n_blocks = (n + 255) // 256
+    kinds = np.full(n_blocks, 2)                               # 0: no converged seed, 1: only converged seeds, 2: random
+    if n_blocks >= 9:
+        runs = [(0, 3), (1, 2), (2, 4)]
+        while sum(r[1] for r in runs) < n_blocks:
+            runs.append((int(rng.integers(0, 3)), int(rng.integers(1, 40))))
+        kinds = np.concatenate([np.full(length, k) for k, length in runs])[:n_blocks]
+        assert all((kinds == k).any() for k in (0, 1, 2))
+    others = np.array([hip.SEED_ERASED, hip.SEED_BEHIND, hip.SEED_NOT_IN_FRAME, hip.SEED_NO_MATCH, hip.SEED_UPDATED, hip.SEED_NAN])
+    kind_of_seed = np.repeat(kinds, 256)[:n]
+    conv = np.where(kind_of_seed == 2, rng.random(n) < 0.3, kind_of_seed == 1)
+    for edge in (262144, 2 * 262144):                          # the last block of a chunk and the first of the next
+        conv[[i for i in (edge - 1, edge) if i < n]] = True
+    status = np.where(conv, hip.SEED_CONVERGED, others[rng.integers(0, len(others), n)]).astype(np.int32)
+    mu = rng.random(n, dtype=np.float32) + np.float32(0.1)
+    sigma2 = rng.random(n, dtype=np.float32) * np.float32(1e-3)
+    xyz = rng.standard_normal((n, 3))
+    id_offset = 3_000_000_017                                  # a rank's first seed id: beyond 32 bits, exact in f64
+    dev = [torch.from_numpy(a).cuda() for a in (status, mu, sigma2, xyz)]
+    rec = torch.full((n, 6), -1.0, dtype=torch.float64, device="cuda")
+    cnt = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ctx.check(ctx.lib.svo_hip_seed_compact_converged_dev(
+        ctx.h, n, C.c_longlong(id_offset), C.c_void_p(dev[0].data_ptr()), C.c_void_p(dev[1].data_ptr()), C.c_void_p(dev[2].data_ptr()),
+        C.c_void_p(dev[3].data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(cnt.data_ptr())), "seed_compact_converged")
+    ctx.sync()
+    idx = np.nonzero(conv)[0]
+    assert int(cnt.item()) == len(idx)
+    want = np.column_stack([(id_offset + idx).astype(np.float64), mu[idx].astype(np.float64), sigma2[idx].astype(np.float64), xyz[idx]])
+    got = rec.cpu().numpy()
+    np.testing.assert_array_equal(got[:len(idx)], want)
+    np.testing.assert_array_equal(got[len(idx):], -1.0)        # nothing written behind the records
+
+
 def test_frame_pipeline_stages_together(ctx):
     """The per-frame data path of FrameHandlerMono::processFrame on the device, stage by stage against the oracle chain:
     SparseImgAlign -> reprojection matching (findMatchDirect) -> pose_optimizer::optimizeGaussNewton -> Point::optimize."""

@@ -64,6 +64,37 @@ def test_resident_batch_equals_the_stateless_pass_over_several_frames(ctx, n):
     sb.free()
 
 
+def test_events_across_scan_chunks(ctx):
+    """280 000 seeds are 1094 blocks of 256, more than the 1024 one chunk of the event scan takes: the events behind seed
+    262 144 get their places from the total the first chunk carries over.  One keyframe pass against the stateless pass."""
+    reps, chunk = 14, 1024 * 256
+    sc, kf, cf, s2 = _case(ctx, 20000, 0.0045, 1280, 720)
+    px, f, level, a, b, mu, z_range, s2 = (np.concatenate([x] * reps) for x in (sc.px, sc.f, sc.level, sc.a, sc.b, sc.mu, sc.z_range, s2))
+    n = len(level)
+    assert n == 280000 and (n + 255) // 256 > 1024
+    sb = hip.SeedBatch(ctx, px, f, level, a, b, mu, z_range, s2)
+    rs = hip.ResidentSeeds(ctx, px, f, level, a, b, mu, z_range, s2)
+    hip.depth_filter_update(ctx, kf, 0, cf, 0, sc.cam, sc.T_ref_w, sc.T_cur_w, sb)
+    ctx.sync()
+    st = sb.status.download()
+    ev, counts = rs.update(kf, 0, cf, 0, sc.cam, sc.T_ref_w, sc.T_cur_w, report_updated=True)
+    want = (st == hip.SEED_CONVERGED) | (st == hip.SEED_NAN) | (st >= hip.SEED_UPDATED)
+    idx = np.nonzero(want)[0]
+    assert len(ev) > 512                                              # the packed path: events fetched from device memory
+    assert (idx >= chunk).any() and idx[idx >= chunk][0] in ev["index"]      # the first event of the second chunk
+    assert np.array_equal(ev["index"], idx)                           # ascending seed index = list order
+    assert np.array_equal(ev["status"], st[idx])
+    assert np.array_equal(ev["mu"], sb.mu.download()[idx]) and np.array_equal(ev["sigma2"], sb.sigma2.download()[idx])
+    assert np.array_equal(ev["px_cur"], sb.px_cur.download()[idx])
+    conv = ev["status"] == hip.SEED_CONVERGED
+    assert conv.any() and np.array_equal(ev["xyz_world"][conv], sb.xyz.download()[idx][conv])
+    assert counts[0] == 0
+    for s_ in range(6):
+        assert counts[s_ + 1] == int((st == s_).sum()), s_
+    rs.destroy()
+    sb.free()
+
+
 def test_erased_seeds_are_left_alone_and_first_pass_matches_the_oracle(ctx):
     from oracle import orc
     n = 3000

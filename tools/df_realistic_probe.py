@@ -11,8 +11,12 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from android_svo_amd import hip, seedsynth  # noqa: E402
 
+SIZES = ((4, 500), (4, 2000), (8, 300), (1, 500), (1, 2000), (1, 4000), (1, 8000), (2, 8000), (1, 16000))
+if len(sys.argv) > 1:                                    # e.g. 4x500,8x300,1x16000: only these (keyframes x seeds)
+    SIZES = tuple(tuple(int(v) for v in s.split("x")) for s in sys.argv[1].split(","))
+
 ctx = hip.Context(0)
-for n_b, n_s in ((4, 500), (4, 2000), (8, 300), (1, 500), (1, 2000), (1, 4000), (1, 8000), (2, 8000), (1, 16000)):
+for n_b, n_s in SIZES:
     mk = seedsynth.make_multi_keyframe_case((n_s,) * n_b, seed=9)
     kf = hip.Pyramid(ctx, 640, 480, 5, n_b)
     cf = hip.Pyramid(ctx, 640, 480, 5, 1)

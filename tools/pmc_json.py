@@ -11,7 +11,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the sources the profiled kernels are compiled from: bench.py refuses a profile whose hashes differ from the tree's
 PROFILED_SOURCES = ("android_svo_amd/csrc/svo_sia.hip", "android_svo_amd/csrc/svo_device_math.h", "android_svo_amd/csrc/Makefile")
 # ... and the depth-filter kernels' (kind "df": tools/pmc_c2.sh)
-PROFILED_SOURCES_DF = ("android_svo_amd/csrc/svo_depth.hip", "android_svo_amd/csrc/svo_align_device.h",
+PROFILED_SOURCES_DF = ("android_svo_amd/csrc/svo_depth.hip", "android_svo_amd/csrc/svo_depth_types.h",
+                       "android_svo_amd/csrc/svo_depth_align.h", "android_svo_amd/csrc/svo_depth_seed.h",
+                       "android_svo_amd/csrc/svo_depth_search.h", "android_svo_amd/csrc/svo_depth_events.h",
+                       "android_svo_amd/csrc/svo_align_device.h",
                        "android_svo_amd/csrc/svo_match_device.h", "android_svo_amd/csrc/svo_device_math.h",
                        "android_svo_amd/csrc/Makefile")
 
