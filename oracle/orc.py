@@ -188,18 +188,33 @@ def compute_tau(T_ref_cur, f, z, px_error_angle):
                                      C.c_double(px_error_angle))
 
 
+# svo_orc_epi_step: one index of the search loop
+EPI_STEP_DTYPE = np.dtype([("uv", np.float64, (2,)), ("px", np.float64, (2,)), ("pxi", np.int32, (2,)), ("dup", np.int32),
+                           ("in_frame", np.int32), ("score", np.int32)], align=True)
+
+
 def find_epipolar_match(cam, ref_pyr, cur_pyr, T_cur_ref, px_ref, f_ref, level_ref, d_est, d_min, d_max,
-                        n_pyr_levels=3, align_max_iter=10, max_steps=1000) -> EpiResult:
+                        n_pyr_levels=3, align_max_iter=10, max_steps=1000, trace=False):
+    """Returns the EpiResult; with trace=True (EpiResult, structured array with one EPI_STEP_DTYPE record per index of
+    the search loop -- empty on paths 0 and 2)."""
     c = camera(cam)
     out = EpiResult()
     T = f64(T_cur_ref)
     p = f64(px_ref)
     ff = f64(f_ref)
-    lib().svo_orc_find_epipolar_match_direct(
-        C.byref(c), pyr_ptrs(ref_pyr), pyr_ptrs(cur_pyr), _p(T, C.c_double), _p(p, C.c_double),
-        _p(ff, C.c_double), C.c_int(level_ref), C.c_double(d_est), C.c_double(d_min), C.c_double(d_max),
-        C.c_int(n_pyr_levels), C.c_int(align_max_iter), C.c_int(max_steps), C.byref(out))
-    return out
+    args = (C.byref(c), pyr_ptrs(ref_pyr), pyr_ptrs(cur_pyr), _p(T, C.c_double), _p(p, C.c_double),
+            _p(ff, C.c_double), C.c_int(level_ref), C.c_double(d_est), C.c_double(d_min), C.c_double(d_max),
+            C.c_int(n_pyr_levels), C.c_int(align_max_iter), C.c_int(max_steps), C.byref(out))
+    if not trace:
+        lib().svo_orc_find_epipolar_match_direct(*args)
+        return out
+    assert EPI_STEP_DTYPE.itemsize == 56
+    cap = int(max_steps) + 2
+    steps = np.zeros(cap, dtype=EPI_STEP_DTYPE)
+    n = C.c_int(0)
+    lib().svo_orc_find_epipolar_match_direct_trace(*args, steps.ctypes.data_as(C.c_void_p), C.c_int(cap), C.byref(n))
+    assert n.value <= cap
+    return out, steps[:n.value].copy()
 
 
 def update_seeds(cam, ref_pyr, cur_pyr, T_ref_w, T_cur_w, px, f, level, a, b, mu, z_range, sigma2,

@@ -1141,13 +1141,15 @@ int svo_orc_depth_from_triangulation(const double T_search_ref[7], const double 
   return 1;
 }
 
-/* S/matcher.cpp:207-355 */
-int svo_orc_find_epipolar_match_direct(
+/* S/matcher.cpp:207-355.  `steps` (may be NULL) receives one record per index of the search loop, at most `cap` of
+ * them; *n_out the number of loop indices visited.  Both entry points below run this one body. */
+static int epi_match_body(
     const svo_orc_camera* cam, const uint8_t* const* ref_pyr, const uint8_t* const* cur_pyr,
     const double T_cur_ref[7], const double px_ref[2], const double f_ref[3], int level_ref,
     double d_estimate, double d_min, double d_max, int n_pyr_levels, int align_max_iter,
-    int max_epi_search_steps, svo_orc_epi_result* o) {
+    int max_epi_search_steps, svo_orc_epi_result* o, svo_orc_epi_step* steps, int cap, int* n_out) {
   memset(o, 0, sizeof(*o));
+  if (n_out) *n_out = 0;
   const int halfpatch = 4, patch_size = 8;
   const int zmssd_threshold = 2000 * 64;
   int zmssd_best = zmssd_threshold;
@@ -1215,11 +1217,21 @@ int svo_orc_find_epipolar_match_direct(
     svo_orc_world2cam_uv(cam, uv, px);
     const int pxi_x = (int)(px[0] / (1 << search_level) + 0.5);
     const int pxi_y = (int)(px[1] / (1 << search_level) + 0.5);
+    svo_orc_epi_step* st = (steps && i < (size_t)cap) ? steps + i : NULL;
+    if (n_out) *n_out = (int)i + 1;
+    if (st) {
+      st->uv[0] = uv[0]; st->uv[1] = uv[1]; st->px[0] = px[0]; st->px[1] = px[1];
+      st->pxi[0] = pxi_x; st->pxi[1] = pxi_y;
+      st->dup = (pxi_x == last_x && pxi_y == last_y);
+      st->in_frame = is_in_frame_level(cam, pxi_x, pxi_y, patch_size, search_level);
+      st->score = -1;
+    }
     if (pxi_x == last_x && pxi_y == last_y) continue;
     last_x = pxi_x; last_y = pxi_y;
     if (!is_in_frame_level(cam, pxi_x, pxi_y, patch_size, search_level)) continue;
     const uint8_t* cur_patch_ptr = cur_img + (pxi_y - halfpatch) * ccols + (pxi_x - halfpatch);
     const int zmssd = svo_orc_zmssd(patch, cur_patch_ptr, ccols);
+    if (st) st->score = zmssd;
     o->n_zmssd++;
     if (zmssd < zmssd_best) { zmssd_best = zmssd; uv_best[0] = uv[0]; uv_best[1] = uv[1]; }
   }
@@ -1239,6 +1251,24 @@ int svo_orc_find_epipolar_match_direct(
     return 0;
   }
   return 0;
+}
+
+int svo_orc_find_epipolar_match_direct(
+    const svo_orc_camera* cam, const uint8_t* const* ref_pyr, const uint8_t* const* cur_pyr,
+    const double T_cur_ref[7], const double px_ref[2], const double f_ref[3], int level_ref,
+    double d_estimate, double d_min, double d_max, int n_pyr_levels, int align_max_iter,
+    int max_epi_search_steps, svo_orc_epi_result* o) {
+  return epi_match_body(cam, ref_pyr, cur_pyr, T_cur_ref, px_ref, f_ref, level_ref, d_estimate, d_min, d_max, n_pyr_levels,
+                        align_max_iter, max_epi_search_steps, o, NULL, 0, NULL);
+}
+
+int svo_orc_find_epipolar_match_direct_trace(
+    const svo_orc_camera* cam, const uint8_t* const* ref_pyr, const uint8_t* const* cur_pyr,
+    const double T_cur_ref[7], const double px_ref[2], const double f_ref[3], int level_ref,
+    double d_estimate, double d_min, double d_max, int n_pyr_levels, int align_max_iter,
+    int max_epi_search_steps, svo_orc_epi_result* o, svo_orc_epi_step* steps, int cap, int* n_out) {
+  return epi_match_body(cam, ref_pyr, cur_pyr, T_cur_ref, px_ref, f_ref, level_ref, d_estimate, d_min, d_max, n_pyr_levels,
+                        align_max_iter, max_epi_search_steps, o, steps, cap, n_out);
 }
 
 /* S/matcher.cpp:156-202 without Point::getCloseViewObs (host bookkeeping: the caller passes the

@@ -195,6 +195,24 @@ int svo_orc_find_epipolar_match_direct(
     double d_estimate, double d_min, double d_max, int n_pyr_levels, int align_max_iter,
     int max_epi_search_steps, svo_orc_epi_result* out);
 
+/* One index i of the search loop (matcher.cpp:299-321) as the function above walked it. */
+typedef struct {
+  double uv[2];          /* the loop's uv at index i (unit-plane coordinates)   */
+  double px[2];          /* world2cam(uv): level-0 pixel, before the scaling    */
+  int pxi[2];            /* the integer pixel on the search level               */
+  int dup;               /* equal to last_checked_pxi: skipped                  */
+  int in_frame;          /* isInFrame(pxi, patch_size, search_level)            */
+  int score;             /* ZMSSD, or -1 when the candidate was not evaluated   */
+} svo_orc_epi_step;
+
+/* The same function -- both entries run one body -- that also records its search loop: steps[i] for every loop index
+ * i < cap, *n_out = number of loop indices visited (0 on paths 0 and 2). */
+int svo_orc_find_epipolar_match_direct_trace(
+    const svo_orc_camera* cam, const uint8_t* const* ref_pyr, const uint8_t* const* cur_pyr,
+    const double T_cur_ref[7], const double px_ref[2], const double f_ref[3], int level_ref,
+    double d_estimate, double d_min, double d_max, int n_pyr_levels, int align_max_iter,
+    int max_epi_search_steps, svo_orc_epi_result* out, svo_orc_epi_step* steps, int cap, int* n_out);
+
 /* Matcher::findMatchDirect, matcher.cpp:156-202, for a reference feature already chosen by the caller
  * (Point::getCloseViewObs is host bookkeeping).  px_cur in/out in level-0 pixels. */
 int svo_orc_find_match_direct(const svo_orc_camera* cam, const uint8_t* const* ref_pyr, const uint8_t* const* cur_pyr,
