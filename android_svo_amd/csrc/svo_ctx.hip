@@ -181,6 +181,9 @@ int svo_hip_ctx_destroy(svo_hip_ctx* ctx) {
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->staging) (void)hipFree(ctx->staging);
   if (ctx->host_staging) (void)hipHostFree(ctx->host_staging);
+  if (ctx->df_jobs_dev) (void)hipFree(ctx->df_jobs_dev);
+  if (ctx->df_jobs_host) (void)hipHostFree(ctx->df_jobs_host);
+  if (ctx->df_jobs_ev) (void)hipEventDestroy(ctx->df_jobs_ev);
   for (svo_seed_block& blk : ctx->seed_pool) {         // (blocks still held by live seed batches go with those batches)
     if (blk.dev) (void)hipFree(blk.dev);
     if (blk.host) (void)hipHostFree(blk.host);

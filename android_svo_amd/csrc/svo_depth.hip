@@ -214,15 +214,22 @@ static void df_pixel_frame(const svo_hip_pyramid* ref, const svo_hip_pyramid* cu
   fr.keep_px_on_failure = keep_px_on_failure;
 }
 
-// frame-level constants of one updateSeeds / findEpipolarMatchDirect batch
-static void df_make_frame(const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, const svo_hip_camera* cam,
-                          const double T_ref_w[7], const double T_cur_w[7], const svo_hip_df_params* prm, DfFrame& fr) {
+// frame-level constants of an updateSeeds pass without the transforms (fr.T stays zero): what the batches of several cameras
+// share, whose jobs carry their own
+static void df_make_pass_frame(const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, const svo_hip_camera* cam, const svo_hip_df_params* prm,
+                               DfFrame& fr) {
   df_pixel_frame(ref, cur, cam, prm->n_pyr_levels, prm->align_max_iter, 0, fr);
-  fr.T = df_make_poses(T_ref_w, T_cur_w);
   const double focal_length = fabs(cam->fx);
   fr.px_error_angle = atan(1.0 / (2.0 * focal_length)) * 2.0;       // depth_filter.cpp:245-247
   fr.max_epi_search_steps = prm->max_epi_search_steps;
   fr.conv_thresh = prm->seed_convergence_sigma2_thresh;
+}
+
+// frame-level constants of one updateSeeds / findEpipolarMatchDirect batch
+static void df_make_frame(const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, const svo_hip_camera* cam,
+                          const double T_ref_w[7], const double T_cur_w[7], const svo_hip_df_params* prm, DfFrame& fr) {
+  df_make_pass_frame(ref, cur, cam, prm, fr);
+  fr.T = df_make_poses(T_ref_w, T_cur_w);
 }
 
 // what every pass refuses before it enqueues anything: the slots, the image sizes, the parameters.  (The grouped entry point
@@ -649,6 +656,7 @@ struct svo_hip_seed_batch {
   char* host_dev = nullptr;             // its device address
   bool pending = false;                 // a pass is enqueued and not collected yet
   int report_updated = 0;
+  unsigned long long call_serial = 0;   // the last svo_hip_seed_batch_update_cameras_async call that named the batch (a batch named twice)
   svo_seed_block blk;                   // the pool block behind dev / host (returned to the context on destroy)
 };
 
@@ -815,6 +823,17 @@ int svo_hip_seed_batch_size(const svo_hip_seed_batch* sb, int* n, int* n_alive) 
   return SVO_HIP_OK;
 }
 
+// the job of a batch in a pass: its arrays, its keyframe's transforms against the current frame, the first of its 256-record blocks
+static void sb_fill_job(DfJob& J, const svo_hip_seed_batch* sb, const double T_ref_w[7], const double T_cur_w[7], int first_block, int ref_slot) {
+  J.T = df_make_poses(T_ref_w, T_cur_w);
+  J.px = sb->px; J.f = sb->f; J.level = sb->level; J.a = sb->a; J.b = sb->b; J.mu = sb->mu; J.z_range = sb->z_range; J.sigma2 = sb->sigma2;
+  J.status = sb->status; J.xyz = sb->xyz; J.px_cur = sb->px_cur; J.alive = sb->alive; J.block_count = sb->block_count; J.hist = sb->hist;
+  J.header = reinterpret_cast<EvHeader*>(sb->host_dev);
+  J.events_host = reinterpret_cast<svo_hip_seed_event*>(sb->host_dev + kEvHeaderBytes);
+  J.events_dev = sb->events_dev;
+  J.n = sb->n; J.n_blocks = sb->n_blocks; J.first_block = first_block; J.ref_slot = ref_slot;
+}
+
 // one launch set over at most DF_GROUP_MAX batches (arguments checked by the callers)
 static int sb_enqueue_jobs(svo_hip_ctx* ctx, int n_jobs, svo_hip_seed_batch* const* batches, const svo_hip_pyramid* ref, const int* ref_slots,
                            const svo_hip_pyramid* cur, int cur_slot, const svo_hip_camera* cam, const double* T_ref_w,
@@ -830,14 +849,7 @@ static int sb_enqueue_jobs(svo_hip_ctx* ctx, int n_jobs, svo_hip_seed_batch* con
   int n_blocks = 0, n_cat = 0;
   for (int j = 0; j < n_jobs; ++j) {
     svo_hip_seed_batch* sb = batches[j];
-    DfJob& J = g.job[j];
-    J.T = df_make_poses(T_ref_w + 7 * (size_t)j, T_cur_w);
-    J.px = sb->px; J.f = sb->f; J.level = sb->level; J.a = sb->a; J.b = sb->b; J.mu = sb->mu; J.z_range = sb->z_range; J.sigma2 = sb->sigma2;
-    J.status = sb->status; J.xyz = sb->xyz; J.px_cur = sb->px_cur; J.alive = sb->alive; J.block_count = sb->block_count; J.hist = sb->hist;
-    J.header = reinterpret_cast<EvHeader*>(sb->host_dev);
-    J.events_host = reinterpret_cast<svo_hip_seed_event*>(sb->host_dev + kEvHeaderBytes);
-    J.events_dev = sb->events_dev;
-    J.n = sb->n; J.n_blocks = sb->n_blocks; J.first_block = n_blocks; J.ref_slot = ref_slots[j];
+    sb_fill_job(g.job[j], sb, T_ref_w + 7 * (size_t)j, T_cur_w, n_blocks, ref_slots[j]);
     n_cat = n_blocks * 256 + sb->n;
     n_blocks += sb->n_blocks;
   }
@@ -901,6 +913,134 @@ int svo_hip_seed_batch_update_async(svo_hip_seed_batch* sb, const svo_hip_pyrami
                                     int cur_slot, const svo_hip_camera* cam, const double T_ref_w[7], const double T_cur_w[7],
                                     const svo_hip_df_params* prm, int report_updated) {
   return svo_hip_seed_batch_update_group_async(1, &sb, ref, &ref_slot, cur, cur_slot, cam, T_ref_w, T_cur_w, prm, report_updated);
+}
+
+// The context's job table of a pass over several cameras: `need` bytes of device memory and of page-locked memory beside it,
+// grown together; the page-locked area is free to be rewritten when this returns.
+static int df_jobs_area(svo_hip_ctx* ctx, size_t need) {
+  if (ctx->df_jobs_in_flight) {                            // the previous call's transfer may still read the area
+    SVO_CHECK_HIP(ctx, hipEventSynchronize(ctx->df_jobs_ev));
+    ctx->df_jobs_in_flight = false;
+  }
+  if (!ctx->df_jobs_ev) SVO_CHECK_HIP(ctx, hipEventCreateWithFlags(&ctx->df_jobs_ev, hipEventDisableTiming));
+  if (ctx->df_jobs_bytes >= need) return SVO_HIP_OK;
+  if (ctx->df_jobs_dev || ctx->df_jobs_host) {
+    SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // kernels of an earlier pass read the table
+    if (ctx->df_jobs_dev) { (void)hipFree(ctx->df_jobs_dev); ++ctx->n_frees; }
+    if (ctx->df_jobs_host) { (void)hipHostFree(ctx->df_jobs_host); ++ctx->n_frees; }
+    ctx->df_jobs_dev = ctx->df_jobs_host = nullptr;
+    ctx->df_jobs_bytes = 0;
+  }
+  const size_t bytes = need + need / 4;
+  SVO_CHECK_HIP(ctx, hipMalloc(&ctx->df_jobs_dev, bytes));
+  ++ctx->n_allocs;
+  SVO_CHECK_HIP(ctx, hipHostMalloc(&ctx->df_jobs_host, bytes, hipHostMallocDefault));
+  ++ctx->n_allocs;
+  ctx->df_jobs_bytes = bytes;
+  return SVO_HIP_OK;
+}
+
+int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, const svo_hip_seed_camera_pass* passes, const svo_hip_pyramid* ref,
+                                            const svo_hip_pyramid* cur, const svo_hip_camera* cam, const svo_hip_df_params* prm) {
+  if (!ctx) return SVO_HIP_ERR_INVALID;
+  const char* who = "svo_hip_seed_batch_update_cameras_async";
+  if (!passes || !ref || !cur || !cam || !prm) return svo_fail(ctx, SVO_HIP_ERR_INVALID, who, "null argument");
+  SVO_REQUIRE(ctx, n_cameras >= 0);
+  // ---- every camera's and every batch's arguments are checked before anything is enqueued
+  // (the call's serial, stamped on the batches the walk has passed, is how a batch named twice is found; it is the one thing a
+  // refused call leaves behind, and it means nothing to the next call, which has a serial of its own)
+  const unsigned long long serial = ++ctx->df_jobs_serial;
+  long long n_jobs_ll = 0, n_blocks_ll = 0;
+  for (int c = 0; c < n_cameras; ++c) {
+    const svo_hip_seed_camera_pass& P = passes[c];
+    SVO_REQUIRE(ctx, P.n_batches >= 0);
+    if (P.n_batches == 0) continue;                        // the camera sits this pass out
+    SVO_REQUIRE(ctx, P.batches && P.ref_slots && P.T_ref_w);
+    SVO_REQUIRE(ctx, P.cur_slot >= 0 && P.cur_slot < cur->batch);
+    for (int k = 0; k < P.n_batches; ++k) {
+      svo_hip_seed_batch* sb = P.batches[k];
+      SVO_REQUIRE(ctx, sb && sb->ctx == ctx);
+      if (sb->pending) return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "the previous pass has not been collected");
+      if (sb->call_serial == serial) return svo_fail(ctx, SVO_HIP_ERR_INVALID, who, "a batch is named twice");
+      sb->call_serial = serial;
+      SVO_REQUIRE(ctx, P.ref_slots[k] >= 0 && P.ref_slots[k] < ref->batch);
+      n_blocks_ll += sb->n_blocks;
+    }
+    n_jobs_ll += P.n_batches;
+  }
+  if (const int rc = df_check_pass_args(ctx, ref, 0, nullptr, cur, 0, cam, prm); rc != SVO_HIP_OK) return rc;
+  SVO_REQUIRE(ctx, n_jobs_ll <= SVO_HIP_DF_CAMERAS_MAX_JOBS && n_blocks_ll * 256 <= SVO_HIP_DF_CAMERAS_MAX_RECORDS);
+  if (n_jobs_ll == 0) return SVO_HIP_OK;
+  const int n_jobs = (int)n_jobs_ll, n_blocks = (int)n_blocks_ll, n_rec = n_blocks * 256;
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  // ---- memory: the pass's scratch (records, transposed patches, levels) and the job table; nothing is enqueued yet
+  const size_t rec_bytes = (size_t)n_rec * sizeof(SeedRec), pwb_bytes = (size_t)25 * n_rec * sizeof(uint32_t);
+  void* ws = nullptr;
+  if (const int rc = svo_ctx_scratch(ctx, rec_bytes + pwb_bytes + (size_t)n_rec * sizeof(int32_t), &ws); rc != SVO_HIP_OK) return rc;
+  const DfScratch s = {(SeedRec*)ws, reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + rec_bytes), n_rec};
+  int32_t* level_cat = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + rec_bytes + pwb_bytes);
+  const size_t jobs_bytes = (size_t)n_jobs * sizeof(DfCamJob), table_bytes = jobs_bytes + (size_t)n_blocks * sizeof(int);
+  if (const int rc = df_jobs_area(ctx, table_bytes); rc != SVO_HIP_OK) return rc;
+  // ---- the table, packed: [jobs][block -> job]
+  DfCamJob* jobs_host = static_cast<DfCamJob*>(ctx->df_jobs_host);
+  int* block_job_host = reinterpret_cast<int*>(static_cast<char*>(ctx->df_jobs_host) + jobs_bytes);
+  memset(jobs_host, 0, jobs_bytes);
+  int j = 0, first_block = 0;
+  for (int c = 0; c < n_cameras; ++c) {
+    const svo_hip_seed_camera_pass& P = passes[c];
+    for (int k = 0; k < P.n_batches; ++k, ++j) {
+      const svo_hip_seed_batch* sb = P.batches[k];
+      sb_fill_job(jobs_host[j].job, sb, P.T_ref_w + 7 * (size_t)k, P.T_cur_w, first_block, P.ref_slots[k]);
+      jobs_host[j].cur_slot = P.cur_slot;
+      jobs_host[j].report_updated = P.report_updated ? 1 : 0;
+      for (int b = 0; b < sb->n_blocks; ++b) block_job_host[first_block + b] = j;
+      first_block += sb->n_blocks;
+    }
+  }
+  const DfCamJob* jobs = static_cast<const DfCamJob*>(ctx->df_jobs_dev);
+  const int* block_job = reinterpret_cast<const int*>(static_cast<const char*>(ctx->df_jobs_dev) + jobs_bytes);
+  DfFrame fr;
+  df_make_pass_frame(ref, cur, cam, prm, fr);
+  const bool prof = ctx->df_profile;
+  // ---- the transfer and the launches; from here on an error path waits for the stream before it returns
+  hipError_t e = hipMemcpyAsync(ctx->df_jobs_dev, ctx->df_jobs_host, table_bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, hipGetErrorString(e));
+  e = hipEventRecord(ctx->df_jobs_ev, ctx->stream);
+  if (e == hipSuccess) {
+    ctx->df_jobs_in_flight = true;
+    df_stamp(ctx, 0);
+    const dim3 fine(n_blocks * (256 / SEEDS_PER_BLOCK));   // 16 records (search) or 16 patches (align) a workgroup
+    static_assert(SEEDS_PER_BLOCK == ALIGN_PATCHES && 256 % SEEDS_PER_BLOCK == 0, "one fine grid for both pixel stages");
+    if (n_rec <= ctx->df_small_max) {
+      hipLaunchKernelGGL(df_small_pass_jobs_kernel, fine, dim3(256), 0, ctx->stream, fr, jobs, block_job, ref->base, ref->pyr_bytes, cur->base,
+                         cur->pyr_bytes, s.recs, s.pwb_t, level_cat, s.n_pad);
+      df_stamp(ctx, 1); df_stamp(ctx, 2); df_stamp(ctx, 3);
+      if (prof) { (void)hipEventRecord(ctx->df_ev[4], ctx->stream); ctx->df_ev_recorded = true; }
+      hipLaunchKernelGGL(ev_small_jobs_kernel, dim3(n_jobs), dim3(1024), 0, ctx->stream, jobs);
+    } else {
+      hipLaunchKernelGGL(df_geometry_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, block_job, s.recs, level_cat);
+      df_stamp(ctx, 1);
+      hipLaunchKernelGGL(df_search_jobs_kernel, fine, dim3(256), 0, ctx->stream, fr, jobs, block_job, ref->base, ref->pyr_bytes, cur->base,
+                         cur->pyr_bytes, (const int32_t*)level_cat, s.recs, s.pwb_t, s.n_pad);
+      df_stamp(ctx, 2);
+      hipLaunchKernelGGL(df_align_jobs_kernel, fine, dim3(ALIGN_BLOCK), 0, ctx->stream, fr, jobs, block_job, cur->base, cur->pyr_bytes, s.n_pad,
+                         (const uint32_t*)s.pwb_t, s.recs);
+      df_stamp(ctx, 3);
+      hipLaunchKernelGGL(df_finalize_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, block_job, (const SeedRec*)s.recs);
+      if (prof) { (void)hipEventRecord(ctx->df_ev[4], ctx->stream); ctx->df_ev_recorded = true; }
+      hipLaunchKernelGGL(ev_scan_jobs_kernel, dim3(n_jobs), dim3(1024), 0, ctx->stream, jobs);
+      hipLaunchKernelGGL(ev_scatter_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, jobs, block_job);
+    }
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->stream);               // nothing of the call is in flight when the caller unwinds
+    ctx->df_jobs_in_flight = false;
+    return svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, hipGetErrorString(e));
+  }
+  for (int c = 0; c < n_cameras; ++c)
+    for (int k = 0; k < passes[c].n_batches; ++k) { passes[c].batches[k]->pending = true; passes[c].batches[k]->report_updated = passes[c].report_updated ? 1 : 0; }
+  return SVO_HIP_OK;
 }
 
 int svo_hip_df_set_small_pass_limit(svo_hip_ctx* ctx, int max_seeds) {

@@ -175,4 +175,13 @@ __global__ __launch_bounds__(ALIGN_BLOCK) void df_align_cams_kernel(DfFrame fr, 
   n_c = n_c < cap ? n_c : cap;
   df_align_quad<ONE_D>(fr, cur_base + (size_t)c * cur_pyr_bytes, n_pad, pwb_t, recs, i, i < c * cap + n_c);
 }
+
+// (the alignment stage over the batches of several cameras: the layout of df_search_jobs_kernel, svo_depth_search.h)
+__global__ __launch_bounds__(ALIGN_BLOCK) void df_align_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
+                                                                    const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes, int n_pad,
+                                                                    const uint32_t* __restrict__ pwb_t, SeedRec* __restrict__ recs) {
+  const int i = blockIdx.x * ALIGN_PATCHES + (threadIdx.x >> 2);
+  const DfCamJob& C = jobs[block_job[blockIdx.x / (256 / ALIGN_PATCHES)]];
+  df_align_quad<false>(fr, cur_base + (size_t)C.cur_slot * cur_pyr_bytes, n_pad, pwb_t, recs, i, i < C.job.first_block * 256 + C.job.n);
+}
 }  // namespace

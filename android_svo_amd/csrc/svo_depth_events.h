@@ -276,6 +276,132 @@ __global__ __launch_bounds__(1024) void ev_small_kernel(DfGroup g) {
   }
 }
 
+// ---- the batches of several cameras in one launch set (svo_hip_seed_batch_update_cameras_async) ----------------------------
+// The kernels of the grouped pass over a job table in device memory (DfCamJob, svo_depth_types.h) instead of a DfGroup in the
+// kernel arguments: a block finds its job with one load from the block -> job map, the job's fields are block-uniform, its
+// report_updated stands where the group's stood, its cur_slot picks the current image in the pixel stages.  The same device
+// functions as above, so every per-seed result and every event is bit-identical to a grouped pass per camera
+// (tests/test_gpu_seed_cameras.py).  DfFrame::T is not read: the transforms are the job's.
+__global__ __launch_bounds__(256) void df_geometry_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
+                                                               SeedRec* __restrict__ recs, int32_t* __restrict__ level_cat) {
+  const DfJob& J = jobs[block_job[blockIdx.x]].job;
+  const int i = (blockIdx.x - J.first_block) * 256 + threadIdx.x;       // seed of its batch
+  if (i < 8) J.hist[i] = 0;
+  df_geometry_job_seed(fr, J, i, (size_t)blockIdx.x * 256 + threadIdx.x, recs, level_cat);
+}
+
+__global__ __launch_bounds__(256) void df_finalize_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
+                                                               const SeedRec* __restrict__ recs) {
+  const DfCamJob& C = jobs[block_job[blockIdx.x]];
+  const DfJob& J = C.job;
+  const int block = blockIdx.x - J.first_block;
+  const int i = block * 256 + threadIdx.x;
+  int st = SVO_HIP_SEED_ERASED;
+  if (i < J.n) {
+    const SeedRec rc = recs[(size_t)blockIdx.x * 256 + threadIdx.x];
+    st = df_finalize_seed(fr.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, fr.px_error_angle, fr.conv_thresh, i, rc, J.f, J.a, J.b, J.mu,
+                          J.z_range, J.sigma2, J.status, nullptr, J.xyz, nullptr, nullptr, J.px_cur, nullptr);
+  }
+  df_finalize_events(st, i, J.n, block, J.alive, C.report_updated, J.block_count, J.hist);
+}
+
+// (one workgroup of 1024 per job)
+__global__ __launch_bounds__(1024) void ev_scan_jobs_kernel(const DfCamJob* __restrict__ jobs) {
+  const DfJob& J = jobs[blockIdx.x].job;
+  int total;
+  block_scan_counts(J.n_blocks, J.block_count, &total);
+  if (threadIdx.x == 0) { J.header->n_events = total; J.hist[8] = total; }
+  if (threadIdx.x < 7) J.header->counts[threadIdx.x] = J.hist[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void ev_scatter_jobs_kernel(const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job) {
+  const DfCamJob& C = jobs[block_job[blockIdx.x]];
+  const DfJob& J = C.job;
+  svo_hip_seed_event* events = J.hist[8] <= EV_DIRECT_MAX ? J.events_host : J.events_dev;
+  const int block = blockIdx.x - J.first_block, i = block * 256 + threadIdx.x;
+  const int st = i < J.n ? J.status[i] : SVO_HIP_SEED_ERASED;
+  const bool ev = seed_event_wanted(st, C.report_updated);
+  __shared__ int s_w[4];
+  const int rank = ordered_rank_in_block(ev, s_w);
+  if (ev) events[J.block_count[block] + rank] = make_seed_event(i, st, J.mu, J.sigma2, J.xyz, J.px_cur);
+}
+
+// the small pass (df_small_pass_kernel): 16 of these workgroups per 256-record block, a wave takes its four seeds through all
+// four stages; a workgroup wholly behind its job's last seed has nothing to do
+__global__ __launch_bounds__(256) void df_small_pass_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
+                                                                 const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes,
+                                                                 const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes,
+                                                                 SeedRec* __restrict__ recs, uint32_t* __restrict__ pwb_t,
+                                                                 int32_t* __restrict__ level_cat, int n_pad) {
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int r0 = (blockIdx.x * 4 + wib) * SEEDS_PER_WAVE;   // the wave's first record
+  const DfCamJob& C = jobs[block_job[blockIdx.x >> 4]];
+  const DfJob& J = C.job;
+  const int n_end = J.first_block * 256 + J.n;             // the end of the job's records
+  if (r0 >= n_end) return;                                 // wave-uniform; no block-level barrier below
+  const uint8_t* cur_pyr = cur_base + (size_t)C.cur_slot * cur_pyr_bytes;
+  const int i0 = r0 - J.first_block * 256;                 // the wave's first seed within its batch
+  // ---- geometry
+  if (lane < SEEDS_PER_WAVE) df_geometry_job_seed(fr, J, i0 + lane, (size_t)r0 + lane, recs, level_cat);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  // ---- warp + epipolar search
+  df_search_block(fr, ref_base, ref_pyr_bytes, cur_pyr, n_end, level_cat, recs, pwb_t, n_pad, blockIdx.x);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  // ---- align2D
+  {
+    const int r = r0 + (lane >> 2);
+    df_align_quad<false>(fr, cur_pyr, n_pad, pwb_t, recs, r, lane < 4 * SEEDS_PER_WAVE && r < n_end);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  // ---- triangulation, computeTau, updateSeed
+  if (lane < SEEDS_PER_WAVE && i0 + lane < J.n) {
+    const SeedRec rc = recs[(size_t)r0 + lane];
+    (void)df_finalize_seed(fr.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, fr.px_error_angle, fr.conv_thresh, i0 + lane, rc, J.f, J.a, J.b,
+                           J.mu, J.z_range, J.sigma2, J.status, nullptr, J.xyz, nullptr, nullptr, J.px_cur, nullptr);
+  }
+}
+
+// (ev_small_kernel over the table: one workgroup of 1024 per job of at most DF_SMALL_MAX seeds)
+__global__ __launch_bounds__(1024) void ev_small_jobs_kernel(const DfCamJob* __restrict__ jobs) {
+  const DfCamJob& C = jobs[blockIdx.x];
+  const DfJob& J = C.job;
+  const int n = J.n, report_updated = C.report_updated;
+  __shared__ int s_cnt[DF_SMALL_MAX / 256], s_off[DF_SMALL_MAX / 256], s_hist[8], s_w[16], s_total;
+  if (threadIdx.x < DF_SMALL_MAX / 256) s_cnt[threadIdx.x] = 0;
+  if (threadIdx.x < 8) s_hist[threadIdx.x] = 0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += 1024) {
+    const int st = J.status[i];
+    if (seed_gone(st)) J.alive[i] = 0;
+    atomicAdd(&s_hist[st + 1], 1);
+    if (seed_event_wanted(st, report_updated)) atomicAdd(&s_cnt[i >> 8], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {                                  // exclusive scan of the (at most 64) block counts
+    const int v = threadIdx.x < J.n_blocks ? s_cnt[threadIdx.x] : 0;
+    const int incl = wave_scan_inclusive(v);
+    s_off[threadIdx.x] = incl - v;
+    if (threadIdx.x == 63) s_total = incl;
+  }
+  __syncthreads();
+  const int total = s_total;
+  if (threadIdx.x == 0) { J.header->n_events = total; J.hist[8] = total; }
+  if (threadIdx.x < 7) J.header->counts[threadIdx.x] = s_hist[threadIdx.x];
+  svo_hip_seed_event* events = total <= EV_DIRECT_MAX ? J.events_host : J.events_dev;
+  for (int base = 0; base < n; base += 1024) {
+    const int i = base + threadIdx.x;
+    const int st = i < n ? J.status[i] : SVO_HIP_SEED_ERASED;
+    const bool ev = seed_event_wanted(st, report_updated);
+    const int rank = ordered_rank_in_block(ev, s_w, (threadIdx.x >> 6) & ~3);   // four waves per 256-seed block
+    if (ev) events[s_off[i >> 8] + rank] = make_seed_event(i, st, J.mu, J.sigma2, J.xyz, J.px_cur);
+    __syncthreads();
+  }
+}
+
 // DepthFilter::updateSeeds on a keyframe (S/depth_filter.cpp:302-306): feature_detector_->setGridOccpuancy(matcher_.px_cur_)
 // for every seed the pass updated -- status UPDATED, CONVERGED or NaN, the seeds a report_updated pass reports.  The status
 // is the gate: px_cur of a seed without a match is not finite, that of an erased seed is stale.  Batch j owns the blocks

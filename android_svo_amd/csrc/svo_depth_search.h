@@ -409,4 +409,16 @@ __global__ __launch_bounds__(256, 7) void df_search_cams_kernel(
   n_c = n_c < cap ? n_c : cap;
   df_search_block(fr, ref_base, ref_pyr_bytes, cur_base + (size_t)c * cur_pyr_bytes, c * cap + n_c, level, recs, pwb_t, n_pad, blockIdx.x);
 }
+
+// ---- the warp / search stage over the batches of several cameras (svo_hip_seed_batch_update_cameras_async): the 16 records of a
+// block lie inside ONE job of the device-resident table (job boundaries are multiples of 256 records); the job names the slot
+// of its camera's current image and the end of its records.
+__global__ __launch_bounds__(256, 7) void df_search_jobs_kernel(
+    DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job, const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes,
+    const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes, const int32_t* __restrict__ level, SeedRec* __restrict__ recs,
+    uint32_t* __restrict__ pwb_t, int n_pad) {
+  const DfCamJob& C = jobs[block_job[blockIdx.x / (256 / SEEDS_PER_BLOCK)]];
+  df_search_block(fr, ref_base, ref_pyr_bytes, cur_base + (size_t)C.cur_slot * cur_pyr_bytes, C.job.first_block * 256 + C.job.n, level, recs, pwb_t,
+                  n_pad, blockIdx.x);
+}
 }  // namespace

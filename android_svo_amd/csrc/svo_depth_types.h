@@ -89,7 +89,18 @@ static_assert(offsetof(DfFrame, T) == sizeof(Cam) && offsetof(DfFrame, px_error_
 static_assert(offsetof(DfJob, T) == 0 && offsetof(DfJob, px) == sizeof(DfPoses) && sizeof(DfJob) == sizeof(DfPoses) + 17 * 8 + 4 * 4,
               "DfJob layout");
 
-constexpr int DF_SMALL_MAX = 16384;                       // upper limit of svo_hip_df_set_small_pass_limit
+// ---- one launch set for the batches of SEVERAL cameras (svo_hip_seed_batch_update_cameras_async) ---------------------------
+// The jobs do not travel as kernel arguments: a table of them lies in device memory, and beside it a map from every 256-record
+// block of the pass to its job.  A job is a DfJob plus what a DfGroup holds once for all its jobs and a pass holds once for all
+// its batches: whether the job's camera reports its updated seeds, and the slot of its camera's current image.  Job
+// boundaries are multiples of 256 records, so a 16-record search block or a 16-patch align block lies inside one job too.
+struct DfCamJob {
+  DfJob job;
+  int cur_slot, report_updated;
+};
+static_assert(sizeof(DfCamJob) == sizeof(DfJob) + 8 && sizeof(DfCamJob) % 8 == 0, "DfCamJob layout");
+
+constexpr int DF_SMALL_MAX = 16384;                      // upper limit of svo_hip_df_set_small_pass_limit
 
 // the batches of one svo_hip_seed_batch_mark_updated launch: batch j owns the blocks [first_block, first_block + ceil(n / 256))
 struct MarkJob { const int32_t* status; const double* px_cur; int n, first_block; };

@@ -40,6 +40,15 @@ struct svo_hip_ctx {
   int df_small_max = 8192;             // passes of at most this many seed records take the two-launch form (svo_depth.hip)
   bool df_ev_recorded = false;
   hipEvent_t df_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // The job table and block -> job map of a pass over several cameras (svo_hip_seed_batch_update_cameras_async, svo_depth.hip):
+  // device memory and the page-locked area they are packed in, both grow-only.  The call returns with its transfer in flight,
+  // so the next call waits for this event before it rewrites the area.
+  void* df_jobs_dev = nullptr;
+  void* df_jobs_host = nullptr;
+  size_t df_jobs_bytes = 0;            // of each of the two
+  hipEvent_t df_jobs_ev = nullptr;
+  bool df_jobs_in_flight = false;
+  unsigned long long df_jobs_serial = 0;      // calls so far
   // Seed batches are created and destroyed at keyframe rate on the depth-filter thread (S/depth_filter.cpp:129-151,256-261);
   // hipFree synchronises the whole DEVICE, i.e. it would stall the tracking thread's stream too (SURVEY 8(b) "Threading": no
   // implicit device synchronisation).  So a destroyed batch returns its block here and a new one takes a free block of its

@@ -1345,4 +1345,13 @@ int svo_hip_tracker_info(const svo_hip_tracker* t, int* n_cells, int* grid_cols,
   return SVO_HIP_OK;
 }
 
+int svo_hip_tracker_last_frame_pyramid(svo_hip_tracker* t, const svo_hip_pyramid** pyr, int* slot) {
+  if (!t) return SVO_HIP_ERR_INVALID;
+  SVO_REQUIRE(t->ctx, pyr && slot);
+  if (!t->have_last) return svo_fail(t->ctx, SVO_HIP_ERR_STATE, "svo_hip_tracker_last_frame_pyramid", "the tracker has no last frame");
+  *pyr = t->sh->frame_pyr[t->sh->last_idx];
+  *slot = t->cam_index;
+  return SVO_HIP_OK;
+}
+
 }  // extern "C"

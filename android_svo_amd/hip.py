@@ -241,10 +241,20 @@ class Pyramid:
         self.ctx.check(self.ctx.lib.svo_hip_pyramid_download_level(self.h, slot, level, _ptr(out, C.c_uint8)), "pyramid_download")
         return out
 
+    @classmethod
+    def borrowed(cls, ctx: Context, handle) -> "Pyramid":
+        """A view of a pyramid batch somebody else owns (a tracker's keyframe or frame batch): destroy() leaves it alone."""
+        self = cls.__new__(cls)
+        w, h, nl, nb = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        ctx.check(ctx.lib.svo_hip_pyramid_info(handle, C.byref(w), C.byref(h), C.byref(nl), C.byref(nb), None, None), "pyramid_info")
+        self.ctx, self.width, self.height, self.n_levels, self.batch = ctx, w.value, h.value, nl.value, nb.value
+        self.h, self._borrowed = C.c_void_p(handle.value if hasattr(handle, "value") else handle), True
+        return self
+
     def destroy(self):
-        if self.h:
+        if self.h and not getattr(self, "_borrowed", False):
             self.ctx.lib.svo_hip_pyramid_destroy(self.h)
-            self.h = C.c_void_p()
+        self.h = C.c_void_p()
 
 
 class SparseImgAlign:
@@ -587,6 +597,11 @@ SEED_EVENT_DTYPE = np.dtype([("index", np.int32), ("status", np.int32), ("mu", n
 SEED_ERASED = -1
 
 
+class CSeedCameraPass(C.Structure):           # svo_hip_seed_camera_pass
+    _fields_ = [("n_batches", C.c_int), ("batches", C.POINTER(C.c_void_p)), ("ref_slots", C.POINTER(C.c_int)),
+                ("T_ref_w", C.POINTER(C.c_double)), ("cur_slot", C.c_int), ("T_cur_w", C.c_double * 7), ("report_updated", C.c_int)]
+
+
 class ResidentSeeds:
     """svo_hip_seed_batch: the seeds of one keyframe resident on the device from creation to their end (uploaded once;
     per frame two poses go down and only the converged / NaN seeds -- on keyframes also the updated ones -- come back)."""
@@ -649,6 +664,36 @@ class ResidentSeeds:
         ctx.check(ctx.lib.svo_hip_seed_batch_update_group_async(len(batches), hs, ref.h, _ptr(slots, C.c_int), cur.h, cur_slot, C.byref(c),
                                                                 _ptr(Tr, C.c_double), _ptr(Tc, C.c_double), C.byref(prm),
                                                                 1 if report_updated else 0), "seed_batch_update_group_async")
+
+    @staticmethod
+    def update_cameras_async(passes, ref: Pyramid, cur: Pyramid, cam, prm=None, ctx: Optional[Context] = None):
+        """svo_hip_seed_batch_update_cameras_async: the batches of SEVERAL cameras as ONE set of launches.  `passes`: per camera
+        (batches, ref_slots, T_ref_w [n][7], cur_slot, T_cur_w, report_updated); a camera without batches sits the pass out.
+        Collect every batch afterwards.  `ctx` is only needed when no camera has a batch."""
+        if ctx is None:
+            ctx = next(b.ctx for p in passes for b in p[0])
+        prm = prm or depth_filter_params()
+        c = make_camera(cam)
+        arr = (CSeedCameraPass * max(len(passes), 1))()
+        keep = []
+        for i, (batches, ref_slots, T_ref_w, cur_slot, T_cur_w, report_updated) in enumerate(passes):
+            n = len(batches)
+            hs = (C.c_void_p * max(n, 1))(*[b.h for b in batches])
+            slots = np.ascontiguousarray(ref_slots, dtype=np.int32).reshape(n)
+            Tr = _f64(np.asarray(T_ref_w, dtype=np.float64).reshape(n, 7))
+            keep += [hs, slots, Tr]
+            arr[i].n_batches = n
+            arr[i].batches = C.cast(hs, C.POINTER(C.c_void_p))
+            arr[i].ref_slots = _ptr(slots, C.c_int)
+            arr[i].T_ref_w = _ptr(Tr, C.c_double)
+            arr[i].cur_slot = int(cur_slot)
+            arr[i].T_cur_w[:] = [float(v) for v in np.asarray(T_cur_w, dtype=np.float64).reshape(7)]
+            arr[i].report_updated = 1 if report_updated else 0
+        ctx.check(ctx.lib.svo_hip_seed_batch_update_cameras_async(ctx.h, len(passes), arr, ref.h, cur.h, C.byref(c), C.byref(prm)),
+                  "seed_batch_update_cameras_async")
+
+    def pending(self) -> bool:
+        return bool(self.ctx.lib.svo_hip_seed_batch_pending(self.h))
 
     def collect_raw(self):
         """(address of the batch's page-locked event block, number of events, status counts [7]) -- no copy"""
@@ -1062,6 +1107,20 @@ class Tracker:
 
     def keyframe_from_last_frame(self, slot: int):
         self.ctx.check(self.ctx.lib.svo_hip_tracker_keyframe_from_last_frame(self.h, slot), "tracker_keyframe_from_last_frame")
+
+    def keyframe_pyramids(self) -> "Pyramid":
+        """the keyframe pyramid batch (svo_hip_tracker_info), borrowed: a group camera c's keyframe slot s is slot
+        c * max_keyframes + s of it"""
+        p = C.c_void_p()
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_info(self.h, None, None, None, C.byref(p)), "tracker_info")
+        return Pyramid.borrowed(self.ctx, p)
+
+    def last_frame_pyramid(self):
+        """svo_hip_tracker_last_frame_pyramid: (the pyramid batch holding the last frames of the tracker's group -- a borrowed
+        view, valid until the next call that tracks, relocalises or sets a last frame --, this camera's slot in it)"""
+        p, slot = C.c_void_p(), C.c_int(-1)
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_last_frame_pyramid(self.h, C.byref(p), C.byref(slot)), "tracker_last_frame_pyramid")
+        return Pyramid.borrowed(self.ctx, p), slot.value
 
     def optimize_structure(self, point, n_iter: int = 5):
         """FrameHandlerBase::optimizeStructure on the given points over the observations the map tables hold.

@@ -9,6 +9,8 @@
 //                                                   world w under <out_dir>/g<w>/, each equal to the lone tracker's
 //        svo_host_demo <case_dir> <out_dir> keyframes [device_seeds] [threaded]   keyframes whose seeds the filter detects and creates
 //                                                   on the device, or (without device_seeds) are detected by the caller and handed in
+//        svo_host_demo <case_dir> <out_dir> filtergroup   svo::DepthFilterGroup: the depth filters of n cameras as one device pass per
+//                                                   step, and a lone DepthFilter per camera over the same frames (filter_group_demo)
 //        svo_host_demo <case_dir> <out_dir> churn   SURVEY 8(b) "Threading": latency of SparseImgAlign::run on the tracking
 //                                                   thread while a second thread (own context) creates seed batches, runs a
 //                                                   pass and drops them at keyframe rate -- and with that thread idle
@@ -648,7 +650,123 @@ static int keyframes_demo(const std::string& dir, const std::string& out, bool d
   return 0;
 }
 
+// ---- svo::DepthFilterGroup: n cameras, each with its own frames (<case_dir>/cam<c>/frame_*), keyframes (cam<c>/keyframes.bin: the
+// frame numbers, the first is 0) and seeds per keyframe (cam<c>/kf<j>_{px,f,level}.bin); options.bin: max_n_kfs and the convergence threshold.  Step k: a camera whose frame k is a
+// keyframe updates its seeds with it (the pass reports the updated seeds, the grid is marked) and then gets the keyframe's new
+// seeds, as DepthFilter's thread does (depth_filter.cpp:191-229); the other cameras update with frame k.  Run twice: through the
+// group (one device pass per step for all cameras) and through one lone unthreaded DepthFilter per camera.  Per camera the
+// sequence of convergence callbacks, the final seeds and the detector grid go to <out_dir>/{group,lone}_cam<c>_*.bin.
+static int filter_group_demo(const std::string& dir, const std::string& out) {
+  const std::vector<double> m = read_bin<double>(dir + "/manifest.bin");      // w h fx fy cx cy n_levels n_frames n_cameras
+  PinholeCamera pc{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
+  const int n_levels = (int)m[6], n_frames = (int)m[7], n_cams = (int)m[8];
+  const auto dm = read_bin<double>(dir + "/depth_mean_min.bin");
+  const auto opt = read_bin<double>(dir + "/options.bin");                    // Options: max_n_kfs, seed_convergence_sigma2_thresh
+  struct SeedSet { std::vector<double> px, f; std::vector<int32_t> level; };
+  struct Cam {
+    std::vector<FramePtr> frames;
+    std::vector<int> keyframes;
+    std::vector<SeedSet> sets;
+  };
+  std::vector<Cam> cams((size_t)n_cams);
+  for (int c = 0; c < n_cams; ++c) {
+    const std::string cd = dir + "/cam" + std::to_string(c);
+    for (int k = 0; k < n_frames; ++k) cams[(size_t)c].frames.push_back(load_frame(cd, &pc, k, n_levels));
+    for (double k : read_bin<double>(cd + "/keyframes.bin")) {
+      const std::string kd = cd + "/kf" + std::to_string(cams[(size_t)c].keyframes.size());
+      cams[(size_t)c].keyframes.push_back((int)k);
+      cams[(size_t)c].frames[(size_t)k]->setKeyframe();
+      cams[(size_t)c].sets.push_back(SeedSet{read_bin<double>(kd + "_px.bin"), read_bin<double>(kd + "_f.bin"), read_bin<int32_t>(kd + "_level.bin")});
+    }
+  }
+  // per run and camera: the features of its keyframes (feature -> running number), the callbacks, the grid
+  struct Side {
+    std::map<Feature*, int> index;
+    std::vector<std::vector<Feature*>> fts;     // per keyframe
+    std::vector<double> conv;                    // per callback: feature number, x, y, z, sigma2
+    std::unique_ptr<DetectorGrid> grid;
+  };
+  auto make_side = [&](const Cam& cam, Side& s) {
+    int id = 0;
+    for (size_t j = 0; j < cam.sets.size(); ++j) {
+      const SeedSet& ss = cam.sets[j];
+      Frame* kf = cam.frames[(size_t)cam.keyframes[j]].get();
+      s.fts.emplace_back();
+      for (size_t i = 0; i < ss.level.size(); ++i) {
+        s.fts.back().push_back(new Feature(kf, Vector2d{{ss.px[2 * i], ss.px[2 * i + 1]}}, Vector3d{{ss.f[3 * i], ss.f[3 * i + 1], ss.f[3 * i + 2]}}, ss.level[i]));
+        s.index[s.fts.back().back()] = id++;
+      }
+    }
+    s.grid.reset(new DetectorGrid(pc.width, pc.height, 30));
+  };
+  auto keyframe_no = [&](const Cam& cam, int k) {
+    for (size_t j = 0; j < cam.keyframes.size(); ++j) if (cam.keyframes[j] == k) return (int)j;
+    return -1;
+  };
+  auto dump = [&](Side& s, std::list<Seed>& seeds, const std::string& tag) {
+    std::vector<double> rows;
+    for (const Seed& sd : seeds) { rows.push_back((double)s.index.at(sd.ftr)); rows.push_back(sd.a); rows.push_back(sd.b); rows.push_back(sd.mu); rows.push_back(sd.sigma2); }
+    write_bin(out + "/" + tag + "_seeds.bin", rows);
+    write_bin(out + "/" + tag + "_conv.bin", s.conv);
+    write_bin(out + "/" + tag + "_grid.bin", std::vector<uint8_t>(s.grid->grid_occupancy_.begin(), s.grid->grid_occupancy_.end()));
+    for (auto& v : s.fts) for (Feature* f : v) delete f;
+  };
+  auto callback = [](Side* s) {
+    return [s](Point* p, double s2) {
+      s->conv.insert(s->conv.end(), {(double)s->index.at(p->obs_.front()), p->pos_[0], p->pos_[1], p->pos_[2], s2});
+      delete p;
+    };
+  };
+  // ---- the group
+  {
+    std::vector<Side> sides((size_t)n_cams);
+    std::vector<DepthFilterGroup::callback_t> cbs;
+    std::vector<DetectorGrid*> grids;
+    for (int c = 0; c < n_cams; ++c) { make_side(cams[(size_t)c], sides[(size_t)c]); cbs.push_back(callback(&sides[(size_t)c])); grids.push_back(sides[(size_t)c].grid.get()); }
+    DepthFilterGroup group(cbs, grids);
+    group.options_.max_n_kfs = (int)opt[0]; group.options_.seed_convergence_sigma2_thresh = opt[1];
+    int n_passes = 0, n_batches = 0;
+    for (int k = 0; k < n_frames; ++k) {
+      std::vector<FramePtr> frames;
+      for (int c = 0; c < n_cams; ++c) frames.push_back(cams[(size_t)c].frames[(size_t)k]);
+      group.addFrames(frames);
+      for (int c = 0; c < n_cams; ++c) { n_batches += group.last_stats_[(size_t)c].n_device_calls; }
+      ++n_passes;
+      for (int c = 0; c < n_cams; ++c) {
+        const int j = keyframe_no(cams[(size_t)c], k);
+        if (j >= 0) group.addKeyframe((size_t)c, cams[(size_t)c].frames[(size_t)k], dm[0], dm[1], sides[(size_t)c].fts[(size_t)j]);
+      }
+    }
+    for (int c = 0; c < n_cams; ++c) dump(sides[(size_t)c], group.getSeeds((size_t)c), "group_cam" + std::to_string(c));
+    write_bin(out + "/group_summary.bin", std::vector<double>{(double)n_passes, (double)n_batches, (double)group.keyframeUploads()});
+  }
+  // ---- a lone filter per camera
+  for (int c = 0; c < n_cams; ++c) {
+    Side side;
+    make_side(cams[(size_t)c], side);
+    Seed::batch_counter = 0;
+    DepthFilter df(callback(&side), side.grid.get());
+    df.options_.max_n_kfs = (int)opt[0]; df.options_.seed_convergence_sigma2_thresh = opt[1];
+    for (int k = 0; k < n_frames; ++k) {
+      df.addFrame(cams[(size_t)c].frames[(size_t)k]);
+      const int j = keyframe_no(cams[(size_t)c], k);
+      if (j >= 0) df.addKeyframe(cams[(size_t)c].frames[(size_t)k], dm[0], dm[1], side.fts[(size_t)j]);
+    }
+    dump(side, df.getSeeds(), "lone_cam" + std::to_string(c));
+  }
+  std::printf("svo_host_demo filtergroup OK\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 3 && std::string(argv[3]) == "filtergroup") {
+    try {
+      return filter_group_demo(argv[1], argv[2]);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "svo_host_demo FAILED: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc > 3 && std::string(argv[3]) == "keyframes") {
     try {
       bool device_seeds = false, threaded = false;
@@ -662,7 +780,7 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n|churn|keyframes [device_seeds] [threaded]]\n", argv[0]); return 2; }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n|filtergroup|churn|keyframes [device_seeds] [threaded]]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {

@@ -876,6 +876,138 @@ class DepthFilter {
   std::unique_ptr<hip_bridge::PyramidCache> kf_pyr_, cur_pyr_;
 };
 
+/// The depth filters of N cameras with one camera model on ONE context, unthreaded: the counterpart of FrameTrackerGroup.  One
+/// keyframe PyramidCache and one current-frame cache are shared by the cameras; every camera has its own seed list, device mirror,
+/// convergence callback, detector grid and keyframe-batch counter.  addFrames() is DepthFilter::updateSeeds of all cameras as ONE
+/// device pass (hip_bridge::updateCameras -> svo_hip_seed_batch_update_cameras_async); each camera's callbacks, grid marks and
+/// erasures come in the order of a lone DepthFilter fed the same frames (tests/test_gpu_depth_filter_group_cpp.py).
+/// Frame ids are what the shared caches know a pyramid by: they must be unique across the cameras (Frame::frame_counter_ is).
+class DepthFilterGroup {
+ public:
+  typedef DepthFilter::callback_t callback_t;
+  DepthFilter::Options options_;
+  int sub_batch_ = 4096;
+  std::vector<hip_bridge::SeedBatchStats> last_stats_;        ///< per camera, of the last addFrames (a camera that sat out: zeros)
+
+  /// cbs[c]: seed_converged_cb of camera c; detectors[c] (optional): its feature detector's grid
+  explicit DepthFilterGroup(std::vector<callback_t> cbs, std::vector<DetectorGrid*> detectors = std::vector<DetectorGrid*>()) {
+    hip_bridge::check(svo_hip_ctx_create(&ctx_, 0, nullptr), nullptr, "ctx_create");
+    kf_pyr_.reset(new hip_bridge::PyramidCache(ctx_, 16));
+    cur_pyr_.reset(new hip_bridge::PyramidCache(ctx_, (int)std::max<size_t>(cbs.size(), 1)));
+    for (size_t c = 0; c < cbs.size(); ++c) {
+      cams_.emplace_back(new Camera);
+      cams_.back()->cb = std::move(cbs[c]);
+      cams_.back()->detector = c < detectors.size() ? detectors[c] : nullptr;
+    }
+    last_stats_.resize(cams_.size());
+  }
+  ~DepthFilterGroup() {
+    for (auto& cam : cams_) cam->mirror.clear();
+    kf_pyr_.reset(); cur_pyr_.reset();
+    svo_hip_ctx_destroy(ctx_);
+  }
+  size_t cameras() const { return cams_.size(); }
+
+  /// DepthFilter::addKeyframe of camera c without a thread: initializeSeeds (depth_filter.cpp:129-151) under the camera's own batch
+  /// counter (the reference's is one static for its one filter; age-out compares it with a seed's batch id)
+  void addKeyframe(size_t c, FramePtr frame, double depth_mean, double depth_min, const std::vector<Feature*>& new_features) {
+    (void)frame;
+    Camera& cam = *cams_.at(c);
+    Seed::batch_counter = ++cam.batch_counter;
+    for (Feature* ftr : new_features) cam.seeds.push_back(Seed(ftr, (float)depth_mean, (float)depth_min));
+  }
+
+  /// DepthFilter::addFrame for every camera, frames[c] camera c's new frame (null: the camera sits this pass out): ONE device pass
+  void addFrames(const std::vector<FramePtr>& frames) {
+    if (frames.size() != cams_.size()) throw std::invalid_argument("addFrames: one frame (or null) per camera");
+    std::vector<Mirror*> mirrors;
+    std::vector<GroupHost> host_objs;
+    std::vector<std::list<Seed>*> lists;
+    std::vector<Frame*> frs;
+    std::vector<int> counters;
+    std::vector<size_t> who;
+    std::vector<const Frame*> all_kfs, all_cur;
+    for (size_t c = 0; c < cams_.size(); ++c) {
+      last_stats_[c] = hip_bridge::SeedBatchStats();
+      Camera& cam = *cams_[c];
+      if (!frames[c] || cam.seeds.empty()) continue;
+      who.push_back(c);
+      mirrors.push_back(&cam.mirror); lists.push_back(&cam.seeds); frs.push_back(frames[c].get()); counters.push_back(cam.batch_counter);
+      host_objs.push_back(GroupHost{this, &cam});
+      all_cur.push_back(frames[c].get());
+      const Frame* prev = nullptr;
+      for (const Seed& s : cam.seeds)
+        if (s.ftr->frame != prev) { prev = s.ftr->frame; if (std::find(all_kfs.begin(), all_kfs.end(), prev) == all_kfs.end()) all_kfs.push_back(prev); }
+    }
+    if (who.empty()) return;
+    // The caches are shared: every keyframe that owns a seed of ANY camera and every current frame of the pass is made resident
+    // here, together, before the first camera resolves its slots.  The cameras' own look-ups in phase 1 then only find resident
+    // frames -- a resident frame keeps its slot (slot_table.h) -- so no camera's look-up can recycle a slot that another camera of
+    // the same pass was given.
+    std::vector<int> slots;
+    if (!kf_pyr_->acquire(all_kfs, slots) || !cur_pyr_->acquire(all_cur, slots)) throw std::runtime_error("DepthFilterGroup: frames of different geometry");
+    std::vector<GroupHost*> hosts;
+    for (GroupHost& h : host_objs) hosts.push_back(&h);
+    std::vector<hip_bridge::SeedBatchStats> st(who.size());
+    svo_hip_df_params prm{3, 10, 1000, options_.seed_convergence_sigma2_thresh};
+    hip_bridge::updateCameras(who.size(), mirrors.data(), hosts.data(), ctx_, lists.data(), frs.data(), prm, counters.data(), options_.max_n_kfs, halt_,
+                              st.data(), sub_batch_);
+    bool failed = false;
+    for (size_t k = 0; k < who.size(); ++k) { last_stats_[who[k]] = st[k]; failed = failed || st[k].n_device_errors != 0; }
+    if (failed) throw std::runtime_error(std::string("depth_filter_group_update: ") + svo_hip_last_error(ctx_));
+  }
+
+  /// camera c's seeds with the device state copied in (DepthFilter::getSeeds)
+  std::list<Seed>& getSeeds(size_t c) {
+    Camera& cam = *cams_.at(c);
+    if (!cam.mirror.syncToHost()) throw std::runtime_error(std::string("seed_batch_download: ") + svo_hip_last_error(ctx_));
+    return cam.seeds;
+  }
+  int keyframeUploads() const { return kf_pyr_->uploads(); }
+
+ private:
+  typedef hip_bridge::DeviceSeedMirror<std::list<Seed> > Mirror;
+  struct Camera {
+    callback_t cb;
+    DetectorGrid* detector = nullptr;
+    std::list<Seed> seeds;
+    Mirror mirror;
+    int batch_counter = 0;
+  };
+  /// Host policy of hip_bridge::DeviceSeedMirror for one camera of the group: the caches are the group's
+  struct GroupHost {
+    DepthFilterGroup* g;
+    Camera* cam;
+    Frame* keyframeOf(const Seed& s) const { return s.ftr->frame; }
+    void feature(const Seed& s, double px[2], double f[3], int* level) const {
+      px[0] = s.ftr->px[0]; px[1] = s.ftr->px[1];
+      for (int k = 0; k < 3; ++k) f[k] = s.ftr->f[k];
+      *level = s.ftr->level;
+    }
+    void pose7(const Frame& fr, double T[7]) const { std::memcpy(T, fr.T_f_w_.p, sizeof(double) * 7); }
+    bool keyframeSlots(const std::vector<Frame*>& kfs, std::vector<int>& slots) {
+      std::vector<const Frame*> c(kfs.begin(), kfs.end());
+      return g->kf_pyr_->acquire(c, slots);
+    }
+    int currentSlot(Frame& fr) { return g->cur_pyr_->slotOf(fr); }
+    svo_hip_pyramid* keyframePyramids() const { return g->kf_pyr_->pyramid(); }
+    svo_hip_pyramid* currentPyramids() const { return g->cur_pyr_->pyramid(); }
+    svo_hip_camera camera(const Frame& fr) const { return fr.cam_->toC(); }
+    bool isKeyframe(const Frame& fr) const { return fr.isKeyframe(); }
+    void setGridOccupancy(const double px_cur[2]) { if (cam->detector) cam->detector->setGridOccpuancy(Vector2d{{px_cur[0], px_cur[1]}}); }
+    void converged(Seed& s, const double xyz[3]) {
+      Point* point = new Point(Vector3d{{xyz[0], xyz[1], xyz[2]}}, s.ftr);
+      s.ftr->point = point;
+      cam->cb(point, s.sigma2);
+    }
+  };
+
+  std::vector<std::unique_ptr<Camera> > cams_;
+  volatile bool halt_ = false;
+  svo_hip_ctx* ctx_ = nullptr;
+  std::unique_ptr<hip_bridge::PyramidCache> kf_pyr_, cur_pyr_;
+};
+
 }  // namespace svo
 
 #endif  // SVO_HOST_H_

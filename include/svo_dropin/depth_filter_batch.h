@@ -88,6 +88,7 @@ class DeviceSeedMirror {
     known_size_ = 0; known_back_id_ = -1;
   }
   size_t deviceBatches() const { return batches_.size(); }
+  struct Pass;                           // what the phases of update() hand on (below)
 
   /// DepthFilter::updateSeeds(frame).  `sub_batch`: seeds per device batch (an upload unit; one frame's pass covers all).
   template <class Host, class Frame>
@@ -112,20 +113,70 @@ class DeviceSeedMirror {
     return svo_hip_seed_batch_mark_updated((int)passed.size(), passed.data(), g->cell_size, g->grid_cols, g->grid_rows, g->occupancy_dev);
   }
 
+  /// update() is the composition of the three phases below (unchanged in behaviour); updateCameras() at the end of this header runs
+  /// phase 1 for several mirrors, makes ONE device call for all of them and runs phase 3 per mirror.
   template <class Mode, class Host, class Frame>
   SeedBatchStats updateImpl(Mode mode, Host& host, svo_hip_ctx* ctx, SeedList& seeds, Frame& frame, const svo_hip_df_params& prm,
                             int batch_counter, int max_n_kfs, const volatile bool& halt, int sub_batch, const DeviceGrid* device_grid) {
+    Pass p;
+    if (!preparePass(host, ctx, seeds, frame, batch_counter, max_n_kfs, halt, sub_batch, device_grid, p)) return p.st;
+    launchPass(mode, host, prm, device_grid, p);
+    collectPass(host, seeds, p);
+    return p.st;
+  }
+
+  /// phase 2, one mirror: the batches of the frame through ONE set of launches (svo_hip_seed_batch_update_group_async)
+  template <class Mode, class Host>
+  void launchPass(Mode mode, Host& host, const svo_hip_df_params& prm, const DeviceGrid* device_grid, Pass& p) {
+    SeedBatchStats& st = p.st;
+    if (p.devs.empty()) return;
+    st.n_device_calls += (int)p.devs.size();
+    const int rc = svo_hip_seed_batch_update_group_async((int)p.devs.size(), p.devs.data(), host.keyframePyramids(), p.slots.data(),
+                                                         host.currentPyramids(), p.cur_slot, &p.cam, p.T_refs.data(), p.T_cur, &prm,
+                                                         p.is_keyframe && !p.mark_on_device ? 1 : 0);
+    // A failure leaves up to 8 batches at a time either enqueued or not (svo_hip.h): the collect loop takes
+    // every batch that has a pass pending -- its seeds WERE updated -- and skips the others, so nothing stays
+    // pending into the next frame.
+    if (rc != SVO_HIP_OK) ++st.n_device_errors;
+    if (p.mark_on_device) {
+      // behind the pass on the stream, one call for the frame's set: the batches whose pass was enqueued
+      std::vector<svo_hip_seed_batch*> passed;
+      for (size_t j = 0; j < p.devs.size(); ++j)
+        if (svo_hip_seed_batch_pending(p.devs[j])) passed.push_back(p.devs[j]);
+      if (!passed.empty() && markUpdated(mode, passed, device_grid) != SVO_HIP_OK) ++st.n_device_errors;
+    }
+  }
+
+ public:
+  /// What phase 1 hands to the device call and to the collect loop of one frame
+  struct Pass {
     SeedBatchStats st;
+    svo_hip_camera cam;
+    int cur_slot = -1;
+    double T_cur[7];
+    bool is_keyframe = false, mark_on_device = false;
+    std::vector<svo_hip_seed_batch*> devs;     // the batches of the pass, list order ...
+    std::vector<int> slots;                    // ... their keyframes' pyramid slots ...
+    std::vector<double> T_refs;                // ... and poses [7] each
+    std::vector<size_t> enqueued;              // their positions in the mirror
+  };
+
+  /// Phase 1: the list against the mirror (new seeds, foreign erasures), age-out (:256-261), and the batches, slots and poses of
+  /// the frame's pass.  false: update() ends here with p.st (halted, nothing to update, no slot for the frame, a device error).
+  template <class Host, class Frame>
+  bool preparePass(Host& host, svo_hip_ctx* ctx, SeedList& seeds, Frame& frame, int batch_counter, int max_n_kfs, const volatile bool& halt,
+                   int sub_batch, const DeviceGrid* device_grid, Pass& p) {
+    SeedBatchStats& st = p.st;
     if (sub_batch < 1) sub_batch = 1;
-    if (halt) { st.halted = true; return st; }
+    if (halt) { st.halted = true; return false; }
     // ---- the list against the mirror: new seeds (initializeSeeds pushed a keyframe's batch) or foreign erasures
     const int back_id = seeds.empty() ? -1 : seeds.back().id;
     if (seeds.size() != known_size_ || back_id != known_back_id_) {
-      if (!reconcile(host, ctx, seeds, sub_batch, st)) { ++st.n_device_errors; return st; }
+      if (!reconcile(host, ctx, seeds, sub_batch, st)) { ++st.n_device_errors; return false; }
     }
     // ---- age-out (:256-261): batches older than max_n_kfs keyframes leave the list and the device
     for (size_t k = 0; k < batches_.size();) {
-      if (halt) { st.halted = true; remember(seeds); return st; }
+      if (halt) { st.halted = true; remember(seeds); return false; }
       Batch& b = batches_[k];
       if ((batch_counter - b.batch_id) > max_n_kfs) {
         for (size_t i = 0; i < b.its.size(); ++i)
@@ -138,63 +189,44 @@ class DeviceSeedMirror {
     }
     for (size_t k = 0; k < batches_.size(); ++k) st.n_seeds += batches_[k].n_alive;
     remember(seeds);
-    if (batches_.empty()) return st;
+    if (batches_.empty()) return false;
 
-    const svo_hip_camera cam = host.camera(frame);
-    const int cur_slot = host.currentSlot(frame);
-    if (cur_slot < 0) return st;
-    double T_cur[7];
-    host.pose7(frame, T_cur);
-    const bool is_keyframe = host.isKeyframe(frame);
-    const bool mark_on_device = is_keyframe && device_grid != NULL;    // the grid marks of :302-306 stay on the device
+    p.cam = host.camera(frame);
+    p.cur_slot = host.currentSlot(frame);
+    if (p.cur_slot < 0) return false;
+    host.pose7(frame, p.T_cur);
+    p.is_keyframe = host.isKeyframe(frame);
+    p.mark_on_device = p.is_keyframe && device_grid != NULL;    // the grid marks of :302-306 stay on the device
 
-    // ---- device: the batches of the frame through ONE set of launches (svo_hip_seed_batch_update_group_async), awaited in
-    // list order
-    std::vector<size_t> enqueued;
-    if (halt) { st.halted = true; return st; }
-    {
-      std::vector<svo_hip_seed_batch*> devs;
-      std::vector<int> slots;
-      std::vector<double> T_refs;
-      // the keyframes of every batch with live seeds, resolved TOGETHER: a slot handed out for one keyframe of this pass must
-      // not be recycled for another (with more keyframes alive than the cache had slots, a one-at-a-time look-up did that,
-      // and the first keyframe's seeds were matched against the second one's image)
-      typedef decltype(((SeedT*)0)->ftr->frame) FramePtrT;
-      std::vector<FramePtrT> kfs;
-      std::vector<size_t> which;
-      for (size_t k = 0; k < batches_.size(); ++k)
-        if (batches_[k].n_alive != 0) { kfs.push_back(batches_[k].kf); which.push_back(k); }
-      std::vector<int> kf_slots;
-      if (!kfs.empty() && !host.keyframeSlots(kfs, kf_slots)) { ++st.n_device_errors; return st; }
-      for (size_t j = 0; j < which.size(); ++j) {
-        Batch& b = batches_[which[j]];
-        if (kf_slots[j] < 0) continue;
-        double T_ref[7];
-        host.pose7(*b.kf, T_ref);
-        devs.push_back(b.dev); slots.push_back(kf_slots[j]); T_refs.insert(T_refs.end(), T_ref, T_ref + 7);
-        enqueued.push_back(which[j]);
-      }
-      if (!devs.empty()) {
-        st.n_device_calls += (int)devs.size();
-        const int rc = svo_hip_seed_batch_update_group_async((int)devs.size(), devs.data(), host.keyframePyramids(), slots.data(),
-                                                             host.currentPyramids(), cur_slot, &cam, T_refs.data(), T_cur, &prm,
-                                                             is_keyframe && !mark_on_device ? 1 : 0);
-        // A failure leaves up to 8 batches at a time either enqueued or not (svo_hip.h): the collect loop below takes
-        // every batch that has a pass pending -- its seeds WERE updated -- and skips the others, so nothing stays
-        // pending into the next frame.
-        if (rc != SVO_HIP_OK) ++st.n_device_errors;
-        if (mark_on_device) {
-          // behind the pass on the stream, one call for the frame's set: the batches whose pass was enqueued
-          std::vector<svo_hip_seed_batch*> passed;
-          for (size_t j = 0; j < devs.size(); ++j)
-            if (svo_hip_seed_batch_pending(devs[j])) passed.push_back(devs[j]);
-          if (!passed.empty() && markUpdated(mode, passed, device_grid) != SVO_HIP_OK) ++st.n_device_errors;
-        }
-      }
+    if (halt) { st.halted = true; return false; }
+    // the keyframes of every batch with live seeds, resolved TOGETHER: a slot handed out for one keyframe of this pass must
+    // not be recycled for another (with more keyframes alive than the cache had slots, a one-at-a-time look-up did that,
+    // and the first keyframe's seeds were matched against the second one's image)
+    typedef decltype(((SeedT*)0)->ftr->frame) FramePtrT;
+    std::vector<FramePtrT> kfs;
+    std::vector<size_t> which;
+    for (size_t k = 0; k < batches_.size(); ++k)
+      if (batches_[k].n_alive != 0) { kfs.push_back(batches_[k].kf); which.push_back(k); }
+    std::vector<int> kf_slots;
+    if (!kfs.empty() && !host.keyframeSlots(kfs, kf_slots)) { ++st.n_device_errors; return false; }
+    for (size_t j = 0; j < which.size(); ++j) {
+      Batch& b = batches_[which[j]];
+      if (kf_slots[j] < 0) continue;
+      double T_ref[7];
+      host.pose7(*b.kf, T_ref);
+      p.devs.push_back(b.dev); p.slots.push_back(kf_slots[j]); p.T_refs.insert(p.T_refs.end(), T_ref, T_ref + 7);
+      p.enqueued.push_back(which[j]);
     }
-    // ---- the events, in list order: grid marks, callbacks, erasures (:302-337)
-    for (size_t e = 0; e < enqueued.size(); ++e) {
-      Batch& b = batches_[enqueued[e]];
+    return true;
+  }
+
+  /// Phase 3: the events of the batches whose pass was enqueued, in list order: grid marks, callbacks, erasures (:302-337); batches
+  /// without a live seed are dropped.
+  template <class Host>
+  void collectPass(Host& host, SeedList& seeds, Pass& p) {
+    SeedBatchStats& st = p.st;
+    for (size_t e = 0; e < p.enqueued.size(); ++e) {
+      Batch& b = batches_[p.enqueued[e]];
       const svo_hip_seed_event* ev = NULL;
       int n_ev = 0;
       int32_t counts[7];
@@ -206,7 +238,7 @@ class DeviceSeedMirror {
         const svo_hip_seed_event& x = ev[j];
         if (x.index < 0 || (size_t)x.index >= b.its.size() || !b.alive[(size_t)x.index]) continue;
         It it = b.its[(size_t)x.index];
-        if (is_keyframe && !mark_on_device) host.setGridOccupancy(x.px_cur);   // :302-306
+        if (p.is_keyframe && !p.mark_on_device) host.setGridOccupancy(x.px_cur);   // :302-306
         if (x.status == SVO_HIP_SEED_CONVERGED) {                   // :310-331
           it->mu = x.mu; it->sigma2 = x.sigma2;
           host.converged(*it, x.xyz_world);
@@ -224,10 +256,8 @@ class DeviceSeedMirror {
       else ++k;
     }
     remember(seeds);
-    return st;
   }
 
- public:
   /// A batch that was created on the device from a detection (svo_hip_seed_batch_create_detected) joins the mirror: the n
   /// list entries the host has just pushed for it, `first` onwards, are its seeds 0..n-1 (batch id `batch_id`, keyframe `kf`).
   /// The mirror owns the batch from here on.  As after reconcile(): the entries are known (where_), the batch stands at the end
@@ -376,6 +406,51 @@ class DeviceSeedMirror {
     return true;
   }
 };
+
+/// DepthFilter::updateSeeds for SEVERAL cameras of one context -- camera c: mirror, host policy, seed list, frame and batch
+/// counter number c -- with ONE device call for all of them (svo_hip_seed_batch_update_cameras_async): phase 1 per mirror in
+/// camera order, the call, phase 3 per mirror in camera order, so that every camera's callbacks, grid marks and erasures come in
+/// the order of its own update().  One camera model and one pair of pyramid batches for all cameras (those of camera 0's host);
+/// a keyframe's updated seeds are reported to Host::setGridOccupancy (no device grid here).
+/// The hosts must SHARE their two pyramid caches: the call takes the batches of hosts[0] for every camera's slots, and nothing here
+/// can check that.  With shared caches a later camera's keyframeSlots() / currentSlot() must not recycle a slot an earlier camera of
+/// the same pass was given: the caller makes every frame of the pass resident TOGETHER before this call, so that the cameras'
+/// look-ups only find resident frames (svo::DepthFilterGroup::addFrames does; slot_table.h: a resident frame keeps its slot).  stats[c]: as update() returns them;
+/// n_device_calls counts the camera's batches in the call.  (The only user of that entry point in this header: code that
+/// never instantiates this template need not link it.)
+template <class Mirror, class Host, class SeedList, class Frame>
+void updateCameras(size_t n_cameras, Mirror* const* mirrors, Host* const* hosts, svo_hip_ctx* ctx, SeedList* const* seeds, Frame* const* frames,
+                   const svo_hip_df_params& prm, const int* batch_counters, int max_n_kfs, const volatile bool& halt, SeedBatchStats* stats,
+                   int sub_batch = 4096) {
+  std::vector<typename Mirror::Pass> passes(n_cameras);
+  std::vector<svo_hip_seed_camera_pass> cams(n_cameras);
+  std::vector<uint8_t> runs(n_cameras, 0);
+  const svo_hip_camera* cam = NULL;
+  for (size_t c = 0; c < n_cameras; ++c) {
+    typename Mirror::Pass& p = passes[c];
+    svo_hip_seed_camera_pass& cp = cams[c];
+    cp.n_batches = 0; cp.batches = NULL; cp.ref_slots = NULL; cp.T_ref_w = NULL; cp.cur_slot = 0; cp.report_updated = 0;
+    for (int i = 0; i < 7; ++i) cp.T_cur_w[i] = 0.0;
+    runs[c] = mirrors[c]->preparePass(*hosts[c], ctx, *seeds[c], *frames[c], batch_counters[c], max_n_kfs, halt, sub_batch, NULL, p) ? 1 : 0;
+    if (!runs[c] || p.devs.empty()) continue;
+    cp.n_batches = (int)p.devs.size(); cp.batches = p.devs.data(); cp.ref_slots = p.slots.data(); cp.T_ref_w = p.T_refs.data();
+    cp.cur_slot = p.cur_slot; cp.report_updated = p.is_keyframe ? 1 : 0;
+    for (int i = 0; i < 7; ++i) cp.T_cur_w[i] = p.T_cur[i];
+    p.st.n_device_calls += cp.n_batches;
+    if (!cam) cam = &p.cam;
+  }
+  if (cam) {
+    const int rc = svo_hip_seed_batch_update_cameras_async(ctx, (int)n_cameras, cams.data(), hosts[0]->keyframePyramids(), hosts[0]->currentPyramids(),
+                                                           cam, &prm);
+    // a refused or failed call has enqueued nothing or has waited for what it had: the collect loops skip batches without a pass
+    if (rc != SVO_HIP_OK)
+      for (size_t c = 0; c < n_cameras; ++c) if (cams[c].n_batches) ++passes[c].st.n_device_errors;
+  }
+  for (size_t c = 0; c < n_cameras; ++c) {
+    if (runs[c]) mirrors[c]->collectPass(*hosts[c], *seeds[c], passes[c]);
+    stats[c] = passes[c].st;
+  }
+}
 
 }  // namespace hip_bridge
 }  // namespace svo

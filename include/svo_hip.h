@@ -549,6 +549,36 @@ int svo_hip_seed_batch_update_group_async(int n_batches, svo_hip_seed_batch* con
                                           const int* ref_slots, const svo_hip_pyramid* cur, int cur_slot,
                                           const svo_hip_camera* cam, const double* T_ref_w /* [n_batches][7] */,
                                           const double T_cur_w[7], const svo_hip_df_params* prm, int report_updated);
+/* The pass of SEVERAL cameras -- each with its own current frame (slot cur_slot of `cur`), pose, keyframe flag and batches --
+ * as ONE set of launches whatever the number of cameras and batches: the depth filter's counterpart of a tracker group, one
+ * camera model for all cameras.  Camera c's batch k runs against keyframe slot ref_slots[k] of `ref` with pose T_ref_w[7 * k ..]
+ * and against the camera's own current image, pose and report_updated.  Results per batch are bit-identical to one
+ * svo_hip_seed_batch_update_group_async per camera; collect, pending, erase, download and mark_updated work on the batches
+ * afterwards as after that call.  The form is chosen as there (two launches up to the small-pass limit, six beyond).
+ * The table of the jobs (a batch's arrays, transforms, current slot and keyframe flag) and the map from every 256-seed block
+ * to its job live in device memory of the context: one packed transfer per call out of page-locked staging, both grow-only
+ * (no allocator call after a warm-up call).  A call may follow another for other batches without a collect in between: the
+ * staging area is rewritten only once the previous call's transfer has left it.
+ * At most SVO_HIP_DF_CAMERAS_MAX_JOBS batches and SVO_HIP_DF_CAMERAS_MAX_RECORDS seed records (every batch rounded up to 256)
+ * per call.  Everything is checked before anything is enqueued and a refused call changes nothing: SVO_HIP_ERR_INVALID for a
+ * null argument, a batch of another context, a batch named twice (also under two cameras), a slot out of range, image sizes
+ * that differ from `cam` and a capacity exceeded; SVO_HIP_ERR_STATE for a batch whose previous pass is not collected.  A call
+ * without any batch returns SVO_HIP_OK and launches nothing.  A device failure after the first enqueue synchronises the stream
+ * before it returns (nothing of the call is still in flight when the caller unwinds). */
+#define SVO_HIP_DF_CAMERAS_MAX_JOBS 1024
+#define SVO_HIP_DF_CAMERAS_MAX_RECORDS (1 << 20)
+typedef struct {
+  int n_batches;                          /* 0: the camera sits this pass out */
+  svo_hip_seed_batch* const* batches;     /* [n_batches], all of the call's context */
+  const int* ref_slots;                   /* [n_batches] slots of `ref` */
+  const double* T_ref_w;                  /* [n_batches][7] */
+  int cur_slot;                           /* slot of `cur` holding this camera's current frame */
+  double T_cur_w[7];
+  int report_updated;                     /* this camera's frame is a keyframe */
+} svo_hip_seed_camera_pass;
+int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, const svo_hip_seed_camera_pass* passes,
+                                            const svo_hip_pyramid* ref, const svo_hip_pyramid* cur,
+                                            const svo_hip_camera* cam, const svo_hip_df_params* prm);
 /* diagnostic / tuning: passes of at most max_seeds seed records (sum over the batches of a call, each rounded up to 256)
  * run as TWO launches -- one wave takes its four seeds through geometry, search, alignment and update, then one workgroup
  * per batch writes the events -- instead of six; results are bit-identical.  0 switches the form off; at most 16384;
@@ -712,6 +742,13 @@ int svo_hip_tracker_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const sv
 int svo_hip_tracker_destroy(svo_hip_tracker* trk);
 /* grid geometry (Reprojector::initializeGrid, reprojector.cpp:44-55) and the keyframe pyramid batch (borrowed) */
 int svo_hip_tracker_info(const svo_hip_tracker* trk, int* n_cells, int* grid_cols, int* grid_rows, svo_hip_pyramid** keyframe_pyramids);
+/* The pyramid batch that holds the last frames of the tracker's group, and this camera's slot in it (0 for a lone tracker).
+ * The batch is BORROWED: it is valid until the next call that tracks, relocalises or sets a last frame on this tracker or its
+ * group (the two frame batches swap roles every tracked frame).  A pass that reads it (svo_hip_seed_batch_update_cameras_async)
+ * must run on the tracker's context: the stream then orders the pass behind the track call and in front of the next one.
+ * With svo_hip_tracker_info's keyframe batch (camera c's keyframe slot s is slot c * max_keyframes + s) a group's depth pass
+ * needs no image upload and no pyramid build of its own.  SVO_HIP_ERR_STATE when the tracker has no last frame. */
+int svo_hip_tracker_last_frame_pyramid(svo_hip_tracker* trk, const svo_hip_pyramid** pyr, int* slot);
 /* keyframe images: level 0 from the host (pyramid built on the device), or the pyramid of the last tracked frame
  * (FrameHandlerMono: new_frame_->setKeyframe(); map_.addKeyframe(new_frame_), :284-330) */
 int svo_hip_tracker_upload_keyframe(svo_hip_tracker* trk, int slot, const uint8_t* level0);
