@@ -940,13 +940,25 @@ static int df_jobs_area(svo_hip_ctx* ctx, size_t need) {
   return SVO_HIP_OK;
 }
 
-int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, const svo_hip_seed_camera_pass* passes, const svo_hip_pyramid* ref,
-                                            const svo_hip_pyramid* cur, const svo_hip_camera* cam, const svo_hip_df_params* prm) {
+// what a pass takes from a camera's model, for the pass's camera table
+static DfCamModel df_cam_model(const svo_hip_camera* cam) {
+  DfCamModel m;
+  memset(&m, 0, sizeof(m));
+  m.cam = svo_make_cam(*cam);
+  m.px_error_angle = atan(1.0 / (2.0 * fabs(cam->fx))) * 2.0;        // depth_filter.cpp:245-247
+  return m;
+}
+
+// The pass over the batches of several cameras: camera c's model is cams[c * cam_stride] -- stride 1 for a rig, 0 for the one
+// model all cameras of svo_hip_seed_batch_update_cameras_async share (its camera table then has one entry).
+static int df_cameras_pass(svo_hip_ctx* ctx, const char* who, int n_cameras, const svo_hip_seed_camera_pass* passes, const svo_hip_pyramid* ref,
+                           const svo_hip_pyramid* cur, const svo_hip_camera* cams, int cam_stride, const svo_hip_df_params* prm) {
   if (!ctx) return SVO_HIP_ERR_INVALID;
-  const char* who = "svo_hip_seed_batch_update_cameras_async";
-  if (!passes || !ref || !cur || !cam || !prm) return svo_fail(ctx, SVO_HIP_ERR_INVALID, who, "null argument");
+  if (!passes || !ref || !cur || !cams || !prm) return svo_fail(ctx, SVO_HIP_ERR_INVALID, who, "null argument");
   SVO_REQUIRE(ctx, n_cameras >= 0);
   // ---- every camera's and every batch's arguments are checked before anything is enqueued
+  const int n_models = cam_stride ? n_cameras : 1;
+  for (int m = 1; m < n_models; ++m) SVO_REQUIRE(ctx, cams[m].width == cams[0].width && cams[m].height == cams[0].height);
   // (the call's serial, stamped on the batches the walk has passed, is how a batch named twice is found; it is the one thing a
   // refused call leaves behind, and it means nothing to the next call, which has a serial of its own)
   const unsigned long long serial = ++ctx->df_jobs_serial;
@@ -968,7 +980,8 @@ int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, con
     }
     n_jobs_ll += P.n_batches;
   }
-  if (const int rc = df_check_pass_args(ctx, ref, 0, nullptr, cur, 0, cam, prm); rc != SVO_HIP_OK) return rc;
+  if (n_models > 0)                                        // (all models have the size of the first)
+    if (const int rc = df_check_pass_args(ctx, ref, 0, nullptr, cur, 0, &cams[0], prm); rc != SVO_HIP_OK) return rc;
   SVO_REQUIRE(ctx, n_jobs_ll <= SVO_HIP_DF_CAMERAS_MAX_JOBS && n_blocks_ll * 256 <= SVO_HIP_DF_CAMERAS_MAX_RECORDS);
   if (n_jobs_ll == 0) return SVO_HIP_OK;
   const int n_jobs = (int)n_jobs_ll, n_blocks = (int)n_blocks_ll, n_rec = n_blocks * 256;
@@ -979,12 +992,15 @@ int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, con
   if (const int rc = svo_ctx_scratch(ctx, rec_bytes + pwb_bytes + (size_t)n_rec * sizeof(int32_t), &ws); rc != SVO_HIP_OK) return rc;
   const DfScratch s = {(SeedRec*)ws, reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + rec_bytes), n_rec};
   int32_t* level_cat = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + rec_bytes + pwb_bytes);
-  const size_t jobs_bytes = (size_t)n_jobs * sizeof(DfCamJob), table_bytes = jobs_bytes + (size_t)n_blocks * sizeof(int);
+  const size_t jobs_bytes = (size_t)n_jobs * sizeof(DfCamJob), cams_off = (jobs_bytes + (size_t)n_blocks * sizeof(int) + 7) & ~(size_t)7,
+               table_bytes = cams_off + (size_t)n_models * sizeof(DfCamModel);
   if (const int rc = df_jobs_area(ctx, table_bytes); rc != SVO_HIP_OK) return rc;
-  // ---- the table, packed: [jobs][block -> job]
+  // ---- the table, packed: [jobs][block -> job][camera models]
   DfCamJob* jobs_host = static_cast<DfCamJob*>(ctx->df_jobs_host);
   int* block_job_host = reinterpret_cast<int*>(static_cast<char*>(ctx->df_jobs_host) + jobs_bytes);
-  memset(jobs_host, 0, jobs_bytes);
+  DfCamModel* cams_host = reinterpret_cast<DfCamModel*>(static_cast<char*>(ctx->df_jobs_host) + cams_off);
+  memset(jobs_host, 0, cams_off);
+  for (int m = 0; m < n_models; ++m) cams_host[m] = df_cam_model(&cams[m]);
   int j = 0, first_block = 0;
   for (int c = 0; c < n_cameras; ++c) {
     const svo_hip_seed_camera_pass& P = passes[c];
@@ -993,14 +1009,16 @@ int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, con
       sb_fill_job(jobs_host[j].job, sb, P.T_ref_w + 7 * (size_t)k, P.T_cur_w, first_block, P.ref_slots[k]);
       jobs_host[j].cur_slot = P.cur_slot;
       jobs_host[j].report_updated = P.report_updated ? 1 : 0;
+      jobs_host[j].cam = c * cam_stride;
       for (int b = 0; b < sb->n_blocks; ++b) block_job_host[first_block + b] = j;
       first_block += sb->n_blocks;
     }
   }
   const DfCamJob* jobs = static_cast<const DfCamJob*>(ctx->df_jobs_dev);
   const int* block_job = reinterpret_cast<const int*>(static_cast<const char*>(ctx->df_jobs_dev) + jobs_bytes);
-  DfFrame fr;
-  df_make_pass_frame(ref, cur, cam, prm, fr);
+  const DfCamModel* cam_table = reinterpret_cast<const DfCamModel*>(static_cast<const char*>(ctx->df_jobs_dev) + cams_off);
+  DfFrame fr;                                              // (its cam gives the kernels the common image size and nothing else)
+  df_make_pass_frame(ref, cur, &cams[0], prm, fr);
   const bool prof = ctx->df_profile;
   // ---- the transfer and the launches; from here on an error path waits for the stream before it returns
   hipError_t e = hipMemcpyAsync(ctx->df_jobs_dev, ctx->df_jobs_host, table_bytes, hipMemcpyHostToDevice, ctx->stream);
@@ -1012,21 +1030,21 @@ int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, con
     const dim3 fine(n_blocks * (256 / SEEDS_PER_BLOCK));   // 16 records (search) or 16 patches (align) a workgroup
     static_assert(SEEDS_PER_BLOCK == ALIGN_PATCHES && 256 % SEEDS_PER_BLOCK == 0, "one fine grid for both pixel stages");
     if (n_rec <= ctx->df_small_max) {
-      hipLaunchKernelGGL(df_small_pass_jobs_kernel, fine, dim3(256), 0, ctx->stream, fr, jobs, block_job, ref->base, ref->pyr_bytes, cur->base,
-                         cur->pyr_bytes, s.recs, s.pwb_t, level_cat, s.n_pad);
+      hipLaunchKernelGGL(df_small_pass_jobs_kernel, fine, dim3(256), 0, ctx->stream, fr, jobs, block_job, cam_table, ref->base, ref->pyr_bytes,
+                         cur->base, cur->pyr_bytes, s.recs, s.pwb_t, level_cat, s.n_pad);
       df_stamp(ctx, 1); df_stamp(ctx, 2); df_stamp(ctx, 3);
       if (prof) { (void)hipEventRecord(ctx->df_ev[4], ctx->stream); ctx->df_ev_recorded = true; }
       hipLaunchKernelGGL(ev_small_jobs_kernel, dim3(n_jobs), dim3(1024), 0, ctx->stream, jobs);
     } else {
-      hipLaunchKernelGGL(df_geometry_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, block_job, s.recs, level_cat);
+      hipLaunchKernelGGL(df_geometry_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, block_job, cam_table, s.recs, level_cat);
       df_stamp(ctx, 1);
-      hipLaunchKernelGGL(df_search_jobs_kernel, fine, dim3(256), 0, ctx->stream, fr, jobs, block_job, ref->base, ref->pyr_bytes, cur->base,
-                         cur->pyr_bytes, (const int32_t*)level_cat, s.recs, s.pwb_t, s.n_pad);
+      hipLaunchKernelGGL(df_search_jobs_kernel, fine, dim3(256), 0, ctx->stream, fr, jobs, block_job, cam_table, ref->base, ref->pyr_bytes,
+                         cur->base, cur->pyr_bytes, (const int32_t*)level_cat, s.recs, s.pwb_t, s.n_pad);
       df_stamp(ctx, 2);
       hipLaunchKernelGGL(df_align_jobs_kernel, fine, dim3(ALIGN_BLOCK), 0, ctx->stream, fr, jobs, block_job, cur->base, cur->pyr_bytes, s.n_pad,
                          (const uint32_t*)s.pwb_t, s.recs);
       df_stamp(ctx, 3);
-      hipLaunchKernelGGL(df_finalize_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, block_job, (const SeedRec*)s.recs);
+      hipLaunchKernelGGL(df_finalize_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, block_job, cam_table, (const SeedRec*)s.recs);
       if (prof) { (void)hipEventRecord(ctx->df_ev[4], ctx->stream); ctx->df_ev_recorded = true; }
       hipLaunchKernelGGL(ev_scan_jobs_kernel, dim3(n_jobs), dim3(1024), 0, ctx->stream, jobs);
       hipLaunchKernelGGL(ev_scatter_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, jobs, block_job);
@@ -1041,6 +1059,17 @@ int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, con
   for (int c = 0; c < n_cameras; ++c)
     for (int k = 0; k < passes[c].n_batches; ++k) { passes[c].batches[k]->pending = true; passes[c].batches[k]->report_updated = passes[c].report_updated ? 1 : 0; }
   return SVO_HIP_OK;
+}
+
+int svo_hip_seed_batch_update_rig_async(svo_hip_ctx* ctx, int n_cameras, const svo_hip_seed_camera_pass* passes, const svo_hip_pyramid* ref,
+                                        const svo_hip_pyramid* cur, const svo_hip_camera* cams, const svo_hip_df_params* prm) {
+  return df_cameras_pass(ctx, "svo_hip_seed_batch_update_rig_async", n_cameras, passes, ref, cur, cams, 1, prm);
+}
+
+// one camera model for all cameras: the rig pass with that model repeated
+int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, const svo_hip_seed_camera_pass* passes, const svo_hip_pyramid* ref,
+                                            const svo_hip_pyramid* cur, const svo_hip_camera* cam, const svo_hip_df_params* prm) {
+  return df_cameras_pass(ctx, "svo_hip_seed_batch_update_cameras_async", n_cameras, passes, ref, cur, cam, 0, prm);
 }
 
 int svo_hip_df_set_small_pass_limit(svo_hip_ctx* ctx, int max_seeds) {

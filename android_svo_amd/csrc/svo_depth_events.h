@@ -139,11 +139,11 @@ __global__ void records_clamp_copy_kernel(const double* __restrict__ rec, const 
 }
 
 // the geometry of seed i of batch J into record r of the pass
-SVO_DEV void df_geometry_job_seed(const DfFrame& fr, const DfJob& J, int i, size_t r, SeedRec* __restrict__ recs,
+SVO_DEV void df_geometry_job_seed(const DfFrame& fr, const Cam& cam, const DfJob& J, int i, size_t r, SeedRec* __restrict__ recs,
                                   int32_t* __restrict__ level_cat) {
   if (i < J.n) {
     level_cat[r] = J.level[i];
-    df_geometry_seed<false>(fr.cam, J.T.T_cur_ref_vis, J.T.T_cur_ref, fr.n_pyr_levels, fr.max_epi_search_steps, J.ref_slot, i, J.n, J.px, J.f,
+    df_geometry_seed<false>(cam, J.T.T_cur_ref_vis, J.T.T_cur_ref, fr.n_pyr_levels, fr.max_epi_search_steps, J.ref_slot, i, J.n, J.px, J.f,
                             J.level, J.mu, J.sigma2, nullptr, nullptr, recs + r, J.alive);
   } else {                                                 // the tail of the batch's last block: records no stage touches
     SeedRec rc = md_dead_record();
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void df_geometry_group_kernel(DfFrame fr, DfGr
   const DfJob& J = g.job[job_of_block(g, blockIdx.x)];
   const int i = (blockIdx.x - J.first_block) * 256 + threadIdx.x;       // seed of its batch
   if (i < 8) J.hist[i] = 0;
-  df_geometry_job_seed(fr, J, i, (size_t)blockIdx.x * 256 + threadIdx.x, recs, level_cat);
+  df_geometry_job_seed(fr, fr.cam, J, i, (size_t)blockIdx.x * 256 + threadIdx.x, recs, level_cat);
 }
 
 __global__ __launch_bounds__(256) void df_finalize_group_kernel(DfFrame fr, DfGroup g, const SeedRec* __restrict__ recs) {
@@ -217,11 +217,11 @@ __global__ __launch_bounds__(256) void df_small_pass_kernel(DfFrame fr, DfGroup 
   const DfJob& J = g.job[job_of_block(g, blockIdx.x >> 4)];          // 16 of these workgroups per 256-seed block
   const int i0 = r0 - J.first_block * 256;                 // ... and its first seed within its batch
   // ---- geometry
-  if (lane < SEEDS_PER_WAVE) df_geometry_job_seed(fr, J, i0 + lane, (size_t)r0 + lane, recs, level_cat);
+  if (lane < SEEDS_PER_WAVE) df_geometry_job_seed(fr, fr.cam, J, i0 + lane, (size_t)r0 + lane, recs, level_cat);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // ---- warp + epipolar search
-  df_search_block(fr, ref_base, ref_pyr_bytes, cur_pyr, n_cat, level_cat, recs, pwb_t, n_pad, blockIdx.x);
+  df_search_block(fr, fr.cam, ref_base, ref_pyr_bytes, cur_pyr, n_cat, level_cat, recs, pwb_t, n_pad, blockIdx.x);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // ---- align2D
@@ -281,25 +281,32 @@ __global__ __launch_bounds__(1024) void ev_small_kernel(DfGroup g) {
 // kernel arguments: a block finds its job with one load from the block -> job map, the job's fields are block-uniform, its
 // report_updated stands where the group's stood, its cur_slot picks the current image in the pixel stages.  The same device
 // functions as above, so every per-seed result and every event is bit-identical to a grouped pass per camera
-// (tests/test_gpu_seed_cameras.py).  DfFrame::T is not read: the transforms are the job's.
+// (tests/test_gpu_seed_cameras.py).  DfFrame::T is not read: the transforms are the job's.  Neither are DfFrame::cam and
+// DfFrame::px_error_angle: they are those of the job's entry in the camera table (DfCamModel), one more block-uniform load, taken
+// before the kernel's first store so that it stays a scalar load.  With one model in every entry that is the pass it was, bit
+// for bit; with a model per camera every batch equals a grouped pass with its camera's model (tests/test_gpu_seed_rig.py).
 __global__ __launch_bounds__(256) void df_geometry_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
-                                                               SeedRec* __restrict__ recs, int32_t* __restrict__ level_cat) {
-  const DfJob& J = jobs[block_job[blockIdx.x]].job;
+                                                               const DfCamModel* __restrict__ cams, SeedRec* __restrict__ recs,
+                                                               int32_t* __restrict__ level_cat) {
+  const DfCamJob& C = jobs[block_job[blockIdx.x]];
+  const DfJob& J = C.job;
+  const Cam cam = cams[C.cam].cam;
   const int i = (blockIdx.x - J.first_block) * 256 + threadIdx.x;       // seed of its batch
   if (i < 8) J.hist[i] = 0;
-  df_geometry_job_seed(fr, J, i, (size_t)blockIdx.x * 256 + threadIdx.x, recs, level_cat);
+  df_geometry_job_seed(fr, cam, J, i, (size_t)blockIdx.x * 256 + threadIdx.x, recs, level_cat);
 }
 
 __global__ __launch_bounds__(256) void df_finalize_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
-                                                               const SeedRec* __restrict__ recs) {
+                                                               const DfCamModel* __restrict__ cams, const SeedRec* __restrict__ recs) {
   const DfCamJob& C = jobs[block_job[blockIdx.x]];
   const DfJob& J = C.job;
+  const DfCamModel M = cams[C.cam];
   const int block = blockIdx.x - J.first_block;
   const int i = block * 256 + threadIdx.x;
   int st = SVO_HIP_SEED_ERASED;
   if (i < J.n) {
     const SeedRec rc = recs[(size_t)blockIdx.x * 256 + threadIdx.x];
-    st = df_finalize_seed(fr.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, fr.px_error_angle, fr.conv_thresh, i, rc, J.f, J.a, J.b, J.mu,
+    st = df_finalize_seed(M.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, M.px_error_angle, fr.conv_thresh, i, rc, J.f, J.a, J.b, J.mu,
                           J.z_range, J.sigma2, J.status, nullptr, J.xyz, nullptr, nullptr, J.px_cur, nullptr);
   }
   df_finalize_events(st, i, J.n, block, J.alive, C.report_updated, J.block_count, J.hist);
@@ -329,6 +336,7 @@ __global__ __launch_bounds__(256) void ev_scatter_jobs_kernel(const DfCamJob* __
 // the small pass (df_small_pass_kernel): 16 of these workgroups per 256-record block, a wave takes its four seeds through all
 // four stages; a workgroup wholly behind its job's last seed has nothing to do
 __global__ __launch_bounds__(256) void df_small_pass_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
+                                                                 const DfCamModel* __restrict__ cams,
                                                                  const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes,
                                                                  const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes,
                                                                  SeedRec* __restrict__ recs, uint32_t* __restrict__ pwb_t,
@@ -340,14 +348,15 @@ __global__ __launch_bounds__(256) void df_small_pass_jobs_kernel(DfFrame fr, con
   const DfJob& J = C.job;
   const int n_end = J.first_block * 256 + J.n;             // the end of the job's records
   if (r0 >= n_end) return;                                 // wave-uniform; no block-level barrier below
+  const DfCamModel M = cams[C.cam];
   const uint8_t* cur_pyr = cur_base + (size_t)C.cur_slot * cur_pyr_bytes;
   const int i0 = r0 - J.first_block * 256;                 // the wave's first seed within its batch
   // ---- geometry
-  if (lane < SEEDS_PER_WAVE) df_geometry_job_seed(fr, J, i0 + lane, (size_t)r0 + lane, recs, level_cat);
+  if (lane < SEEDS_PER_WAVE) df_geometry_job_seed(fr, M.cam, J, i0 + lane, (size_t)r0 + lane, recs, level_cat);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // ---- warp + epipolar search
-  df_search_block(fr, ref_base, ref_pyr_bytes, cur_pyr, n_end, level_cat, recs, pwb_t, n_pad, blockIdx.x);
+  df_search_block(fr, M.cam, ref_base, ref_pyr_bytes, cur_pyr, n_end, level_cat, recs, pwb_t, n_pad, blockIdx.x);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // ---- align2D
@@ -360,7 +369,7 @@ __global__ __launch_bounds__(256) void df_small_pass_jobs_kernel(DfFrame fr, con
   // ---- triangulation, computeTau, updateSeed
   if (lane < SEEDS_PER_WAVE && i0 + lane < J.n) {
     const SeedRec rc = recs[(size_t)r0 + lane];
-    (void)df_finalize_seed(fr.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, fr.px_error_angle, fr.conv_thresh, i0 + lane, rc, J.f, J.a, J.b,
+    (void)df_finalize_seed(M.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, M.px_error_angle, fr.conv_thresh, i0 + lane, rc, J.f, J.a, J.b,
                            J.mu, J.z_range, J.sigma2, J.status, nullptr, J.xyz, nullptr, nullptr, J.px_cur, nullptr);
   }
 }

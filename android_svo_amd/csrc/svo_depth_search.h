@@ -96,7 +96,8 @@ SVO_DEV int zmssd_8x8_win(const uint8_t* row0, int ox, const uint32_t* patch_wor
 //   C  the four seeds at once, 16 lanes each: align2D / align1D (lane = 4 pixels of the 8x8 patch)
 // (the body: workgroup `block` of 256 threads, seeds [16 * block, 16 * block + 16); no block-level barrier inside -- every wave
 // works on its own four seeds)
-SVO_DEV void df_search_block(const DfFrame& fr, const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes,
+// (`cam_of_block`: the camera model of the block's records -- fr.cam, or the model of the block's camera where a pass has several)
+SVO_DEV void df_search_block(const DfFrame& fr, const Cam& cam_of_block, const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes,
                              const uint8_t* __restrict__ cur_pyr, int n, const int32_t* __restrict__ level,
                              SeedRec* __restrict__ recs, uint32_t* __restrict__ pwb_t, int n_pad, int block) {
   __shared__ __attribute__((aligned(16))) uint8_t s_pwb[SEEDS_PER_BLOCK][112];
@@ -108,7 +109,7 @@ SVO_DEV void df_search_block(const DfFrame& fr, const uint8_t* __restrict__ ref_
   const int lane = threadIdx.x & 63;
   const int i0 = (block * 4 + wib) * SEEDS_PER_WAVE;
   if (i0 >= n) return;                     // wave-uniform; no block-level barrier is used below
-  const Cam cam = fr.cam;
+  const Cam cam = cam_of_block;
   // the wave's four records (384 contiguous bytes) and levels go to LDS in one round trip: every phase below reads
   // its per-seed parameters from there instead of paying a memory latency per dependent field access
   __shared__ __attribute__((aligned(16))) SeedRec s_rec[SEEDS_PER_BLOCK];
@@ -393,7 +394,7 @@ SVO_DEV void df_search_block(const DfFrame& fr, const uint8_t* __restrict__ ref_
 __global__ __launch_bounds__(256, 7) void df_search_kernel(
     DfFrame fr, const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes, const uint8_t* __restrict__ cur_pyr, int n,
     const int32_t* __restrict__ level, SeedRec* __restrict__ recs, uint32_t* __restrict__ pwb_t, int n_pad) {
-  df_search_block(fr, ref_base, ref_pyr_bytes, cur_pyr, n, level, recs, pwb_t, n_pad, blockIdx.x);
+  df_search_block(fr, fr.cam, ref_base, ref_pyr_bytes, cur_pyr, n, level, recs, pwb_t, n_pad, blockIdx.x);
 }
 
 // ---- the warp / search and alignment stages over the candidates of the cameras of a tracker (svo_track.hip; a lone tracker
@@ -407,18 +408,18 @@ __global__ __launch_bounds__(256, 7) void df_search_cams_kernel(
   const int c = (int)(((long long)blockIdx.x * SEEDS_PER_BLOCK) / cap);
   int n_c = counters[(size_t)c * counter_stride];
   n_c = n_c < cap ? n_c : cap;
-  df_search_block(fr, ref_base, ref_pyr_bytes, cur_base + (size_t)c * cur_pyr_bytes, c * cap + n_c, level, recs, pwb_t, n_pad, blockIdx.x);
+  df_search_block(fr, fr.cam, ref_base, ref_pyr_bytes, cur_base + (size_t)c * cur_pyr_bytes, c * cap + n_c, level, recs, pwb_t, n_pad, blockIdx.x);
 }
 
 // ---- the warp / search stage over the batches of several cameras (svo_hip_seed_batch_update_cameras_async): the 16 records of a
 // block lie inside ONE job of the device-resident table (job boundaries are multiples of 256 records); the job names the slot
-// of its camera's current image and the end of its records.
+// of its camera's current image, the end of its records and its camera's model in the pass's camera table.
 __global__ __launch_bounds__(256, 7) void df_search_jobs_kernel(
-    DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job, const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes,
-    const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes, const int32_t* __restrict__ level, SeedRec* __restrict__ recs,
-    uint32_t* __restrict__ pwb_t, int n_pad) {
+    DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job, const DfCamModel* __restrict__ cams,
+    const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes, const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes,
+    const int32_t* __restrict__ level, SeedRec* __restrict__ recs, uint32_t* __restrict__ pwb_t, int n_pad) {
   const DfCamJob& C = jobs[block_job[blockIdx.x / (256 / SEEDS_PER_BLOCK)]];
-  df_search_block(fr, ref_base, ref_pyr_bytes, cur_base + (size_t)C.cur_slot * cur_pyr_bytes, C.job.first_block * 256 + C.job.n, level, recs, pwb_t,
+  df_search_block(fr, cams[C.cam].cam, ref_base, ref_pyr_bytes, cur_base + (size_t)C.cur_slot * cur_pyr_bytes, C.job.first_block * 256 + C.job.n, level, recs, pwb_t,
                   n_pad, blockIdx.x);
 }
 }  // namespace

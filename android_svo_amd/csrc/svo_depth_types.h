@@ -94,11 +94,21 @@ static_assert(offsetof(DfJob, T) == 0 && offsetof(DfJob, px) == sizeof(DfPoses) 
 // block of the pass to its job.  A job is a DfJob plus what a DfGroup holds once for all its jobs and a pass holds once for all
 // its batches: whether the job's camera reports its updated seeds, and the slot of its camera's current image.  Job
 // boundaries are multiples of 256 records, so a 16-record search block or a 16-patch align block lies inside one job too.
+// The cameras of the pass may each have their own model (svo_hip_seed_batch_update_rig_async; the image size is common): a table
+// of them lies behind the block map, and a job names its camera's entry.  What a pass derives from the camera model travels
+// with it, so the kernels read `cam` and `px_error_angle` of their job's entry where the other passes read them from the
+// DfFrame; the entry is block-uniform like the job.
 struct DfCamJob {
   DfJob job;
   int cur_slot, report_updated;
+  int cam, pad_;             // entry of the pass's camera table
 };
-static_assert(sizeof(DfCamJob) == sizeof(DfJob) + 8 && sizeof(DfCamJob) % 8 == 0, "DfCamJob layout");
+struct DfCamModel {
+  Cam cam;
+  double px_error_angle;     // 2 atan(1 / (2 |fx|))   (depth_filter.cpp:245-247)
+};
+static_assert(sizeof(DfCamJob) == sizeof(DfJob) + 16 && sizeof(DfCamJob) % 8 == 0, "DfCamJob layout");
+static_assert(sizeof(DfCamModel) == sizeof(Cam) + 8 && sizeof(DfCamModel) % 8 == 0, "DfCamModel layout");
 
 constexpr int DF_SMALL_MAX = 16384;                      // upper limit of svo_hip_df_set_small_pass_limit
 

@@ -331,10 +331,12 @@ int svo_match_stages_cams(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const sv
                           int cap, const int* counters_dev, int counter_stride, const int32_t* level_ref_dev, svo_dev::SeedRec* recs,
                           uint32_t* pwb_t, int n_pad, int n_pyr_levels, int align_max_iter, bool edgelets);
 // svo_refine.hip: the pose refinement of a batch whose counts / poses lie n_feat_stride ints / T_stride doubles apart
-// (svo_hip_pose_optimize_batch_dev: 1 and 7)
+// (svo_hip_pose_optimize_batch_dev: 1 and 7).  error_multiplier2_dev: optional, frame b's error multiplier (|fx| of its
+// camera) at [b * error_multiplier2_stride] in device memory; NULL: `error_multiplier2` for every frame.
 int svo_pose_optimize_batch_strided(svo_hip_ctx* ctx, int batch, int max_n, const int32_t* n_feat_dev, int n_feat_stride,
                                     const double* T_f_w_dev, int T_stride, const double* f_dev, const double* pos_dev,
                                     const int32_t* level_dev, uint8_t* has_point_dev, double error_multiplier2,
+                                    const double* error_multiplier2_dev, int error_multiplier2_stride,
                                     double reproj_thresh, int n_iter, svo_hip_pose_opt_result* results_dev);
 
 // ---- multi-GPU exchange (svo_comm.hip): RCCL over xGMI, or a host-staged shared-memory transport for bring-up / tests.

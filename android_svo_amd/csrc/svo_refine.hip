@@ -230,11 +230,15 @@ __device__ __constant__ double kExpSeries[32] = {
 // large update angles (theta^2 > 0.25): the library path of SE3::exp
 __device__ __noinline__ void se3_exp_cold(const double* l, double* out) { se3_exp(l, out); }
 
+// EM_PER_FRAME: frame b's error multiplier is em_dev[b * em_stride] (the cameras of a rig each have their own |fx|); else
+// `em_all` for every frame, and the kernel is the one it was.
+template <bool EM_PER_FRAME>
 __global__ __launch_bounds__(PR_THREADS) void pose_refine_kernel(
     int max_n, const int* __restrict__ n_feat, const double* __restrict__ T_in, const double* __restrict__ f,
-    const double* __restrict__ pos, const int* __restrict__ level, uint8_t* __restrict__ has_point, double em,
+    const double* __restrict__ pos, const int* __restrict__ level, uint8_t* __restrict__ has_point, double em_all,
     double reproj_thresh, int n_iter, float* __restrict__ err_ws, double* __restrict__ sq_init_ws,
-    double* __restrict__ sq_final_ws, PoseOptOut* __restrict__ out, int n_feat_stride, int T_stride) {
+    double* __restrict__ sq_final_ws, PoseOptOut* __restrict__ out, int n_feat_stride, int T_stride,
+    const double* __restrict__ em_dev, int em_stride) {
   __shared__ int hist[256];
   __shared__ __attribute__((aligned(16))) unsigned long long s_keys[2][PR_THREADS];
   __shared__ unsigned s_cnt[4][PR_THREADS];
@@ -251,6 +255,7 @@ __global__ __launch_bounds__(PR_THREADS) void pose_refine_kernel(
   __shared__ unsigned s_count;
 
   const int b = blockIdx.x;
+  const double em = EM_PER_FRAME ? em_dev[(size_t)b * em_stride] : em_all;
   const int n = n_feat[(size_t)b * n_feat_stride];      // (strides: a tracker group reads the counts / poses where its other kernels left them)
   const size_t base = (size_t)b * max_n;
   const double* fb = f + 3 * base;
@@ -569,11 +574,12 @@ __global__ void ldlt6_batch_kernel(int n, const double* __restrict__ H, const do
 int svo_pose_optimize_batch_strided(svo_hip_ctx* ctx, int batch, int max_n, const int32_t* n_feat_dev, int n_feat_stride,
                                     const double* T_f_w_dev, int T_stride, const double* f_dev, const double* pos_dev,
                                     const int32_t* level_dev, uint8_t* has_point_dev, double error_multiplier2,
+                                    const double* error_multiplier2_dev, int error_multiplier2_stride,
                                     double reproj_thresh, int n_iter, svo_hip_pose_opt_result* results_dev) {
   if (!ctx) return SVO_HIP_ERR_INVALID;
   SVO_REQUIRE(ctx, batch > 0 && max_n > 0 && n_iter >= 0 && n_feat_stride >= 1 && T_stride >= 7);
   SVO_REQUIRE(ctx, n_feat_dev && T_f_w_dev && f_dev && pos_dev && level_dev && has_point_dev && results_dev);
-  SVO_REQUIRE(ctx, error_multiplier2 > 0.0);
+  SVO_REQUIRE(ctx, error_multiplier2_dev ? error_multiplier2_stride >= 1 : error_multiplier2 > 0.0);
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
   const size_t per = (size_t)batch * max_n;
   void* ws = nullptr;
@@ -582,9 +588,10 @@ int svo_pose_optimize_batch_strided(svo_hip_ctx* ctx, int batch, int max_n, cons
   double* sq_init = reinterpret_cast<double*>(ws);
   double* sq_final = sq_init + per;
   float* err = reinterpret_cast<float*>(sq_final + per);
-  hipLaunchKernelGGL(pose_refine_kernel, dim3(batch), dim3(PR_THREADS), 0, ctx->stream, max_n, n_feat_dev, T_f_w_dev, f_dev,
+  auto* kernel = error_multiplier2_dev ? pose_refine_kernel<true> : pose_refine_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(batch), dim3(PR_THREADS), 0, ctx->stream, max_n, n_feat_dev, T_f_w_dev, f_dev,
                      pos_dev, level_dev, has_point_dev, error_multiplier2, reproj_thresh, n_iter, err, sq_init, sq_final,
-                     reinterpret_cast<PoseOptOut*>(results_dev), n_feat_stride, T_stride);
+                     reinterpret_cast<PoseOptOut*>(results_dev), n_feat_stride, T_stride, error_multiplier2_dev, error_multiplier2_stride);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   return SVO_HIP_OK;
 }
@@ -597,7 +604,7 @@ int svo_hip_pose_optimize_batch_dev(svo_hip_ctx* ctx, int batch, int max_n, cons
                                     const int32_t* level_dev, uint8_t* has_point_dev, double error_multiplier2,
                                     double reproj_thresh, int n_iter, svo_hip_pose_opt_result* results_dev) {
   return svo_pose_optimize_batch_strided(ctx, batch, max_n, n_feat_dev, 1, T_f_w_dev, 7, f_dev, pos_dev, level_dev, has_point_dev,
-                                         error_multiplier2, reproj_thresh, n_iter, results_dev);
+                                         error_multiplier2, nullptr, 0, reproj_thresh, n_iter, results_dev);
 }
 
 int svo_hip_pose_optimize(svo_hip_ctx* ctx, int n, const double T_f_w[7], const double* f, const double* pos,

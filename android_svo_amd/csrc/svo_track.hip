@@ -103,6 +103,7 @@ struct svo_hip_tracker_shared {
   int* ft_level = nullptr;                  // [n_cams][NF]
   uint8_t* ft_has_point = nullptr;          // [n_cams][NF]
   svo_hip_pose_opt_result* po = nullptr;    // [n_cams]
+  double* err_mult = nullptr;               // [n_cams] |fx| of every camera: the pose refinement's error multiplier (groups only)
   // the argument table of the chain's kernels (TrkCamArgs per camera): built on the host every call, uploaded when it changed
   std::vector<TrkCamArgs> args_next;
   TrkCamArgs* args_host = nullptr;          // page-locked: the bytes of the last upload
@@ -375,7 +376,7 @@ static int trk_check_config(svo_hip_ctx* ctx, const svo_hip_camera* cam, const s
   return SVO_HIP_OK;
 }
 
-// the shared part of n_cams cameras with one camera model and one configuration
+// the shared part of n_cams cameras with one image size (`cam`: any of them) and one configuration
 static int trk_shared_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const svo_hip_tracker_config* cfg, int n_cams, svo_hip_tracker_shared** out) {
   *out = nullptr;
   svo_hip_tracker_shared* sh = new (std::nothrow) svo_hip_tracker_shared();
@@ -654,14 +655,14 @@ static int trk_args_table(svo_hip_tracker_shared* sh, SeedRec* recs) {
   const int stride = sh->rec_stride;
   MdFrame mf;
   memset(&mf, 0, sizeof(mf));
-  mf.cam = svo_make_cam(t0->cam); mf.n_pyr_levels = c.n_pyr_levels; mf.n_kf = c.max_keyframes; mf.n_ref_levels = c.n_levels;
+  mf.n_pyr_levels = c.n_pyr_levels; mf.n_kf = c.max_keyframes; mf.n_ref_levels = c.n_levels;
   TrkCamArgs* an = sh->args_next.data();
   memset(an, 0, (size_t)N * sizeof(TrkCamArgs));
   for (int k = 0; k < N; ++k) {
     svo_hip_tracker* t = sh->members[(size_t)k];
     TrkCamArgs& a = an[k];
     a.m = make_map(t); a.pl = t->pl; a.ft = t->ft; a.last = t->last;
-    a.mf = mf; a.mf.slot_base = k * c.max_keyframes;
+    a.mf = mf; a.mf.cam = svo_make_cam(t->cam); a.mf.slot_base = k * c.max_keyframes;
     a.T_slot_w = t->T_slot_w;
     a.recs = recs + (size_t)k * stride;
     a.sia_state = svo_sia_state_dev(sh->sia, k);
@@ -739,7 +740,7 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
   if (N == 1) hipLaunchKernelGGL(trk_plan_one_kernel, dim3(1), dim3(TRK_THREADS), 0, ctx->stream, an[0]);
   else hipLaunchKernelGGL(trk_plan_cams_kernel, dim3(N), dim3(TRK_THREADS), 0, ctx->stream, ad);
   SVO_CHECK_HIP(ctx, hipGetLastError());
-  // warp + align2D (+ align1D when a map holds edgelets) over every camera's candidates
+  // warp + align2D (+ align1D when a map holds edgelets) over every camera's candidates (these stages read the image size only)
   rc = svo_match_stages_cams(ctx, sh->kf_pyr, cur, &t0->cam, N, stride, sh->counters, 8, sh->cand_level_ref, recs, pwb_t, n_pad, c.n_pyr_levels,
                              c.align_max_iter, any_edgelet);
   if (rc != SVO_HIP_OK) return rc;
@@ -750,8 +751,8 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
   const FrameState* st0 = svo_sia_state_dev(sh->sia, 0);
   static_assert(sizeof(FrameState) % sizeof(double) == 0, "the solver records are a whole number of doubles apart");
   rc = svo_pose_optimize_batch_strided(ctx, N, c.max_frame_features, sh->counters + 5, 8, st0->T_cur_w, (int)(sizeof(FrameState) / sizeof(double)),
-                                       sh->ft_f, sh->ft_pos, sh->ft_level, sh->ft_has_point, fabs(t0->cam.fx), c.pose_optim_thresh,
-                                       c.pose_optim_num_iter, sh->po);
+                                       sh->ft_f, sh->ft_pos, sh->ft_level, sh->ft_has_point, fabs(t0->cam.fx), sh->err_mult, 1,
+                                       c.pose_optim_thresh, c.pose_optim_num_iter, sh->po);
   if (rc != SVO_HIP_OK) return rc;
   // ---- hand-over + result: written straight into the page-locked blocks, the frame's sequence number last
   const unsigned long long seq = ++sh->seq;
@@ -785,34 +786,61 @@ int svo_hip_tracker_track(svo_hip_tracker* t, const uint8_t* level0, svo_hip_tra
   return SVO_HIP_OK;
 }
 
-// ---- a group of cameras: N trackers with one camera model and one configuration whose frames are tracked TOGETHER -- one
-// chain of launches per call whatever N (every kernel of the chain takes one workgroup, or one slice of its grid, per camera).
+// ---- a group of cameras: N trackers with one image size and one configuration, each with its own camera model, whose frames
+// are tracked TOGETHER -- one chain of launches per call whatever N (every kernel of the chain takes one workgroup, or one slice
+// of its grid, per camera, and reads the camera model of its entry of the argument table).
 // Every camera keeps its own map, last frame and result block and is set up with the svo_hip_tracker_* functions of its
 // handle (svo_hip_tracker_group_camera); only the per-frame call is the group's.
 struct svo_hip_tracker_group {
   svo_hip_tracker_shared* sh = nullptr;
 };
 
-int svo_hip_tracker_group_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const svo_hip_tracker_config* cfg, int n_cameras,
-                                 svo_hip_tracker_group** out) {
-  if (!ctx || !cam || !cfg || !out) return SVO_HIP_ERR_INVALID;
+// camera k's model is cams[k * cam_stride]: stride 1 for a rig, 0 for the one model svo_hip_tracker_group_create repeats
+static int trk_group_create(svo_hip_ctx* ctx, const svo_hip_camera* cams, int cam_stride, const svo_hip_tracker_config* cfg, int n_cameras,
+                            svo_hip_tracker_group** out) {
+  if (!ctx || !cfg || !out) return SVO_HIP_ERR_INVALID;
   *out = nullptr;
+  // every refusal comes before the first allocation
+  SVO_REQUIRE(ctx, cams != nullptr);
   SVO_REQUIRE(ctx, n_cameras >= 1 && n_cameras <= 1024);
-  int rc = trk_check_config(ctx, cam, cfg);
-  if (rc != SVO_HIP_OK) return rc;
+  for (int k = 0; k < (cam_stride ? n_cameras : 1); ++k) {
+    const int rc = trk_check_config(ctx, &cams[k], cfg);
+    if (rc != SVO_HIP_OK) return rc;
+    // the pyramid batches, the detector grid and the page-locked image blocks are shared and sized once
+    SVO_REQUIRE(ctx, cams[k].width == cams[0].width && cams[k].height == cams[0].height);
+  }
   // a block of the batched warp / alignment stages takes 16 candidates and must not straddle two cameras
   SVO_REQUIRE(ctx, n_cameras == 1 || cfg->max_items % 16 == 0);
   svo_hip_tracker_group* g = new (std::nothrow) svo_hip_tracker_group();
   if (!g) return SVO_HIP_ERR_NOMEM;
-  rc = trk_shared_create(ctx, cam, cfg, n_cameras, &g->sh);
+  int rc = trk_shared_create(ctx, &cams[0], cfg, n_cameras, &g->sh);
   for (int k = 0; k < n_cameras && rc == SVO_HIP_OK; ++k) {
     svo_hip_tracker* t = nullptr;
-    rc = trk_member_create(g->sh, k, cam, cfg, &t);
+    rc = trk_member_create(g->sh, k, &cams[(size_t)k * cam_stride], cfg, &t);
     if (rc == SVO_HIP_OK) g->sh->members.push_back(t);
+  }
+  if (rc == SVO_HIP_OK && n_cameras > 1) {                 // (a group of one runs the lone tracker's chain: the scalar |fx|)
+    std::vector<double> em((size_t)n_cameras);
+    for (int k = 0; k < n_cameras; ++k) em[(size_t)k] = fabs(cams[(size_t)k * cam_stride].fx);
+    trk_alloc(ctx, &g->sh->dev_allocs, &rc, &g->sh->err_mult, (size_t)n_cameras);
+    if (rc == SVO_HIP_OK && (hipMemcpyAsync(g->sh->err_mult, em.data(), em.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+                             hipStreamSynchronize(ctx->stream) != hipSuccess))
+      rc = svo_fail(ctx, SVO_HIP_ERR_DEVICE, "svo_hip_tracker_group_create", "upload of the cameras' error multipliers failed");
   }
   if (rc != SVO_HIP_OK) { svo_hip_tracker_group_destroy(g); return rc; }
   *out = g;
   return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_group_create_rig(svo_hip_ctx* ctx, const svo_hip_camera* cams, const svo_hip_tracker_config* cfg, int n_cameras,
+                                     svo_hip_tracker_group** out) {
+  return trk_group_create(ctx, cams, 1, cfg, n_cameras, out);
+}
+
+// one camera model for all cameras: the rig with that model repeated
+int svo_hip_tracker_group_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const svo_hip_tracker_config* cfg, int n_cameras,
+                                 svo_hip_tracker_group** out) {
+  return trk_group_create(ctx, cam, 0, cfg, n_cameras, out);
 }
 
 int svo_hip_tracker_group_destroy(svo_hip_tracker_group* g) {

@@ -666,14 +666,22 @@ class ResidentSeeds:
                                                                 1 if report_updated else 0), "seed_batch_update_group_async")
 
     @staticmethod
-    def update_cameras_async(passes, ref: Pyramid, cur: Pyramid, cam, prm=None, ctx: Optional[Context] = None):
+    def update_cameras_async(passes, ref: Pyramid, cur: Pyramid, cam_or_cams, prm=None, ctx: Optional[Context] = None):
         """svo_hip_seed_batch_update_cameras_async: the batches of SEVERAL cameras as ONE set of launches.  `passes`: per camera
         (batches, ref_slots, T_ref_w [n][7], cur_slot, T_cur_w, report_updated); a camera without batches sits the pass out.
-        Collect every batch afterwards.  `ctx` is only needed when no camera has a batch."""
+        Collect every batch afterwards.  `ctx` is only needed when no camera has a batch.
+        `cam_or_cams`: one camera model for all cameras, or a sequence of len(passes) models, cams[c] the model of passes[c]'s
+        camera (svo_hip_seed_batch_update_rig_async; the image size is common to all)."""
         if ctx is None:
             ctx = next(b.ctx for p in passes for b in p[0])
         prm = prm or depth_filter_params()
-        c = make_camera(cam)
+        rig = isinstance(cam_or_cams, (list, tuple))
+        if rig:
+            if len(cam_or_cams) != len(passes):
+                raise ValueError("a rig pass takes one camera model per pass: %d models, %d passes" % (len(cam_or_cams), len(passes)))
+            c = (CCamera * max(len(passes), 1))(*[make_camera(m) for m in cam_or_cams])
+        else:
+            c = make_camera(cam_or_cams)
         arr = (CSeedCameraPass * max(len(passes), 1))()
         keep = []
         for i, (batches, ref_slots, T_ref_w, cur_slot, T_cur_w, report_updated) in enumerate(passes):
@@ -689,8 +697,12 @@ class ResidentSeeds:
             arr[i].cur_slot = int(cur_slot)
             arr[i].T_cur_w[:] = [float(v) for v in np.asarray(T_cur_w, dtype=np.float64).reshape(7)]
             arr[i].report_updated = 1 if report_updated else 0
-        ctx.check(ctx.lib.svo_hip_seed_batch_update_cameras_async(ctx.h, len(passes), arr, ref.h, cur.h, C.byref(c), C.byref(prm)),
-                  "seed_batch_update_cameras_async")
+        if rig:
+            ctx.check(ctx.lib.svo_hip_seed_batch_update_rig_async(ctx.h, len(passes), arr, ref.h, cur.h, c, C.byref(prm)),
+                      "seed_batch_update_rig_async")
+        else:
+            ctx.check(ctx.lib.svo_hip_seed_batch_update_cameras_async(ctx.h, len(passes), arr, ref.h, cur.h, C.byref(c), C.byref(prm)),
+                      "seed_batch_update_cameras_async")
 
     def pending(self) -> bool:
         return bool(self.ctx.lib.svo_hip_seed_batch_pending(self.h))
@@ -1351,11 +1363,18 @@ class Tracker:
 
 
 class TrackerGroup:
-    """svo_hip_tracker_group: n cameras (one camera model, one configuration) tracked together, one chain of launches per call.
+    """svo_hip_tracker_group: n cameras (one image size, one configuration) tracked together, one chain of launches per call.
     `cameras[c]` is a Tracker bound to camera c's handle: set_map / set_last_frame / upload_keyframe / optimize_structure /
-    image_buffer / last_result work on it; track() and destroy() are the group's."""
+    image_buffer / last_result work on it; track() and destroy() are the group's.
+    `cam_or_cams`: one camera model for all cameras, or a sequence of n_cameras models (a rig, svo_hip_tracker_group_create_rig):
+    cameras[c].cam is camera c's."""
 
-    def __init__(self, ctx: Context, cam, n_cameras: int, **overrides):
+    def __init__(self, ctx: Context, cam_or_cams, n_cameras: int, **overrides):
+        rig = isinstance(cam_or_cams, (list, tuple))
+        if rig and len(cam_or_cams) != int(n_cameras):
+            raise ValueError("a rig takes one camera model per camera: %d models, %d cameras" % (len(cam_or_cams), int(n_cameras)))
+        cams = list(cam_or_cams) if rig else [cam_or_cams] * int(n_cameras)
+        cam = cams[0]                          # (the image size is common to all)
         self.ctx, self.cam, self.n = ctx, cam, int(n_cameras)
         self.cfg = CTrackerConfig()
         ctx.check(ctx.lib.svo_hip_tracker_default_config(C.byref(self.cfg)), "tracker_default_config")
@@ -1364,12 +1383,16 @@ class TrackerGroup:
             setattr(self.cfg, k, v)
         self.ccam = make_camera(cam)
         self.h = C.c_void_p()
-        ctx.check(ctx.lib.svo_hip_tracker_group_create(ctx.h, C.byref(self.ccam), C.byref(self.cfg), self.n, C.byref(self.h)), "tracker_group_create")
+        if rig:
+            ccams = (CCamera * self.n)(*[make_camera(m) for m in cams])
+            ctx.check(ctx.lib.svo_hip_tracker_group_create_rig(ctx.h, ccams, C.byref(self.cfg), self.n, C.byref(self.h)), "tracker_group_create_rig")
+        else:
+            ctx.check(ctx.lib.svo_hip_tracker_group_create(ctx.h, C.byref(self.ccam), C.byref(self.cfg), self.n, C.byref(self.h)), "tracker_group_create")
         self.cameras = []
         for c in range(self.n):
             th = C.c_void_p()
             ctx.check(ctx.lib.svo_hip_tracker_group_camera(self.h, c, C.byref(th)), "tracker_group_camera")
-            self.cameras.append(Tracker(ctx, cam, _group_handle=th, _cfg=self.cfg))
+            self.cameras.append(Tracker(ctx, cams[c], _group_handle=th, _cfg=self.cfg))
         self._ptrs = (C.POINTER(C.c_uint8) * self.n)()
         self._res = (CTrackResult * self.n)()
 

@@ -7,10 +7,14 @@
 //        svo_host_demo <case_dir> <out_dir> trackgroup [n]   the same tracking chain for n (default 2) copies of the world at once through
 //                                                   svo::FrameTrackerGroup (hip_bridge::FrameTrackerGroupT, svo_hip_tracker_group): outputs of
 //                                                   world w under <out_dir>/g<w>/, each equal to the lone tracker's
+//        svo_host_demo <case_dir> <out_dir> trackgroup n rig   a camera rig: world w is the case <case_dir>/cam<w> with a camera model of its
+//                                                   own (track_manifest.bin, optional track_dist.bin: k1 k2 p1 p2 k3); outputs under
+//                                                   <out_dir>/g<w>/, each equal to `track` on <case_dir>/cam<w>
 //        svo_host_demo <case_dir> <out_dir> keyframes [device_seeds] [threaded]   keyframes whose seeds the filter detects and creates
 //                                                   on the device, or (without device_seeds) are detected by the caller and handed in
 //        svo_host_demo <case_dir> <out_dir> filtergroup   svo::DepthFilterGroup: the depth filters of n cameras as one device pass per
-//                                                   step, and a lone DepthFilter per camera over the same frames (filter_group_demo)
+//                                                   step, and a lone DepthFilter per camera over the same frames (filter_group_demo);
+//                                                   `filtergroup rig`: every camera with the model of <case_dir>/cam<c>/camera.bin
 //        svo_host_demo <case_dir> <out_dir> churn   SURVEY 8(b) "Threading": latency of SparseImgAlign::run on the tracking
 //                                                   thread while a second thread (own context) creates seed batches, runs a
 //                                                   pass and drops them at keyframe rate -- and with that thread idle
@@ -149,10 +153,21 @@ static svo_hip_tracker_config track_config(const std::vector<double>& m, int max
 // hold the positions the call wrote.  track_decision.bin, 13 doubles per frame: the device's have_depth, depth_mean, depth_min,
 // overlap_valid, need_new_kf, furthest keyframe (in order of creation, -1: none), the host's six, and the device decisions so far.
 // With max_kfs the keyframe that leaves is the one the device named; the run throws if the host names another.
+// the camera of a tracking case: the manifest's size and intrinsics, and the radtan coefficients of track_dist.bin where the case has one
+static PinholeCamera track_camera(const std::string& dir, const std::vector<double>& m) {
+  PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
+  struct stat st;
+  if (::stat((dir + "/track_dist.bin").c_str(), &st) == 0) {
+    const std::vector<double> d = read_bin<double>(dir + "/track_dist.bin");
+    for (size_t k = 0; k < 5 && k < d.size(); ++k) cam.d[k] = d[k];
+  }
+  return cam;
+}
+
 static int track_demo(const std::string& dir, const std::string& out, TrackerPort& port, bool incremental = false, bool times = false,
                       int max_kfs = 0, bool full_remove = false, int kf_every = 0, bool compact = false, int new_seeds = 0, int reloc_at = -1) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
-  PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
+  PinholeCamera cam = track_camera(dir, m);
   const int n_kf = (int)m[6], n_points = (int)m[7], n_obs = (int)m[8], n_cand = (int)m[10], n_frames = (int)m[11];
   const auto kf_pose = read_bin<double>(dir + "/kf_pose.bin"), pt_pos = read_bin<double>(dir + "/pt_pos.bin");
   const auto pt_type = read_bin<int32_t>(dir + "/pt_type.bin"), pt_failed = read_bin<int32_t>(dir + "/pt_n_failed.bin"),
@@ -400,20 +415,25 @@ static int track_demo(const std::string& dir, const std::string& out, TrackerPor
 static int track_lone(const std::string& dir, const std::string& out, bool incremental, bool times, int max_kfs, bool full_remove, int kf_every,
                       int max_points, bool compact, int new_seeds, int reloc_at) {
   const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
-  PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
+  PinholeCamera cam = track_camera(dir, m);
   FrameTracker tracker(cam, track_config(m, max_kfs, max_points));
   TrackerPort port;
   port.lone = &tracker;
   return track_demo(dir, out, port, incremental, times, max_kfs, full_remove, kf_every, compact, new_seeds, reloc_at);
 }
 
-// n copies of the world, one svo::FrameTrackerGroup: every world's outputs must equal the lone tracker's
-static int track_group(const std::string& dir, const std::string& out, int n) {
-  const std::vector<double> m = read_bin<double>(dir + "/track_manifest.bin");
-  PinholeCamera cam{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
+// n copies of the world, one svo::FrameTrackerGroup: every world's outputs must equal the lone tracker's.  rig: n worlds of their
+// own (<dir>/cam<w>), every camera with its own model (one image size, one configuration: that of cam0's manifest)
+static int track_group(const std::string& dir, const std::string& out, int n, bool rig) {
+  auto world_dir = [&](int w) { return rig ? dir + "/cam" + std::to_string(w) : dir; };
+  const std::vector<double> m = read_bin<double>(world_dir(0) + "/track_manifest.bin");
+  std::vector<PinholeCamera> cams;
+  for (int w = 0; w < n; ++w) cams.push_back(track_camera(world_dir(w), read_bin<double>(world_dir(w) + "/track_manifest.bin")));
+  std::vector<const PinholeCamera*> cam_ptrs;
+  for (const PinholeCamera& c : cams) cam_ptrs.push_back(&c);
   svo_hip_tracker_config cfg = track_config(m);
   cfg.max_items = (cfg.max_items + 15) / 16 * 16;
-  FrameTrackerGroup group(cam, cfg, n);
+  FrameTrackerGroup group(cam_ptrs, cfg);
   if (!group.ok()) throw std::runtime_error("svo::FrameTrackerGroup: no device tracker group");
   GroupRendezvous rz;
   rz.group = &group; rz.n = (size_t)n;
@@ -427,7 +447,7 @@ static int track_group(const std::string& dir, const std::string& out, int n) {
       TrackerPort port;
       port.rz = &rz; port.baton = &baton; port.w = (size_t)w;
       try {
-        track_demo(dir, out + "/g" + std::to_string(w), port);
+        track_demo(world_dir(w), out + "/g" + std::to_string(w), port);
       } catch (const std::exception& e) {
         errors[(size_t)w] = e.what();
         rz.ok = false; ++rz.failed; ++rz.generation; rz.cv.notify_all();      // let the others go (they fail at their next frame)
@@ -435,7 +455,7 @@ static int track_group(const std::string& dir, const std::string& out, int n) {
     });
   for (std::thread& t : worlds) t.join();
   for (const std::string& e : errors) if (!e.empty()) throw std::runtime_error(e);
-  std::printf("svo_host_demo trackgroup OK (%d worlds)\n", n);
+  std::printf("svo_host_demo trackgroup OK (%d worlds%s)\n", n, rig ? ", a rig" : "");
   return 0;
 }
 
@@ -656,10 +676,19 @@ static int keyframes_demo(const std::string& dir, const std::string& out, bool d
 // seeds, as DepthFilter's thread does (depth_filter.cpp:191-229); the other cameras update with frame k.  Run twice: through the
 // group (one device pass per step for all cameras) and through one lone unthreaded DepthFilter per camera.  Per camera the
 // sequence of convergence callbacks, the final seeds and the detector grid go to <out_dir>/{group,lone}_cam<c>_*.bin.
-static int filter_group_demo(const std::string& dir, const std::string& out) {
+// rig: camera c's model is cam<c>/camera.bin (fx fy cx cy k1 k2 p1 p2 k3; the manifest's image size)
+static int filter_group_demo(const std::string& dir, const std::string& out, bool rig) {
   const std::vector<double> m = read_bin<double>(dir + "/manifest.bin");      // w h fx fy cx cy n_levels n_frames n_cameras
   PinholeCamera pc{(int)m[0], (int)m[1], m[2], m[3], m[4], m[5]};
   const int n_levels = (int)m[6], n_frames = (int)m[7], n_cams = (int)m[8];
+  std::vector<PinholeCamera> pcs((size_t)n_cams, pc);         // (the frames keep pointers into it)
+  for (int c = 0; c < n_cams && rig; ++c) {
+    const std::vector<double> k = read_bin<double>(dir + "/cam" + std::to_string(c) + "/camera.bin");
+    if (k.size() != 9) throw std::runtime_error("filtergroup rig: camera.bin holds fx fy cx cy and five distortion coefficients");
+    PinholeCamera& q = pcs[(size_t)c];
+    q.fx = k[0]; q.fy = k[1]; q.cx = k[2]; q.cy = k[3];
+    for (int i = 0; i < 5; ++i) q.d[i] = k[4 + (size_t)i];
+  }
   const auto dm = read_bin<double>(dir + "/depth_mean_min.bin");
   const auto opt = read_bin<double>(dir + "/options.bin");                    // Options: max_n_kfs, seed_convergence_sigma2_thresh
   struct SeedSet { std::vector<double> px, f; std::vector<int32_t> level; };
@@ -671,7 +700,7 @@ static int filter_group_demo(const std::string& dir, const std::string& out) {
   std::vector<Cam> cams((size_t)n_cams);
   for (int c = 0; c < n_cams; ++c) {
     const std::string cd = dir + "/cam" + std::to_string(c);
-    for (int k = 0; k < n_frames; ++k) cams[(size_t)c].frames.push_back(load_frame(cd, &pc, k, n_levels));
+    for (int k = 0; k < n_frames; ++k) cams[(size_t)c].frames.push_back(load_frame(cd, &pcs[(size_t)c], k, n_levels));
     for (double k : read_bin<double>(cd + "/keyframes.bin")) {
       const std::string kd = cd + "/kf" + std::to_string(cams[(size_t)c].keyframes.size());
       cams[(size_t)c].keyframes.push_back((int)k);
@@ -754,14 +783,14 @@ static int filter_group_demo(const std::string& dir, const std::string& out) {
     }
     dump(side, df.getSeeds(), "lone_cam" + std::to_string(c));
   }
-  std::printf("svo_host_demo filtergroup OK\n");
+  std::printf("svo_host_demo filtergroup OK%s\n", rig ? " (a rig)" : "");
   return 0;
 }
 
 int main(int argc, char** argv) {
   if (argc > 3 && std::string(argv[3]) == "filtergroup") {
     try {
-      return filter_group_demo(argv[1], argv[2]);
+      return filter_group_demo(argv[1], argv[2], argc > 4 && std::string(argv[4]) == "rig");
     } catch (const std::exception& e) {
       std::fprintf(stderr, "svo_host_demo FAILED: %s\n", e.what());
       return 1;
@@ -780,11 +809,11 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n|filtergroup|churn|keyframes [device_seeds] [threaded]]\n", argv[0]); return 2; }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n [rig]|filtergroup [rig]|churn|keyframes [device_seeds] [threaded]]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {
-      return track_group(dir, out, argc > 4 ? std::atoi(argv[4]) : 2);
+      return track_group(dir, out, argc > 4 ? std::atoi(argv[4]) : 2, argc > 5 && std::string(argv[5]) == "rig");
     } catch (const std::exception& e) {
       std::fprintf(stderr, "svo_host_demo FAILED: %s\n", e.what());
       return 1;

@@ -464,6 +464,16 @@ class FrameTrackerGroup : public hip_bridge::FrameTrackerGroupT<HostTrackerPolic
  public:
   FrameTrackerGroup(const PinholeCamera& cam, const svo_hip_tracker_config& cfg, int n_cameras)
       : hip_bridge::FrameTrackerGroupT<HostTrackerPolicy>(cam.toC(), cfg, n_cameras) {}
+  /// a rig: camera c tracks with cams[c] (one image size; a device group of per-camera models when they differ)
+  FrameTrackerGroup(const std::vector<const PinholeCamera*>& cams, const svo_hip_tracker_config& cfg)
+      : hip_bridge::FrameTrackerGroupT<HostTrackerPolicy>(toC(cams), cfg) {}
+
+ private:
+  static std::vector<svo_hip_camera> toC(const std::vector<const PinholeCamera*>& cams) {
+    std::vector<svo_hip_camera> out;
+    for (const PinholeCamera* c : cams) out.push_back(c->toC());
+    return out;
+  }
 };
 
 /// I/sparse_img_align.h:33-79
@@ -876,10 +886,12 @@ class DepthFilter {
   std::unique_ptr<hip_bridge::PyramidCache> kf_pyr_, cur_pyr_;
 };
 
-/// The depth filters of N cameras with one camera model on ONE context, unthreaded: the counterpart of FrameTrackerGroup.  One
+/// The depth filters of N cameras (one image size, every camera with the model of its frames) on ONE context, unthreaded: the
+/// counterpart of FrameTrackerGroup.  One
 /// keyframe PyramidCache and one current-frame cache are shared by the cameras; every camera has its own seed list, device mirror,
 /// convergence callback, detector grid and keyframe-batch counter.  addFrames() is DepthFilter::updateSeeds of all cameras as ONE
-/// device pass (hip_bridge::updateCameras -> svo_hip_seed_batch_update_cameras_async); each camera's callbacks, grid marks and
+/// device pass (hip_bridge::updateCameraRig -> svo_hip_seed_batch_update_cameras_async, or svo_hip_seed_batch_update_rig_async when the
+/// cameras' models differ); each camera's callbacks, grid marks and
 /// erasures come in the order of a lone DepthFilter fed the same frames (tests/test_gpu_depth_filter_group_cpp.py).
 /// Frame ids are what the shared caches know a pyramid by: they must be unique across the cameras (Frame::frame_counter_ is).
 class DepthFilterGroup {
@@ -950,8 +962,8 @@ class DepthFilterGroup {
     for (GroupHost& h : host_objs) hosts.push_back(&h);
     std::vector<hip_bridge::SeedBatchStats> st(who.size());
     svo_hip_df_params prm{3, 10, 1000, options_.seed_convergence_sigma2_thresh};
-    hip_bridge::updateCameras(who.size(), mirrors.data(), hosts.data(), ctx_, lists.data(), frs.data(), prm, counters.data(), options_.max_n_kfs, halt_,
-                              st.data(), sub_batch_);
+    hip_bridge::updateCameraRig(who.size(), mirrors.data(), hosts.data(), ctx_, lists.data(), frs.data(), prm, counters.data(), options_.max_n_kfs,
+                                halt_, st.data(), sub_batch_);
     bool failed = false;
     for (size_t k = 0; k < who.size(); ++k) { last_stats_[who[k]] = st[k]; failed = failed || st[k].n_device_errors != 0; }
     if (failed) throw std::runtime_error(std::string("depth_filter_group_update: ") + svo_hip_last_error(ctx_));

@@ -82,9 +82,13 @@ class MultiKeyframeCase:
 
 
 def make_multi_keyframe_case(sizes, seed: int = 5, width: int = 640, height: int = 480, baseline: float = 0.08, depth: float = 2.0,
-                             levels=(0, 0, 0, 1, 2), border: int = 40) -> MultiKeyframeCase:
+                             levels=(0, 0, 0, 1, 2), border: int = 40, cam=None) -> MultiKeyframeCase:
+    """`cam`: the camera that renders and observes the scene (width x height; default synth.Camera.default).  The bearings are
+    those of the undistorted pinhole model: the caller of a camera with distortion replaces them."""
     rng = np.random.default_rng(seed)
-    cam = synth.Camera.default(width, height)
+    if cam is None:
+        cam = synth.Camera.default(width, height)
+    assert (cam.width, cam.height) == (width, height)
     scene = synth.PlaneScene(seed=seed, depth=depth, tilt=(rng.uniform(-0.15, 0.15), rng.uniform(-0.15, 0.15)))
     T_cur_w = synth.se3_from_twist(rng.uniform(-0.05, 0.05, 3), rng.uniform(-0.02, 0.02, 3))
     cur_pyr = synth.build_pyramid(scene.render(cam, T_cur_w))

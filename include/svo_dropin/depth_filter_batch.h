@@ -51,6 +51,7 @@
 #include <vector>
 
 #include "svo_hip.h"
+#include "svo_dropin/camera_rig.h"
 
 namespace svo {
 namespace hip_bridge {
@@ -410,20 +411,40 @@ class DeviceSeedMirror {
 /// DepthFilter::updateSeeds for SEVERAL cameras of one context -- camera c: mirror, host policy, seed list, frame and batch
 /// counter number c -- with ONE device call for all of them (svo_hip_seed_batch_update_cameras_async): phase 1 per mirror in
 /// camera order, the call, phase 3 per mirror in camera order, so that every camera's callbacks, grid marks and erasures come in
-/// the order of its own update().  One camera model and one pair of pyramid batches for all cameras (those of camera 0's host);
-/// a keyframe's updated seeds are reported to Host::setGridOccupancy (no device grid here).
+/// the order of its own update().  One pair of pyramid batches for all cameras (those of camera 0's host); a keyframe's updated
+/// seeds are reported to Host::setGridOccupancy (no device grid here).
+/// updateCameras() is for cameras that share ONE camera model (that of the first camera with a pass); updateCameraRig() below takes
+/// every camera's own model from its host (Host::camera of its frame: same image size, own intrinsics and distortion).
 /// The hosts must SHARE their two pyramid caches: the call takes the batches of hosts[0] for every camera's slots, and nothing here
 /// can check that.  With shared caches a later camera's keyframeSlots() / currentSlot() must not recycle a slot an earlier camera of
 /// the same pass was given: the caller makes every frame of the pass resident TOGETHER before this call, so that the cameras'
 /// look-ups only find resident frames (svo::DepthFilterGroup::addFrames does; slot_table.h: a resident frame keeps its slot).  stats[c]: as update() returns them;
-/// n_device_calls counts the camera's batches in the call.  (The only user of that entry point in this header: code that
-/// never instantiates this template need not link it.)
-template <class Mirror, class Host, class SeedList, class Frame>
-void updateCameras(size_t n_cameras, Mirror* const* mirrors, Host* const* hosts, svo_hip_ctx* ctx, SeedList* const* seeds, Frame* const* frames,
-                   const svo_hip_df_params& prm, const int* batch_counters, int max_n_kfs, const volatile bool& halt, SeedBatchStats* stats,
-                   int sub_batch = 4096) {
+/// n_device_calls counts the camera's batches in the call.  (The only users of the two entry points in this header: code that
+/// never instantiates a template need not link what it calls.)
+// the device call of a pass: RIG = false knows one model only; RIG = true takes the rig call when the models differ
+template <bool RIG> struct CamerasCall;
+template <> struct CamerasCall<false> {
+  static int run(svo_hip_ctx* ctx, int n, const svo_hip_seed_camera_pass* passes, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur,
+                 const svo_hip_camera* models, const svo_hip_camera* first, const svo_hip_df_params* prm) {
+    (void)models;
+    return svo_hip_seed_batch_update_cameras_async(ctx, n, passes, ref, cur, first, prm);
+  }
+};
+template <> struct CamerasCall<true> {
+  static int run(svo_hip_ctx* ctx, int n, const svo_hip_seed_camera_pass* passes, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur,
+                 const svo_hip_camera* models, const svo_hip_camera* first, const svo_hip_df_params* prm) {
+    if (oneCameraModel(models, (size_t)n)) return svo_hip_seed_batch_update_cameras_async(ctx, n, passes, ref, cur, first, prm);
+    return svo_hip_seed_batch_update_rig_async(ctx, n, passes, ref, cur, models, prm);
+  }
+};
+
+template <bool RIG, class Mirror, class Host, class SeedList, class Frame>
+void updateCamerasWith(size_t n_cameras, Mirror* const* mirrors, Host* const* hosts, svo_hip_ctx* ctx, SeedList* const* seeds, Frame* const* frames,
+                       const svo_hip_df_params& prm, const int* batch_counters, int max_n_kfs, const volatile bool& halt, SeedBatchStats* stats,
+                       int sub_batch) {
   std::vector<typename Mirror::Pass> passes(n_cameras);
   std::vector<svo_hip_seed_camera_pass> cams(n_cameras);
+  std::vector<svo_hip_camera> models(n_cameras);             // camera c's model; a camera that sits out gets the first one's (its size)
   std::vector<uint8_t> runs(n_cameras, 0);
   const svo_hip_camera* cam = NULL;
   for (size_t c = 0; c < n_cameras; ++c) {
@@ -440,8 +461,9 @@ void updateCameras(size_t n_cameras, Mirror* const* mirrors, Host* const* hosts,
     if (!cam) cam = &p.cam;
   }
   if (cam) {
-    const int rc = svo_hip_seed_batch_update_cameras_async(ctx, (int)n_cameras, cams.data(), hosts[0]->keyframePyramids(), hosts[0]->currentPyramids(),
-                                                           cam, &prm);
+    for (size_t c = 0; c < n_cameras; ++c) models[c] = cams[c].n_batches ? passes[c].cam : *cam;
+    const int rc = CamerasCall<RIG>::run(ctx, (int)n_cameras, cams.data(), hosts[0]->keyframePyramids(), hosts[0]->currentPyramids(), models.data(),
+                                         cam, &prm);
     // a refused or failed call has enqueued nothing or has waited for what it had: the collect loops skip batches without a pass
     if (rc != SVO_HIP_OK)
       for (size_t c = 0; c < n_cameras; ++c) if (cams[c].n_batches) ++passes[c].st.n_device_errors;
@@ -450,6 +472,23 @@ void updateCameras(size_t n_cameras, Mirror* const* mirrors, Host* const* hosts,
     if (runs[c]) mirrors[c]->collectPass(*hosts[c], *seeds[c], passes[c]);
     stats[c] = passes[c].st;
   }
+}
+
+template <class Mirror, class Host, class SeedList, class Frame>
+void updateCameras(size_t n_cameras, Mirror* const* mirrors, Host* const* hosts, svo_hip_ctx* ctx, SeedList* const* seeds, Frame* const* frames,
+                   const svo_hip_df_params& prm, const int* batch_counters, int max_n_kfs, const volatile bool& halt, SeedBatchStats* stats,
+                   int sub_batch = 4096) {
+  updateCamerasWith<false>(n_cameras, mirrors, hosts, ctx, seeds, frames, prm, batch_counters, max_n_kfs, halt, stats, sub_batch);
+}
+
+/// updateCameras() for a camera rig: camera c's pass goes with the model its host gives for its frame.  Equal models make the
+/// call updateCameras() makes (svo_hip_seed_batch_update_cameras_async); models that differ make ONE
+/// svo_hip_seed_batch_update_rig_async call.
+template <class Mirror, class Host, class SeedList, class Frame>
+void updateCameraRig(size_t n_cameras, Mirror* const* mirrors, Host* const* hosts, svo_hip_ctx* ctx, SeedList* const* seeds, Frame* const* frames,
+                     const svo_hip_df_params& prm, const int* batch_counters, int max_n_kfs, const volatile bool& halt, SeedBatchStats* stats,
+                     int sub_batch = 4096) {
+  updateCamerasWith<true>(n_cameras, mirrors, hosts, ctx, seeds, frames, prm, batch_counters, max_n_kfs, halt, stats, sub_batch);
 }
 
 }  // namespace hip_bridge

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "svo_hip.h"
+#include "svo_dropin/camera_rig.h"
 
 namespace svo {
 namespace hip_bridge {
@@ -696,6 +697,8 @@ class FrameTrackerT {
 /// N cameras -- N FrameHandlerMono objects, each with its own svo::Map -- tracked together: svo_hip_tracker_group (one chain of
 /// launches per call for all of them).  camera(c) is camera c's FrameTrackerT (mapChanged, pointsOptimised, optimiseStructure,
 /// lastFrameBecameKeyframe, imageBuffer as for a lone tracker); trackAll is processFrame's three stages for every camera.
+/// The cameras of a rig each have their own model (one image size): the second constructor takes camera c's from cams[c] and
+/// creates the group with svo_hip_tracker_group_create_rig when they are not all equal.
 template <class Host>
 class FrameTrackerGroupT {
  public:
@@ -706,11 +709,16 @@ class FrameTrackerGroupT {
 
   FrameTrackerGroupT(const svo_hip_camera& cam, const svo_hip_tracker_config& cfg, int n_cameras) : ctx_(0), group_(NULL) {
     if (ctx_.ok() && svo_hip_tracker_group_create(ctx_.get(), &cam, &cfg, n_cameras, &group_) != SVO_HIP_OK) group_ = NULL;
-    for (int c = 0; group_ && c < n_cameras; ++c) {
-      svo_hip_tracker* t = NULL;
-      if (svo_hip_tracker_group_camera(group_, c, &t) != SVO_HIP_OK) { svo_hip_tracker_group_destroy(group_); group_ = NULL; break; }
-      cameras_.push_back(new Camera(ctx_.get(), t, cfg));
+    adoptCameras(cfg, n_cameras);
+  }
+  FrameTrackerGroupT(const std::vector<svo_hip_camera>& cams, const svo_hip_tracker_config& cfg) : ctx_(0), group_(NULL) {
+    const int n = (int)cams.size();
+    if (ctx_.ok() && n > 0) {
+      const int rc = oneCameraModel(cams.data(), cams.size()) ? svo_hip_tracker_group_create(ctx_.get(), &cams[0], &cfg, n, &group_)
+                                                              : svo_hip_tracker_group_create_rig(ctx_.get(), cams.data(), &cfg, n, &group_);
+      if (rc != SVO_HIP_OK) group_ = NULL;
     }
+    adoptCameras(cfg, n);
   }
   ~FrameTrackerGroupT() {
     for (size_t c = 0; c < cameras_.size(); ++c) delete cameras_[c];
@@ -745,6 +753,13 @@ class FrameTrackerGroupT {
  private:
   FrameTrackerGroupT(const FrameTrackerGroupT&);
   FrameTrackerGroupT& operator=(const FrameTrackerGroupT&);
+  void adoptCameras(const svo_hip_tracker_config& cfg, int n_cameras) {
+    for (int c = 0; group_ && c < n_cameras; ++c) {
+      svo_hip_tracker* t = NULL;
+      if (svo_hip_tracker_group_camera(group_, c, &t) != SVO_HIP_OK) { svo_hip_tracker_group_destroy(group_); group_ = NULL; break; }
+      cameras_.push_back(new Camera(ctx_.get(), t, cfg));
+    }
+  }
   TrackerContext ctx_;
   svo_hip_tracker_group* group_;
   std::vector<Camera*> cameras_;

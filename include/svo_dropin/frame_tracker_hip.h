@@ -94,7 +94,15 @@ class FrameTrackerGroup : public FrameTrackerGroupT<SvoTrackerHost> {
  public:
   FrameTrackerGroup(vk::AbstractCamera* cam, int n_cameras, int max_keyframes = 256)
       : FrameTrackerGroupT<SvoTrackerHost>(toCamera(cam), groupConfig(max_keyframes), n_cameras) {}
+  /// a camera rig: camera c tracks with cams[c] (each FrameHandlerMono's own cam_; one image size)
+  explicit FrameTrackerGroup(const std::vector<vk::AbstractCamera*>& cams, int max_keyframes = 256)
+      : FrameTrackerGroupT<SvoTrackerHost>(toCameras(cams), groupConfig(max_keyframes)) {}
  private:
+  static std::vector<svo_hip_camera> toCameras(const std::vector<vk::AbstractCamera*>& cams) {
+    std::vector<svo_hip_camera> out;
+    for (size_t c = 0; c < cams.size(); ++c) out.push_back(toCamera(cams[c]));
+    return out;
+  }
   static svo_hip_tracker_config groupConfig(int max_keyframes) {
     svo_hip_tracker_config cfg = SvoTrackerHost::config(max_keyframes);
     cfg.max_items = (cfg.max_items + 15) / 16 * 16;          // a block of the batched warp stage takes 16 candidates of ONE camera

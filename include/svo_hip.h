@@ -550,13 +550,14 @@ int svo_hip_seed_batch_update_group_async(int n_batches, svo_hip_seed_batch* con
                                           const svo_hip_camera* cam, const double* T_ref_w /* [n_batches][7] */,
                                           const double T_cur_w[7], const svo_hip_df_params* prm, int report_updated);
 /* The pass of SEVERAL cameras -- each with its own current frame (slot cur_slot of `cur`), pose, keyframe flag and batches --
- * as ONE set of launches whatever the number of cameras and batches: the depth filter's counterpart of a tracker group, one
- * camera model for all cameras.  Camera c's batch k runs against keyframe slot ref_slots[k] of `ref` with pose T_ref_w[7 * k ..]
+ * as ONE set of launches whatever the number of cameras and batches: the depth filter's counterpart of a tracker group.  This
+ * form takes one `cam` that every camera shares; svo_hip_seed_batch_update_rig_async below takes a model per camera, and this
+ * call is that one with `cam` repeated.  Camera c's batch k runs against keyframe slot ref_slots[k] of `ref` with pose T_ref_w[7 * k ..]
  * and against the camera's own current image, pose and report_updated.  Results per batch are bit-identical to one
  * svo_hip_seed_batch_update_group_async per camera; collect, pending, erase, download and mark_updated work on the batches
  * afterwards as after that call.  The form is chosen as there (two launches up to the small-pass limit, six beyond).
- * The table of the jobs (a batch's arrays, transforms, current slot and keyframe flag) and the map from every 256-seed block
- * to its job live in device memory of the context: one packed transfer per call out of page-locked staging, both grow-only
+ * The table of the jobs (a batch's arrays, transforms, current slot, keyframe flag and camera), the map from every 256-seed block
+ * to its job and the camera models of the pass live in device memory of the context: one packed transfer per call out of page-locked staging, both grow-only
  * (no allocator call after a warm-up call).  A call may follow another for other batches without a collect in between: the
  * staging area is rewritten only once the previous call's transfer has left it.
  * At most SVO_HIP_DF_CAMERAS_MAX_JOBS batches and SVO_HIP_DF_CAMERAS_MAX_RECORDS seed records (every batch rounded up to 256)
@@ -579,6 +580,15 @@ typedef struct {
 int svo_hip_seed_batch_update_cameras_async(svo_hip_ctx* ctx, int n_cameras, const svo_hip_seed_camera_pass* passes,
                                             const svo_hip_pyramid* ref, const svo_hip_pyramid* cur,
                                             const svo_hip_camera* cam, const svo_hip_df_params* prm);
+/* The same pass for a camera RIG: cams[c] is the model of passes[c]'s camera -- its own fx, fy, cx, cy and distortion.  The image
+ * SIZE is common: the pyramids are shared, so every cams[c] must have the width and height of cams[0] and of `ref` and `cur`
+ * (SVO_HIP_ERR_INVALID otherwise, also for a camera that sits the pass out, and for a null `cams`; checked with everything else
+ * before anything is enqueued).  Every batch's results are bit-identical to svo_hip_seed_batch_update_group_async for its
+ * camera alone with that camera's model; n equal models give what svo_hip_seed_batch_update_cameras_async gives.  The models
+ * (with the pixel error angle 2 atan(1 / (2 |fx|)) each implies) travel behind the job table in the same packed transfer. */
+int svo_hip_seed_batch_update_rig_async(svo_hip_ctx* ctx, int n_cameras, const svo_hip_seed_camera_pass* passes,
+                                        const svo_hip_pyramid* ref, const svo_hip_pyramid* cur,
+                                        const svo_hip_camera* cams /* [n_cameras] */, const svo_hip_df_params* prm);
 /* diagnostic / tuning: passes of at most max_seeds seed records (sum over the batches of a call, each rounded up to 256)
  * run as TWO launches -- one wave takes its four seeds through geometry, search, alignment and update, then one workgroup
  * per batch writes the events -- instead of six; results are bit-identical.  0 switches the form off; at most 16384;
@@ -798,7 +808,7 @@ int svo_hip_tracker_track(svo_hip_tracker* trk, const uint8_t* level0, svo_hip_t
  * north_star's "concurrent frame pairs" for the whole per-frame chain: N svo::FrameHandlerMono objects (N cameras, or N
  * sequences replayed side by side) each track one frame at a time; with N trackers on N host threads the HIP runtime's launch
  * path serialises them (measured: 5.5 k frames/s for one camera, 20 k for 4, 21-26 k for 8-16, whatever the number of hardware
- * queues: profiles/r05_cameras_threads.txt).  A group creates N trackers with one camera model and one configuration that
+ * queues: profiles/r05_cameras_threads.txt).  A group creates N trackers with one image size and one configuration that
  * share the SparseImgAlign solver (camera c = slot c), the frame and keyframe pyramid batches and the per-camera arrays of
  * the batched stages, and tracks one frame of EVERY camera with ONE chain of launches: every kernel of the chain takes one
  * workgroup (or one slice of its grid) per camera, the cameras' arguments come from a table in device memory.
@@ -811,10 +821,19 @@ int svo_hip_tracker_track(svo_hip_tracker* trk, const uint8_t* level0, svo_hip_t
  * than alone (rounding level on that frame; every later frame starts from that pose).  With
  * svo_hip_tracker_set_sia_option(SVO_HIP_SIA_OPT_REDUCTION, SVO_HIP_SIA_REDUCTION_TILE_ORDER) on the group AND on the lone
  * tracker nothing depends on the company: every camera equals its lone tracker whatever the other cameras hold
- * (tests/test_gpu_tracker_invariance.py).  cfg->max_items must be a multiple of 16 when n_cameras > 1. */
+ * (tests/test_gpu_tracker_invariance.py).  cfg->max_items must be a multiple of 16 when n_cameras > 1.
+ * The cameras of a RIG each have their own model: svo_hip_tracker_group_create_rig takes cams[n_cameras], cams[c] camera c's
+ * fx, fy, cx, cy and distortion, and every stage of the chain, the per-handle calls (relocalisation, map edits,
+ * svo_hip_tracker_mark_last_frame, the structure step) and the pose refinement's error multiplier |fx| use camera c's own:
+ * camera c equals a lone svo_hip_tracker created with cams[c] (tests/test_gpu_tracker_rig.py).  The image SIZE is common -- the
+ * pyramid batches, the grid and the page-locked image blocks are shared and sized once: SVO_HIP_ERR_INVALID for a camera whose
+ * width or height differs from cams[0], for a null `cams`, n_cameras < 1 and for what svo_hip_tracker_create refuses, for any
+ * camera; a refused call has allocated nothing.  svo_hip_tracker_group_create is the rig call with `cam` repeated. */
 typedef struct svo_hip_tracker_group svo_hip_tracker_group;
 int svo_hip_tracker_group_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const svo_hip_tracker_config* cfg, int n_cameras,
                                  svo_hip_tracker_group** out);
+int svo_hip_tracker_group_create_rig(svo_hip_ctx* ctx, const svo_hip_camera* cams /* [n_cameras] */, const svo_hip_tracker_config* cfg,
+                                     int n_cameras, svo_hip_tracker_group** out);
 int svo_hip_tracker_group_destroy(svo_hip_tracker_group* group);
 int svo_hip_tracker_group_camera(svo_hip_tracker_group* group, int index, svo_hip_tracker** camera);
 /* One frame of every camera: level0[c] = camera c's new image (its svo_hip_tracker_image_buffer: no copy); results[n_cameras]
