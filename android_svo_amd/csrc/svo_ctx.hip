@@ -315,8 +315,14 @@ int svo_hip_pyramid_create(svo_hip_ctx* ctx, int width, int height, int n_levels
   }
   p->level_offset[n_levels] = off;
   p->pyr_bytes = off;
+  // tail slack for the 8-byte row reads.  64 bytes cover every accepted patch (it ends at most one byte past its level).  A
+  // patch that is NOT accepted still has its rows loaded, from offset 0 of the level (svo_sia.hip: 7 rows of 8 bytes, the last
+  // byte at 6 * cols + 7): on a last level of fewer than 7 rows that is past the level, by more than 64 bytes when the level
+  // is wide and short (752x64: level 4 is 47x4 = 188 bytes in a block of 192, the loads end at byte 289).
+  const size_t last_cols = (size_t)(width >> (n_levels - 1)), last_bytes = off - p->level_offset[n_levels - 1];
+  const size_t past_last = 6 * last_cols + 8 > last_bytes ? 6 * last_cols + 8 - last_bytes : 0;
   void* d = nullptr;
-  int rc = svo_hip_malloc(ctx, &d, p->pyr_bytes * (size_t)batch + 64);   // +64: tail slack for 8-byte row reads
+  int rc = svo_hip_malloc(ctx, &d, p->pyr_bytes * (size_t)batch + (past_last > 64 ? past_last : 64));
   if (rc != SVO_HIP_OK) { delete p; return rc; }
   p->base = (uint8_t*)d;
   *out = p;

@@ -236,6 +236,15 @@ class Pyramid:
         self.ctx.check(self.ctx.lib.svo_hip_pyramid_upload_level0_and_build(self.h, slot, _ptr(im, C.c_uint8)), "pyramid_build")
         self.ctx.sync()
 
+    def upload_level0_batch_and_build(self, first_slot: int, imgs):
+        """svo_hip_pyramid_upload_level0_batch_and_build: level 0 of len(imgs) consecutive slots in one strided transfer, the
+        coarser levels of all of them on the device"""
+        packed = np.ascontiguousarray(np.stack([np.asarray(im, dtype=np.uint8) for im in imgs]))
+        assert packed.shape[1:] == (self.height, self.width)
+        self.ctx.check(self.ctx.lib.svo_hip_pyramid_upload_level0_batch_and_build(self.h, first_slot, len(packed), _ptr(packed, C.c_uint8)),
+                       "pyramid_batch_build")
+        self.ctx.sync()
+
     def download_level(self, slot: int, level: int) -> np.ndarray:
         out = np.empty((self.height >> level, self.width >> level), dtype=np.uint8)
         self.ctx.check(self.ctx.lib.svo_hip_pyramid_download_level(self.h, slot, level, _ptr(out, C.c_uint8)), "pyramid_download")

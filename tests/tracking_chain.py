@@ -15,11 +15,15 @@ CELL = 30           # Config::gridSize()
 MAX_FTS = 120       # Config::maxFts()
 
 
-def make_sequence(n_frames=20, n_map=600, orbit=False):
+def make_sequence(n_frames=20, n_map=600, orbit=False, width=640, height=480, focal=None, border=48):
     """orbit: instead of moving on, the camera walks the first 20 poses of the path back and forth (0 .. 19 .. 0 .. 19 ...), so
-    that a sequence of any length keeps the keyframe's map in view."""
+    that a sequence of any length keeps the keyframe's map in view.
+    width, height, focal: the camera (focal None: synth.Camera.default's); border: how far from the image border the map's
+    features in keyframe 0 stay."""
     rng = np.random.default_rng(2024)
-    cam = synth.Camera.default()
+    cam = synth.Camera.default(width, height)
+    if focal is not None:
+        cam.fx = cam.fy = float(focal)
     scene = synth.PlaneScene(seed=77, depth=2.2, tilt=(0.06, -0.04))
     T0 = synth.se3_from_twist([0.01, -0.02, 0.0], [0.004, -0.003, 0.002])
     step_t, step_r = np.array([0.012, 0.004, -0.003]), np.array([0.0015, -0.0025, 0.002])
@@ -38,7 +42,7 @@ def make_sequence(n_frames=20, n_map=600, orbit=False):
         pyrs = [base[j] for j in idx]
     if not orbit:
         pyrs = [synth.build_pyramid(scene.render(cam, T)) for T in truth]
-    px0 = synth.grid_features(cam, n_map, rng)           # the map: points seen in keyframe 0
+    px0 = synth.grid_features(cam, n_map, rng, border=border)      # the map: points seen in keyframe 0
     f0 = synth.cam2world(cam, px0)
     pos = scene.intersect(cam, T0, px0[:, 0], px0[:, 1])
     return dict(cam=cam, truth=truth, pyrs=pyrs, px0=px0, f0=f0, pos=pos, T0=T0)
