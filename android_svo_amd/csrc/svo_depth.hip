@@ -274,6 +274,63 @@ static void df_launch_pixel_stages(svo_hip_ctx* ctx, const DfFrame& fr, const ui
   if (stamps) df_stamp(ctx, 3);
 }
 
+// scratch of a resident-batch pass of n_blocks 256-record blocks: records (every block of the thread-per-seed stages whole), the
+// transposed patches, the levels
+struct DfPassScratch { DfScratch s; int32_t* level_cat; };
+static int df_pass_scratch(svo_hip_ctx* ctx, int n_blocks, DfPassScratch* p) {
+  const int n_rec = n_blocks * 256;
+  const size_t rec_bytes = (size_t)n_rec * sizeof(SeedRec), pwb_bytes = (size_t)25 * n_rec * sizeof(uint32_t);
+  void* ws = nullptr;
+  if (const int rc = svo_ctx_scratch(ctx, rec_bytes + pwb_bytes + (size_t)n_rec * sizeof(int32_t), &ws); rc != SVO_HIP_OK) return rc;
+  p->s = {(SeedRec*)ws, reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + rec_bytes), n_rec};
+  p->level_cat = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + rec_bytes + pwb_bytes);
+  return SVO_HIP_OK;
+}
+
+// the pixel stages of a large resident-batch pass, n_fine workgroups of 16 records (search) or 16 patches (align): over the
+// concatenation up to the last job's last record where the jobs are a group's, job by job where they are a table's
+static_assert(SEEDS_PER_BLOCK == ALIGN_PATCHES && 256 % SEEDS_PER_BLOCK == 0, "one fine grid for both pixel stages");
+static void df_launch_jobs_pixel_stages(svo_hip_ctx* ctx, const DfFrame& fr, const DfGroupJobs& jobs, const svo_hip_pyramid* ref, int,
+                                        const DfPassScratch& p) {
+  const DfJob& last = jobs.g.job[jobs.g.n_jobs - 1];
+  df_launch_pixel_stages(ctx, fr, ref->base, ref->pyr_bytes, jobs.cur_pyr, last.first_block * 256 + last.n, p.level_cat, p.s, false, true);
+}
+static void df_launch_jobs_pixel_stages(svo_hip_ctx* ctx, const DfFrame& fr, const DfTableJobs& jobs, const svo_hip_pyramid* ref, int n_fine,
+                                        const DfPassScratch& p) {
+  const DfCamJob* table = (const DfCamJob*)jobs.jobs;      // (these two kernels take the table's addresses one by one)
+  const int* block_job = (const int*)jobs.block_job;
+  hipLaunchKernelGGL(df_search_jobs_kernel, dim3(n_fine), dim3(256), 0, ctx->stream, fr, table, block_job, (const DfCamModel*)jobs.cams, ref->base,
+                     ref->pyr_bytes, jobs.cur_base, jobs.cur_pyr_bytes, (const int32_t*)p.level_cat, p.s.recs, p.s.pwb_t, p.s.n_pad);
+  df_stamp(ctx, 2);
+  hipLaunchKernelGGL(df_align_jobs_kernel, dim3(n_fine), dim3(ALIGN_BLOCK), 0, ctx->stream, fr, table, block_job, jobs.cur_base, jobs.cur_pyr_bytes,
+                     p.s.n_pad, (const uint32_t*)p.s.pwb_t, p.s.recs);
+  df_stamp(ctx, 3);
+}
+
+// The launches of a resident-batch pass over n_jobs jobs of n_blocks 256-record blocks together, from either job source: two for a
+// small pass (a wave takes its four seeds through every stage, then one workgroup per job does the events), six otherwise.
+template <class Jobs>
+static void df_launch_jobs_pass(svo_hip_ctx* ctx, const DfFrame& fr, const Jobs& jobs, int n_jobs, int n_blocks, int n_fine,
+                                const svo_hip_pyramid* ref, const DfPassScratch& p) {
+  const auto last = [ctx] { if (ctx->df_profile) { (void)hipEventRecord(ctx->df_ev[4], ctx->stream); ctx->df_ev_recorded = true; } };
+  df_stamp(ctx, 0);
+  if (n_blocks * 256 <= ctx->df_small_max) {
+    hipLaunchKernelGGL(df_small_pass_kernel<Jobs>, dim3(n_fine), dim3(256), 0, ctx->stream, fr, jobs, ref->base, ref->pyr_bytes, p.s.recs,
+                       p.s.pwb_t, p.level_cat, p.s.n_pad);
+    df_stamp(ctx, 1); df_stamp(ctx, 2); df_stamp(ctx, 3);
+    last();
+    hipLaunchKernelGGL(ev_small_kernel<Jobs>, dim3(n_jobs), dim3(1024), 0, ctx->stream, jobs);
+  } else {
+    hipLaunchKernelGGL(df_geometry_jobs_kernel<Jobs>, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, p.s.recs, p.level_cat);
+    df_stamp(ctx, 1);
+    df_launch_jobs_pixel_stages(ctx, fr, jobs, ref, n_fine, p);
+    hipLaunchKernelGGL(df_finalize_jobs_kernel<Jobs>, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, (const SeedRec*)p.s.recs);
+    last();
+    hipLaunchKernelGGL(ev_scan_jobs_kernel<Jobs>, dim3(n_jobs), dim3(1024), 0, ctx->stream, jobs);
+    hipLaunchKernelGGL(ev_scatter_jobs_kernel<Jobs>, dim3(n_blocks), dim3(256), 0, ctx->stream, jobs);
+  }
+}
+
 // One DepthFilter::updateSeeds pass over n seeds in device SoA arrays: geometry -> search -> align -> finalize on the
 // context stream (the stateless entries svo_hip_depth_filter_update[_dev]; the seed batches have their own launches below).
 static int df_run_pass(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, int ref_slot, const svo_hip_pyramid* cur, int cur_slot,
@@ -838,12 +895,12 @@ static void sb_fill_job(DfJob& J, const svo_hip_seed_batch* sb, const double T_r
 static int sb_enqueue_jobs(svo_hip_ctx* ctx, int n_jobs, svo_hip_seed_batch* const* batches, const svo_hip_pyramid* ref, const int* ref_slots,
                            const svo_hip_pyramid* cur, int cur_slot, const svo_hip_camera* cam, const double* T_ref_w,
                            const double T_cur_w[7], const svo_hip_df_params* prm, int report_updated) {
-  const uint8_t* cur_img = cur->base + (size_t)cur_slot * cur->pyr_bytes;
-  const bool prof = ctx->df_profile;
   DfFrame fr;
   df_make_frame(ref, cur, cam, T_ref_w, T_cur_w, prm, fr);
-  DfGroup g;
-  memset(&g, 0, sizeof(g));
+  DfGroupJobs jobs;
+  memset(&jobs, 0, sizeof(jobs));
+  jobs.cur_pyr = cur->base + (size_t)cur_slot * cur->pyr_bytes;
+  DfGroup& g = jobs.g;
   g.n_jobs = n_jobs;
   g.report_updated = report_updated ? 1 : 0;
   int n_blocks = 0, n_cat = 0;
@@ -853,30 +910,9 @@ static int sb_enqueue_jobs(svo_hip_ctx* ctx, int n_jobs, svo_hip_seed_batch* con
     n_cat = n_blocks * 256 + sb->n;
     n_blocks += sb->n_blocks;
   }
-  // scratch of the pass: records (every block of the thread-per-seed stages whole), the transposed patches, the levels
-  const int n_rec = n_blocks * 256;
-  const size_t rec_bytes = (size_t)n_rec * sizeof(SeedRec), pwb_bytes = (size_t)25 * n_rec * sizeof(uint32_t);
-  void* ws = nullptr;
-  if (const int rc = svo_ctx_scratch(ctx, rec_bytes + pwb_bytes + (size_t)n_rec * sizeof(int32_t), &ws); rc != SVO_HIP_OK) return rc;
-  const DfScratch s = {(SeedRec*)ws, reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + rec_bytes), n_rec};
-  int32_t* level_cat = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + rec_bytes + pwb_bytes);
-  df_stamp(ctx, 0);
-  if (n_rec <= ctx->df_small_max) {
-    // two launches: a wave takes its four seeds through every stage, then one workgroup per batch does the events
-    hipLaunchKernelGGL(df_small_pass_kernel, dim3((n_cat + SEEDS_PER_BLOCK - 1) / SEEDS_PER_BLOCK), dim3(256), 0, ctx->stream, fr, g,
-                       ref->base, ref->pyr_bytes, cur_img, n_cat, s.recs, s.pwb_t, level_cat, s.n_pad);
-    df_stamp(ctx, 1); df_stamp(ctx, 2); df_stamp(ctx, 3);
-    if (prof) { (void)hipEventRecord(ctx->df_ev[4], ctx->stream); ctx->df_ev_recorded = true; }
-    hipLaunchKernelGGL(ev_small_kernel, dim3(n_jobs), dim3(1024), 0, ctx->stream, g);
-  } else {
-    hipLaunchKernelGGL(df_geometry_group_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, g, s.recs, level_cat);
-    df_stamp(ctx, 1);
-    df_launch_pixel_stages(ctx, fr, ref->base, ref->pyr_bytes, cur_img, n_cat, level_cat, s, false, true);
-    hipLaunchKernelGGL(df_finalize_group_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, g, (const SeedRec*)s.recs);
-    if (prof) { (void)hipEventRecord(ctx->df_ev[4], ctx->stream); ctx->df_ev_recorded = true; }
-    hipLaunchKernelGGL(ev_scan_group_kernel, dim3(n_jobs), dim3(1024), 0, ctx->stream, g);
-    hipLaunchKernelGGL(ev_scatter_group_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, g);
-  }
+  DfPassScratch p;
+  if (const int rc = df_pass_scratch(ctx, n_blocks, &p); rc != SVO_HIP_OK) return rc;
+  df_launch_jobs_pass(ctx, fr, jobs, n_jobs, n_blocks, (n_cat + SEEDS_PER_BLOCK - 1) / SEEDS_PER_BLOCK, ref, p);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   for (int j = 0; j < n_jobs; ++j) { batches[j]->pending = true; batches[j]->report_updated = g.report_updated; }
   return SVO_HIP_OK;
@@ -984,14 +1020,11 @@ static int df_cameras_pass(svo_hip_ctx* ctx, const char* who, int n_cameras, con
     if (const int rc = df_check_pass_args(ctx, ref, 0, nullptr, cur, 0, &cams[0], prm); rc != SVO_HIP_OK) return rc;
   SVO_REQUIRE(ctx, n_jobs_ll <= SVO_HIP_DF_CAMERAS_MAX_JOBS && n_blocks_ll * 256 <= SVO_HIP_DF_CAMERAS_MAX_RECORDS);
   if (n_jobs_ll == 0) return SVO_HIP_OK;
-  const int n_jobs = (int)n_jobs_ll, n_blocks = (int)n_blocks_ll, n_rec = n_blocks * 256;
+  const int n_jobs = (int)n_jobs_ll, n_blocks = (int)n_blocks_ll;
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  // ---- memory: the pass's scratch (records, transposed patches, levels) and the job table; nothing is enqueued yet
-  const size_t rec_bytes = (size_t)n_rec * sizeof(SeedRec), pwb_bytes = (size_t)25 * n_rec * sizeof(uint32_t);
-  void* ws = nullptr;
-  if (const int rc = svo_ctx_scratch(ctx, rec_bytes + pwb_bytes + (size_t)n_rec * sizeof(int32_t), &ws); rc != SVO_HIP_OK) return rc;
-  const DfScratch s = {(SeedRec*)ws, reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + rec_bytes), n_rec};
-  int32_t* level_cat = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + rec_bytes + pwb_bytes);
+  // ---- memory: the pass's scratch and the job table; nothing is enqueued yet
+  DfPassScratch p;
+  if (const int rc = df_pass_scratch(ctx, n_blocks, &p); rc != SVO_HIP_OK) return rc;
   const size_t jobs_bytes = (size_t)n_jobs * sizeof(DfCamJob), cams_off = (jobs_bytes + (size_t)n_blocks * sizeof(int) + 7) & ~(size_t)7,
                table_bytes = cams_off + (size_t)n_models * sizeof(DfCamModel);
   if (const int rc = df_jobs_area(ctx, table_bytes); rc != SVO_HIP_OK) return rc;
@@ -1014,41 +1047,18 @@ static int df_cameras_pass(svo_hip_ctx* ctx, const char* who, int n_cameras, con
       first_block += sb->n_blocks;
     }
   }
-  const DfCamJob* jobs = static_cast<const DfCamJob*>(ctx->df_jobs_dev);
-  const int* block_job = reinterpret_cast<const int*>(static_cast<const char*>(ctx->df_jobs_dev) + jobs_bytes);
-  const DfCamModel* cam_table = reinterpret_cast<const DfCamModel*>(static_cast<const char*>(ctx->df_jobs_dev) + cams_off);
+  const char* table = static_cast<const char*>(ctx->df_jobs_dev);
+  const DfTableJobs jobs = {(DfFixed<DfCamJob>)table, (DfFixed<int>)(table + jobs_bytes), (DfFixed<DfCamModel>)(table + cams_off), cur->base,
+                            cur->pyr_bytes};
   DfFrame fr;                                              // (its cam gives the kernels the common image size and nothing else)
   df_make_pass_frame(ref, cur, &cams[0], prm, fr);
-  const bool prof = ctx->df_profile;
   // ---- the transfer and the launches; from here on an error path waits for the stream before it returns
   hipError_t e = hipMemcpyAsync(ctx->df_jobs_dev, ctx->df_jobs_host, table_bytes, hipMemcpyHostToDevice, ctx->stream);
   if (e != hipSuccess) return svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, hipGetErrorString(e));
   e = hipEventRecord(ctx->df_jobs_ev, ctx->stream);
   if (e == hipSuccess) {
     ctx->df_jobs_in_flight = true;
-    df_stamp(ctx, 0);
-    const dim3 fine(n_blocks * (256 / SEEDS_PER_BLOCK));   // 16 records (search) or 16 patches (align) a workgroup
-    static_assert(SEEDS_PER_BLOCK == ALIGN_PATCHES && 256 % SEEDS_PER_BLOCK == 0, "one fine grid for both pixel stages");
-    if (n_rec <= ctx->df_small_max) {
-      hipLaunchKernelGGL(df_small_pass_jobs_kernel, fine, dim3(256), 0, ctx->stream, fr, jobs, block_job, cam_table, ref->base, ref->pyr_bytes,
-                         cur->base, cur->pyr_bytes, s.recs, s.pwb_t, level_cat, s.n_pad);
-      df_stamp(ctx, 1); df_stamp(ctx, 2); df_stamp(ctx, 3);
-      if (prof) { (void)hipEventRecord(ctx->df_ev[4], ctx->stream); ctx->df_ev_recorded = true; }
-      hipLaunchKernelGGL(ev_small_jobs_kernel, dim3(n_jobs), dim3(1024), 0, ctx->stream, jobs);
-    } else {
-      hipLaunchKernelGGL(df_geometry_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, block_job, cam_table, s.recs, level_cat);
-      df_stamp(ctx, 1);
-      hipLaunchKernelGGL(df_search_jobs_kernel, fine, dim3(256), 0, ctx->stream, fr, jobs, block_job, cam_table, ref->base, ref->pyr_bytes,
-                         cur->base, cur->pyr_bytes, (const int32_t*)level_cat, s.recs, s.pwb_t, s.n_pad);
-      df_stamp(ctx, 2);
-      hipLaunchKernelGGL(df_align_jobs_kernel, fine, dim3(ALIGN_BLOCK), 0, ctx->stream, fr, jobs, block_job, cur->base, cur->pyr_bytes, s.n_pad,
-                         (const uint32_t*)s.pwb_t, s.recs);
-      df_stamp(ctx, 3);
-      hipLaunchKernelGGL(df_finalize_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, fr, jobs, block_job, cam_table, (const SeedRec*)s.recs);
-      if (prof) { (void)hipEventRecord(ctx->df_ev[4], ctx->stream); ctx->df_ev_recorded = true; }
-      hipLaunchKernelGGL(ev_scan_jobs_kernel, dim3(n_jobs), dim3(1024), 0, ctx->stream, jobs);
-      hipLaunchKernelGGL(ev_scatter_jobs_kernel, dim3(n_blocks), dim3(256), 0, ctx->stream, jobs, block_job);
-    }
+    df_launch_jobs_pass(ctx, fr, jobs, n_jobs, n_blocks, n_blocks * (256 / SEEDS_PER_BLOCK), ref, p);
     e = hipGetLastError();
   }
   if (e != hipSuccess) {

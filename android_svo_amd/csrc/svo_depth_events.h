@@ -1,6 +1,7 @@
 // svo_depth_events.h -- what the host hears of a pass, in seed order: the converged-seed records of the multi-GPU gather and the
 // events of a device-resident seed batch, with the grouped and small-pass kernels that produce them.  One block scan, one
-// ordered rank, one event rule and one event record, shared by the large-pass and small-pass forms.
+// ordered rank, one event rule and one event record, shared by the large-pass and small-pass forms; each of those kernels is
+// written once over a job source (DfGroupJobs: the jobs in the kernel arguments; DfTableJobs: a job table in device memory).
 #pragma once
 #include "svo_depth_seed.h"
 #include "svo_depth_search.h"
@@ -153,31 +154,81 @@ SVO_DEV void df_geometry_job_seed(const DfFrame& fr, const Cam& cam, const DfJob
   }
 }
 
-__global__ __launch_bounds__(256) void df_geometry_group_kernel(DfFrame fr, DfGroup g, SeedRec* __restrict__ recs,
-                                                                int32_t* __restrict__ level_cat) {
-  const DfJob& J = g.job[job_of_block(g, blockIdx.x)];
+// ---- where a block of a resident-batch pass finds its job ------------------------------------------------------------------
+// The grouped and small-pass kernels below are written once over a job source, and instantiated for the two there are.  A
+// source answers, for a 256-record block or a job index: which job, its DfJob, its report_updated, its camera's model and
+// px_error_angle, its current image.  All of it is block-uniform; the kernels take what they need of it BEFORE THEIR FIRST
+// STORE, so that it is read on the scalar side.
+// DfGroupJobs: the jobs travel in the kernel arguments (svo_hip_seed_batch_update[_group]_async): at most DF_GROUP_MAX batches of
+// one camera, whose model is the DfFrame's and whose current image is one pointer.
+struct DfGroupJobs {
+  DfGroup g;
+  const uint8_t* cur_pyr;
+  SVO_DEV int of_block(int block) const { return job_of_block(g, block); }
+  SVO_DEV const DfJob& job(int j) const { return g.job[j]; }
+  SVO_DEV int report_updated(int) const { return g.report_updated; }
+  SVO_DEV const Cam& cam(const DfFrame& fr, int) const { return fr.cam; }
+  SVO_DEV double px_error_angle(const DfFrame& fr, int) const { return fr.px_error_angle; }
+  SVO_DEV const uint8_t* cur_image(int) const { return cur_pyr; }
+};
+static_assert(sizeof(DfFrame) + sizeof(DfGroupJobs) + 64 <= 4096, "kernel arguments of the grouped stages");
+// DfTableJobs: the jobs lie in a table in device memory (svo_hip_seed_batch_update_cameras_async / _rig_async, DfCamJob in
+// svo_depth_types.h): a block finds its job with one load from the block -> job map; the job names its camera's entry of the
+// camera table and the slot of its camera's current image.  DfFrame::T, ::cam and ::px_error_angle are not read.  With one
+// model in every entry that is a grouped pass per camera, bit for bit (tests/test_gpu_seed_cameras.py); with a model per camera
+// every batch equals a grouped pass with its camera's model (tests/test_gpu_seed_rig.py).
+// No kernel writes the table, so its pointers are to the constant address space: the table's entries stay scalar-side loads after
+// a kernel's stores, which a plain pointer inside a struct (it cannot be __restrict__) would not give.
+template <class T> using DfFixed = const __attribute__((address_space(4))) T*;
+struct DfTableJobs {
+  DfFixed<DfCamJob> jobs;
+  DfFixed<int> block_job;
+  DfFixed<DfCamModel> cams;
+  const uint8_t* cur_base;
+  size_t cur_pyr_bytes;
+  SVO_DEV const DfCamJob& entry(int j) const { return *(const DfCamJob*)(jobs + j); }
+  SVO_DEV const DfCamModel& model(int j) const { return *(const DfCamModel*)(cams + jobs[j].cam); }
+  SVO_DEV int of_block(int block) const { return block_job[block]; }
+  SVO_DEV const DfJob& job(int j) const { return entry(j).job; }
+  SVO_DEV int report_updated(int j) const { return jobs[j].report_updated; }
+  SVO_DEV const Cam& cam(const DfFrame&, int j) const { return model(j).cam; }
+  SVO_DEV double px_error_angle(const DfFrame&, int j) const { return model(j).px_error_angle; }
+  SVO_DEV const uint8_t* cur_image(int j) const { return cur_base + (size_t)jobs[j].cur_slot * cur_pyr_bytes; }
+};
+
+template <class Jobs>
+__global__ __launch_bounds__(256) void df_geometry_jobs_kernel(DfFrame fr, Jobs jobs, SeedRec* __restrict__ recs, int32_t* __restrict__ level_cat) {
+  const int j = jobs.of_block(blockIdx.x);
+  const DfJob& J = jobs.job(j);
+  const Cam cam = jobs.cam(fr, j);
   const int i = (blockIdx.x - J.first_block) * 256 + threadIdx.x;       // seed of its batch
   if (i < 8) J.hist[i] = 0;
-  df_geometry_job_seed(fr, fr.cam, J, i, (size_t)blockIdx.x * 256 + threadIdx.x, recs, level_cat);
+  df_geometry_job_seed(fr, cam, J, i, (size_t)blockIdx.x * 256 + threadIdx.x, recs, level_cat);
 }
 
-__global__ __launch_bounds__(256) void df_finalize_group_kernel(DfFrame fr, DfGroup g, const SeedRec* __restrict__ recs) {
-  const DfJob& J = g.job[job_of_block(g, blockIdx.x)];
+template <class Jobs>
+__global__ __launch_bounds__(256) void df_finalize_jobs_kernel(DfFrame fr, Jobs jobs, const SeedRec* __restrict__ recs) {
+  const int j = jobs.of_block(blockIdx.x);
+  const DfJob& J = jobs.job(j);
+  const Cam cam = jobs.cam(fr, j);
+  const double px_error_angle = jobs.px_error_angle(fr, j);
+  const int report_updated = jobs.report_updated(j);
   const int block = blockIdx.x - J.first_block;
   const int i = block * 256 + threadIdx.x;
   int st = SVO_HIP_SEED_ERASED;
   if (i < J.n) {
     const SeedRec rc = recs[(size_t)blockIdx.x * 256 + threadIdx.x];
-    st = df_finalize_seed(fr.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, fr.px_error_angle, fr.conv_thresh, i, rc, J.f, J.a, J.b, J.mu,
+    st = df_finalize_seed(cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, px_error_angle, fr.conv_thresh, i, rc, J.f, J.a, J.b, J.mu,
                           J.z_range, J.sigma2, J.status, nullptr, J.xyz, nullptr, nullptr, J.px_cur, nullptr);
   }
-  df_finalize_events(st, i, J.n, block, J.alive, g.report_updated, J.block_count, J.hist);
+  df_finalize_events(st, i, J.n, block, J.alive, report_updated, J.block_count, J.hist);
 }
 
 // exclusive scan of a batch's per-block event counts (one workgroup of 1024 per batch) + the header of its page-locked event
 // block (host memory); the total also to hist[8], where the scatter reads it
-__global__ __launch_bounds__(1024) void ev_scan_group_kernel(DfGroup g) {
-  const DfJob& J = g.job[blockIdx.x];
+template <class Jobs>
+__global__ __launch_bounds__(1024) void ev_scan_jobs_kernel(Jobs jobs) {
+  const DfJob& J = jobs.job(blockIdx.x);
   int total;
   block_scan_counts(J.n_blocks, J.block_count, &total);
   if (threadIdx.x == 0) { J.header->n_events = total; J.hist[8] = total; }
@@ -185,12 +236,15 @@ __global__ __launch_bounds__(1024) void ev_scan_group_kernel(DfGroup g) {
 }
 
 // the events of one 256-seed block, ascending seed index, into the host block or the packed device array (EV_DIRECT_MAX)
-__global__ __launch_bounds__(256) void ev_scatter_group_kernel(DfGroup g) {
-  const DfJob& J = g.job[job_of_block(g, blockIdx.x)];
+template <class Jobs>
+__global__ __launch_bounds__(256) void ev_scatter_jobs_kernel(Jobs jobs) {
+  const int j = jobs.of_block(blockIdx.x);
+  const DfJob& J = jobs.job(j);
+  const int report_updated = jobs.report_updated(j);
   svo_hip_seed_event* events = J.hist[8] <= EV_DIRECT_MAX ? J.events_host : J.events_dev;
   const int block = blockIdx.x - J.first_block, i = block * 256 + threadIdx.x;
   const int st = i < J.n ? J.status[i] : SVO_HIP_SEED_ERASED;
-  const bool ev = seed_event_wanted(st, g.report_updated);
+  const bool ev = seed_event_wanted(st, report_updated);
   __shared__ int s_w[4];
   const int rank = ordered_rank_in_block(ev, s_w);
   if (ev) events[J.block_count[block] + rank] = make_seed_event(i, st, J.mu, J.sigma2, J.xyz, J.px_cur);
@@ -206,157 +260,29 @@ __global__ __launch_bounds__(256) void ev_scatter_group_kernel(DfGroup g) {
 // finalize stage's bookkeeping, ev_scan and ev_scatter do: outcome counts, `alive`, the scan and the ordered events.
 // The lanes that idle through the f64 stages cost nothing here: the chip is empty.  Same device functions as the large pass,
 // so every per-seed result is bit-identical (tests/test_gpu_seed_batch.py).
-__global__ __launch_bounds__(256) void df_small_pass_kernel(DfFrame fr, DfGroup g, const uint8_t* __restrict__ ref_base,
-                                                            size_t ref_pyr_bytes, const uint8_t* __restrict__ cur_pyr, int n_cat,
+// 16 of these workgroups per 256-record block; a wave wholly behind its job's last seed has nothing to do: no later stage reads
+// the records there.
+template <class Jobs>
+__global__ __launch_bounds__(256) void df_small_pass_kernel(DfFrame fr, Jobs jobs, const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes,
                                                             SeedRec* __restrict__ recs, uint32_t* __restrict__ pwb_t,
                                                             int32_t* __restrict__ level_cat, int n_pad) {
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int r0 = (blockIdx.x * 4 + wib) * SEEDS_PER_WAVE;   // the wave's first record
-  if (r0 >= n_cat) return;                                 // wave-uniform; no block-level barrier below
-  const DfJob& J = g.job[job_of_block(g, blockIdx.x >> 4)];          // 16 of these workgroups per 256-seed block
-  const int i0 = r0 - J.first_block * 256;                 // ... and its first seed within its batch
-  // ---- geometry
-  if (lane < SEEDS_PER_WAVE) df_geometry_job_seed(fr, fr.cam, J, i0 + lane, (size_t)r0 + lane, recs, level_cat);
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  // ---- warp + epipolar search
-  df_search_block(fr, fr.cam, ref_base, ref_pyr_bytes, cur_pyr, n_cat, level_cat, recs, pwb_t, n_pad, blockIdx.x);
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  // ---- align2D
-  {
-    const int r = r0 + (lane >> 2);
-    df_align_quad<false>(fr, cur_pyr, n_pad, pwb_t, recs, r, lane < 4 * SEEDS_PER_WAVE && r < n_cat);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  // ---- triangulation, computeTau, updateSeed
-  if (lane < SEEDS_PER_WAVE && i0 + lane < J.n) {
-    const SeedRec rc = recs[(size_t)r0 + lane];
-    (void)df_finalize_seed(fr.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, fr.px_error_angle, fr.conv_thresh, i0 + lane, rc, J.f, J.a, J.b,
-                           J.mu, J.z_range, J.sigma2, J.status, nullptr, J.xyz, nullptr, nullptr, J.px_cur, nullptr);
-  }
-}
-
-// one workgroup of 1024 per batch: what df_finalize_events, ev_scan_group_kernel and ev_scatter_group_kernel do, for a batch of at most
-// DF_SMALL_MAX seeds
-__global__ __launch_bounds__(1024) void ev_small_kernel(DfGroup g) {
-  const DfJob& J = g.job[blockIdx.x];
-  const int n = J.n, report_updated = g.report_updated;
-  __shared__ int s_cnt[DF_SMALL_MAX / 256], s_off[DF_SMALL_MAX / 256], s_hist[8], s_w[16], s_total;
-  if (threadIdx.x < DF_SMALL_MAX / 256) s_cnt[threadIdx.x] = 0;
-  if (threadIdx.x < 8) s_hist[threadIdx.x] = 0;
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += 1024) {
-    const int st = J.status[i];
-    if (seed_gone(st)) J.alive[i] = 0;
-    atomicAdd(&s_hist[st + 1], 1);
-    if (seed_event_wanted(st, report_updated)) atomicAdd(&s_cnt[i >> 8], 1);
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {                                  // exclusive scan of the (at most 64) block counts
-    const int v = threadIdx.x < J.n_blocks ? s_cnt[threadIdx.x] : 0;
-    const int incl = wave_scan_inclusive(v);
-    s_off[threadIdx.x] = incl - v;
-    if (threadIdx.x == 63) s_total = incl;
-  }
-  __syncthreads();
-  const int total = s_total;
-  if (threadIdx.x == 0) { J.header->n_events = total; J.hist[8] = total; }
-  if (threadIdx.x < 7) J.header->counts[threadIdx.x] = s_hist[threadIdx.x];
-  svo_hip_seed_event* events = total <= EV_DIRECT_MAX ? J.events_host : J.events_dev;
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int st = i < n ? J.status[i] : SVO_HIP_SEED_ERASED;
-    const bool ev = seed_event_wanted(st, report_updated);
-    const int rank = ordered_rank_in_block(ev, s_w, (threadIdx.x >> 6) & ~3);   // four waves per 256-seed block
-    if (ev) events[s_off[i >> 8] + rank] = make_seed_event(i, st, J.mu, J.sigma2, J.xyz, J.px_cur);
-    __syncthreads();
-  }
-}
-
-// ---- the batches of several cameras in one launch set (svo_hip_seed_batch_update_cameras_async) ----------------------------
-// The kernels of the grouped pass over a job table in device memory (DfCamJob, svo_depth_types.h) instead of a DfGroup in the
-// kernel arguments: a block finds its job with one load from the block -> job map, the job's fields are block-uniform, its
-// report_updated stands where the group's stood, its cur_slot picks the current image in the pixel stages.  The same device
-// functions as above, so every per-seed result and every event is bit-identical to a grouped pass per camera
-// (tests/test_gpu_seed_cameras.py).  DfFrame::T is not read: the transforms are the job's.  Neither are DfFrame::cam and
-// DfFrame::px_error_angle: they are those of the job's entry in the camera table (DfCamModel), one more block-uniform load, taken
-// before the kernel's first store so that it stays a scalar load.  With one model in every entry that is the pass it was, bit
-// for bit; with a model per camera every batch equals a grouped pass with its camera's model (tests/test_gpu_seed_rig.py).
-__global__ __launch_bounds__(256) void df_geometry_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
-                                                               const DfCamModel* __restrict__ cams, SeedRec* __restrict__ recs,
-                                                               int32_t* __restrict__ level_cat) {
-  const DfCamJob& C = jobs[block_job[blockIdx.x]];
-  const DfJob& J = C.job;
-  const Cam cam = cams[C.cam].cam;
-  const int i = (blockIdx.x - J.first_block) * 256 + threadIdx.x;       // seed of its batch
-  if (i < 8) J.hist[i] = 0;
-  df_geometry_job_seed(fr, cam, J, i, (size_t)blockIdx.x * 256 + threadIdx.x, recs, level_cat);
-}
-
-__global__ __launch_bounds__(256) void df_finalize_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
-                                                               const DfCamModel* __restrict__ cams, const SeedRec* __restrict__ recs) {
-  const DfCamJob& C = jobs[block_job[blockIdx.x]];
-  const DfJob& J = C.job;
-  const DfCamModel M = cams[C.cam];
-  const int block = blockIdx.x - J.first_block;
-  const int i = block * 256 + threadIdx.x;
-  int st = SVO_HIP_SEED_ERASED;
-  if (i < J.n) {
-    const SeedRec rc = recs[(size_t)blockIdx.x * 256 + threadIdx.x];
-    st = df_finalize_seed(M.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, M.px_error_angle, fr.conv_thresh, i, rc, J.f, J.a, J.b, J.mu,
-                          J.z_range, J.sigma2, J.status, nullptr, J.xyz, nullptr, nullptr, J.px_cur, nullptr);
-  }
-  df_finalize_events(st, i, J.n, block, J.alive, C.report_updated, J.block_count, J.hist);
-}
-
-// (one workgroup of 1024 per job)
-__global__ __launch_bounds__(1024) void ev_scan_jobs_kernel(const DfCamJob* __restrict__ jobs) {
-  const DfJob& J = jobs[blockIdx.x].job;
-  int total;
-  block_scan_counts(J.n_blocks, J.block_count, &total);
-  if (threadIdx.x == 0) { J.header->n_events = total; J.hist[8] = total; }
-  if (threadIdx.x < 7) J.header->counts[threadIdx.x] = J.hist[threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void ev_scatter_jobs_kernel(const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job) {
-  const DfCamJob& C = jobs[block_job[blockIdx.x]];
-  const DfJob& J = C.job;
-  svo_hip_seed_event* events = J.hist[8] <= EV_DIRECT_MAX ? J.events_host : J.events_dev;
-  const int block = blockIdx.x - J.first_block, i = block * 256 + threadIdx.x;
-  const int st = i < J.n ? J.status[i] : SVO_HIP_SEED_ERASED;
-  const bool ev = seed_event_wanted(st, C.report_updated);
-  __shared__ int s_w[4];
-  const int rank = ordered_rank_in_block(ev, s_w);
-  if (ev) events[J.block_count[block] + rank] = make_seed_event(i, st, J.mu, J.sigma2, J.xyz, J.px_cur);
-}
-
-// the small pass (df_small_pass_kernel): 16 of these workgroups per 256-record block, a wave takes its four seeds through all
-// four stages; a workgroup wholly behind its job's last seed has nothing to do
-__global__ __launch_bounds__(256) void df_small_pass_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
-                                                                 const DfCamModel* __restrict__ cams,
-                                                                 const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes,
-                                                                 const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes,
-                                                                 SeedRec* __restrict__ recs, uint32_t* __restrict__ pwb_t,
-                                                                 int32_t* __restrict__ level_cat, int n_pad) {
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int r0 = (blockIdx.x * 4 + wib) * SEEDS_PER_WAVE;   // the wave's first record
-  const DfCamJob& C = jobs[block_job[blockIdx.x >> 4]];
-  const DfJob& J = C.job;
+  const int j = jobs.of_block(blockIdx.x >> 4);
+  const DfJob& J = jobs.job(j);
   const int n_end = J.first_block * 256 + J.n;             // the end of the job's records
   if (r0 >= n_end) return;                                 // wave-uniform; no block-level barrier below
-  const DfCamModel M = cams[C.cam];
-  const uint8_t* cur_pyr = cur_base + (size_t)C.cur_slot * cur_pyr_bytes;
+  const Cam cam = jobs.cam(fr, j);
+  const double px_error_angle = jobs.px_error_angle(fr, j);
+  const uint8_t* cur_pyr = jobs.cur_image(j);
   const int i0 = r0 - J.first_block * 256;                 // the wave's first seed within its batch
   // ---- geometry
-  if (lane < SEEDS_PER_WAVE) df_geometry_job_seed(fr, M.cam, J, i0 + lane, (size_t)r0 + lane, recs, level_cat);
+  if (lane < SEEDS_PER_WAVE) df_geometry_job_seed(fr, cam, J, i0 + lane, (size_t)r0 + lane, recs, level_cat);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // ---- warp + epipolar search
-  df_search_block(fr, M.cam, ref_base, ref_pyr_bytes, cur_pyr, n_end, level_cat, recs, pwb_t, n_pad, blockIdx.x);
+  df_search_block(fr, cam, ref_base, ref_pyr_bytes, cur_pyr, n_end, level_cat, recs, pwb_t, n_pad, blockIdx.x);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // ---- align2D
@@ -369,16 +295,17 @@ __global__ __launch_bounds__(256) void df_small_pass_jobs_kernel(DfFrame fr, con
   // ---- triangulation, computeTau, updateSeed
   if (lane < SEEDS_PER_WAVE && i0 + lane < J.n) {
     const SeedRec rc = recs[(size_t)r0 + lane];
-    (void)df_finalize_seed(M.cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, M.px_error_angle, fr.conv_thresh, i0 + lane, rc, J.f, J.a, J.b,
+    (void)df_finalize_seed(cam, J.T.T_cur_ref, J.T.T_ref_cur, J.T.T_ref_inv, px_error_angle, fr.conv_thresh, i0 + lane, rc, J.f, J.a, J.b,
                            J.mu, J.z_range, J.sigma2, J.status, nullptr, J.xyz, nullptr, nullptr, J.px_cur, nullptr);
   }
 }
 
-// (ev_small_kernel over the table: one workgroup of 1024 per job of at most DF_SMALL_MAX seeds)
-__global__ __launch_bounds__(1024) void ev_small_jobs_kernel(const DfCamJob* __restrict__ jobs) {
-  const DfCamJob& C = jobs[blockIdx.x];
-  const DfJob& J = C.job;
-  const int n = J.n, report_updated = C.report_updated;
+// one workgroup of 1024 per batch: what df_finalize_events, ev_scan_jobs_kernel and ev_scatter_jobs_kernel do, for a batch of at
+// most DF_SMALL_MAX seeds
+template <class Jobs>
+__global__ __launch_bounds__(1024) void ev_small_kernel(Jobs jobs) {
+  const DfJob& J = jobs.job(blockIdx.x);
+  const int n = J.n, report_updated = jobs.report_updated(blockIdx.x);
   __shared__ int s_cnt[DF_SMALL_MAX / 256], s_off[DF_SMALL_MAX / 256], s_hist[8], s_w[16], s_total;
   if (threadIdx.x < DF_SMALL_MAX / 256) s_cnt[threadIdx.x] = 0;
   if (threadIdx.x < 8) s_hist[threadIdx.x] = 0;

@@ -1,5 +1,7 @@
 // svo_depth_types.h -- the depth filter's constants and the structs its kernels and the host half of svo_depth.hip share: the
-// frame-level constants of a pass, a keyframe's transforms, the jobs of a grouped pass, the header of the event block.  The
+// frame-level constants of a pass, a keyframe's transforms, the jobs of a grouped pass in their two forms (DfGroup for the kernel
+// arguments, DfCamJob / DfCamModel for a table in device memory; the job sources over them, DfGroupJobs and DfTableJobs, are in
+// svo_depth_events.h beside the kernels written over them), the header of the event block.  The
 // svo_depth_*.h headers are the parts of that ONE translation unit (anonymous namespace, `using namespace` at header scope):
 // nothing else may include them.
 #pragma once
@@ -80,7 +82,6 @@ struct DfGroup {
   DfJob job[DF_GROUP_MAX];
   int n_jobs, report_updated;
 };
-static_assert(sizeof(DfFrame) + sizeof(DfGroup) + 64 <= 4096, "kernel arguments of the grouped stages");
 // DfPoses sits where the four double[7] sat: the layout of the kernel arguments is what it was
 static_assert(sizeof(DfPoses) == 4 * 7 * sizeof(double) && offsetof(DfPoses, T_cur_ref_vis) == 56 && offsetof(DfPoses, T_cur_ref) == 112 &&
               offsetof(DfPoses, T_ref_inv) == 168, "four transforms back to back");
