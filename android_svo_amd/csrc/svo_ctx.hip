@@ -11,10 +11,14 @@ namespace {
 // 2x2 truncating mean, one thread per 4 output pixels (reads 2 x 8 B, writes 4 B):
 // vk::halfSample scalar / NEON form, vision.cpp:49-67,89-110.  HBM-bound: 1.25 B moved
 // per input byte.
-// in / out point at the level inside pyramid slot 0 of the launch; blockIdx.z selects the slot (stride pyr_bytes)
-__global__ void half_sample_kernel(const uint8_t* __restrict__ in, int w, int h, uint8_t* __restrict__ out, size_t slot_stride = 0) {
-  in += (size_t)blockIdx.z * slot_stride;
-  out += (size_t)blockIdx.z * slot_stride;
+// in / out point at the level inside pyramid slot 0 of the launch; blockIdx.z selects the slot (stride pyr_bytes), or the
+// entry of slot_list that names it (LIST: a tracker group's subset call)
+template <bool LIST>
+__global__ void half_sample_kernel(const uint8_t* __restrict__ in, int w, int h, uint8_t* __restrict__ out, size_t slot_stride = 0,
+                                   const int* __restrict__ slot_list = nullptr) {
+  const int z = LIST ? slot_list[blockIdx.z] : (int)blockIdx.z;
+  in += (size_t)z * slot_stride;
+  out += (size_t)z * slot_stride;
   const int ow = w >> 1, oh = h >> 1;
   const int quads = (ow + 3) >> 2;
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -47,17 +51,20 @@ __global__ void half_sample_kernel(const uint8_t* __restrict__ in, int w, int h,
 // inside this kernel and is written to the pyramid's level 0 on the way -- no separate copy, no dependent launch behind
 // it).  The strip is read row by row, 16 bytes per lane, consecutive lanes consecutive addresses: whole rows per request
 // (64 x 16 tiles, i.e. 64-byte requests, read the image at a third of the link rate).
+// LIST: blockIdx.z is an index into slot_list, whose entry names the slot (and the image block) the workgroup builds.
 constexpr int PYR_STRIP_MAX_W = 2048;
+template <bool LIST>
 __global__ __launch_bounds__(256) void pyramid_strip_kernel(uint8_t* __restrict__ base, int w, int h, int n_levels, size_t o1, size_t o2,
                                                             size_t o3, size_t o4, size_t slot_stride, const uint8_t* __restrict__ src0,
-                                                            size_t src_stride = 0) {
+                                                            size_t src_stride = 0, const int* __restrict__ slot_list = nullptr) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   uint8_t* l0 = lds;                      // [16][w]
   uint8_t* l1 = l0 + 16 * w;              // [8][w/2]
   uint8_t* l2 = l1 + 4 * w;               // [4][w/4]
   uint8_t* l3 = l2 + w;                   // [2][w/8]
-  base += (size_t)blockIdx.z * slot_stride;
-  if (src0) src0 += (size_t)blockIdx.z * src_stride;       // (a tracker group: the cameras' page-locked images lie src_stride apart)
+  const int z = LIST ? slot_list[blockIdx.z] : (int)blockIdx.z;
+  base += (size_t)z * slot_stride;
+  if (src0) src0 += (size_t)z * src_stride;                // (a tracker group: the cameras' page-locked images lie src_stride apart)
   const int t = threadIdx.x, nt = blockDim.x;
   const int ty = blockIdx.x;
   {
@@ -104,20 +111,50 @@ __global__ __launch_bounds__(256) void pyramid_strip_kernel(uint8_t* __restrict_
   }
 }
 
+// The listed slots of one pyramid batch copied to the same slots of another in ONE launch (a tracker group's subset call
+// carries pyramids between its two frame batches): blockIdx.y = entry of the list, the blocks of a row stride over the slot
+// 16 bytes per lane.  A slot starts slot * pyr_bytes behind the base, which is no multiple of 16 for odd image sizes: the
+// bytes in front of the first 16-byte boundary and behind the last one are copied one by one by the row's first block.  Both
+// bases are 16-byte aligned (the host checks), so source and destination share that boundary.
+__global__ __launch_bounds__(256) void pyramid_copy_slots_kernel(uint8_t* __restrict__ dst_base, const uint8_t* __restrict__ src_base,
+                                                                 size_t pyr_bytes, const int* __restrict__ slot_list) {
+  const size_t o = (size_t)slot_list[blockIdx.y] * pyr_bytes;
+  uint8_t* d = dst_base + o;
+  const uint8_t* s = src_base + o;
+  size_t head = (16 - (o & 15)) & 15;
+  if (head > pyr_bytes) head = pyr_bytes;
+  const size_t n16 = (pyr_bytes - head) / 16;
+  const size_t tail0 = head + n16 * 16;
+  uint4* d4 = reinterpret_cast<uint4*>(d + head);
+  const uint4* s4 = reinterpret_cast<const uint4*>(s + head);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) d4[i] = s4[i];
+  if (blockIdx.x == 0 && threadIdx.x < 16) {
+    if (threadIdx.x < head) d[threadIdx.x] = s[threadIdx.x];
+    const size_t t = tail0 + threadIdx.x;
+    if (t < pyr_bytes) d[t] = s[t];
+  }
+}
+
 }  // namespace
 
 // levels 1.. of n_slots pyramids starting at first_slot, from their level 0 (already in place), on the context stream
 // (level0_mapped: device address of a page-locked host image to take level 0 from -- slot k's image at level0_mapped + k *
 // mapped_stride; null: level 0 is in place)
-int svo_pyramid_build_levels(svo_hip_pyramid* pyr, int first_slot, int n_slots, const uint8_t* level0_mapped, size_t mapped_stride) {
+// (slots_host / slots_dev: the same list of n_slots slots on both sides -- slot s is built from level0_mapped + s * mapped_stride;
+// null: the contiguous range from first_slot)
+static int pyramid_build(svo_hip_pyramid* pyr, int first_slot, int n_slots, const int* slots_host, const int* slots_dev,
+                         const uint8_t* level0_mapped, size_t mapped_stride) {
   svo_hip_ctx* ctx = pyr->ctx;
+  const bool list = slots_dev != nullptr;
   uint8_t* base = pyr->base + (size_t)first_slot * pyr->pyr_bytes;
   const bool tiled = pyr->width % 16 == 0 && pyr->width <= PYR_STRIP_MAX_W && pyr->height % 16 == 0 && pyr->n_levels <= 5 && pyr->n_levels >= 2 &&
                      (pyr->pyr_bytes % 16) == 0;
   if (level0_mapped && !tiled) {       // shapes the tile kernel does not take: an ordinary copy first
-    for (int k = 0; k < n_slots; ++k)
-      SVO_CHECK_HIP(ctx, hipMemcpyAsync(base + (size_t)k * pyr->pyr_bytes, level0_mapped + (size_t)k * mapped_stride, (size_t)pyr->width * pyr->height,
+    for (int k = 0; k < n_slots; ++k) {
+      const size_t z = list ? (size_t)slots_host[k] : (size_t)k;
+      SVO_CHECK_HIP(ctx, hipMemcpyAsync(base + z * pyr->pyr_bytes, level0_mapped + z * mapped_stride, (size_t)pyr->width * pyr->height,
                                         hipMemcpyDefault, ctx->stream));
+    }
     level0_mapped = nullptr;
   }
   if (pyr->n_levels < 2) return SVO_HIP_OK;
@@ -125,8 +162,12 @@ int svo_pyramid_build_levels(svo_hip_pyramid* pyr, int first_slot, int n_slots, 
     const size_t o1 = pyr->level_offset[1], o2 = pyr->n_levels > 2 ? pyr->level_offset[2] : 0, o3 = pyr->n_levels > 3 ? pyr->level_offset[3] : 0,
                  o4 = pyr->n_levels > 4 ? pyr->level_offset[4] : 0;
     const size_t lds = (size_t)16 * pyr->width + 4 * pyr->width + pyr->width + pyr->width / 4 + 64;
-    hipLaunchKernelGGL(pyramid_strip_kernel, dim3(pyr->height / 16, 1, n_slots), dim3(256), lds, ctx->stream, base, pyr->width, pyr->height,
-                       pyr->n_levels, o1, o2, o3, o4, pyr->pyr_bytes, level0_mapped, mapped_stride);
+    if (list)
+      hipLaunchKernelGGL(pyramid_strip_kernel<true>, dim3(pyr->height / 16, 1, n_slots), dim3(256), lds, ctx->stream, base, pyr->width, pyr->height,
+                         pyr->n_levels, o1, o2, o3, o4, pyr->pyr_bytes, level0_mapped, mapped_stride, slots_dev);
+    else
+      hipLaunchKernelGGL(pyramid_strip_kernel<false>, dim3(pyr->height / 16, 1, n_slots), dim3(256), lds, ctx->stream, base, pyr->width, pyr->height,
+                         pyr->n_levels, o1, o2, o3, o4, pyr->pyr_bytes, level0_mapped, mapped_stride, (const int*)nullptr);
     SVO_CHECK_HIP(ctx, hipGetLastError());
     return SVO_HIP_OK;
   }
@@ -134,10 +175,41 @@ int svo_pyramid_build_levels(svo_hip_pyramid* pyr, int first_slot, int n_slots, 
     const int w = pyr->width >> (l - 1), h = pyr->height >> (l - 1);
     const int ow = w >> 1, oh = h >> 1;
     dim3 block(64), grid(((ow + 3) / 4 + 63) / 64, oh, n_slots);
-    hipLaunchKernelGGL(half_sample_kernel, grid, block, 0, ctx->stream, base + pyr->level_offset[l - 1], w, h,
-                       base + pyr->level_offset[l], pyr->pyr_bytes);
+    if (list)
+      hipLaunchKernelGGL(half_sample_kernel<true>, grid, block, 0, ctx->stream, base + pyr->level_offset[l - 1], w, h,
+                         base + pyr->level_offset[l], pyr->pyr_bytes, slots_dev);
+    else
+      hipLaunchKernelGGL(half_sample_kernel<false>, grid, block, 0, ctx->stream, base + pyr->level_offset[l - 1], w, h,
+                         base + pyr->level_offset[l], pyr->pyr_bytes, (const int*)nullptr);
     SVO_CHECK_HIP(ctx, hipGetLastError());
   }
+  return SVO_HIP_OK;
+}
+
+int svo_pyramid_build_levels(svo_hip_pyramid* pyr, int first_slot, int n_slots, const uint8_t* level0_mapped, size_t mapped_stride) {
+  return pyramid_build(pyr, first_slot, n_slots, nullptr, nullptr, level0_mapped, mapped_stride);
+}
+
+int svo_pyramid_build_slots(svo_hip_pyramid* pyr, int n_slots, const int* slots_host, const int* slots_dev, const uint8_t* level0_mapped,
+                            size_t mapped_stride) {
+  if (!pyr || !slots_host || !slots_dev) return SVO_HIP_ERR_INVALID;
+  SVO_REQUIRE(pyr->ctx, n_slots >= 1 && n_slots <= pyr->batch);
+  for (int k = 0; k < n_slots; ++k) SVO_REQUIRE(pyr->ctx, slots_host[k] >= 0 && slots_host[k] < pyr->batch);
+  return pyramid_build(pyr, 0, n_slots, slots_host, slots_dev, level0_mapped, mapped_stride);
+}
+
+int svo_pyramid_copy_slots(svo_hip_pyramid* dst, const svo_hip_pyramid* src, int n_slots, const int* slots_host, const int* slots_dev) {
+  if (!dst || !src || !slots_host || !slots_dev) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = dst->ctx;
+  SVO_REQUIRE(ctx, dst != src && dst->pyr_bytes == src->pyr_bytes && dst->batch == src->batch && n_slots >= 1 && n_slots <= dst->batch);
+  SVO_REQUIRE(ctx, ((uintptr_t)dst->base & 15) == 0 && ((uintptr_t)src->base & 15) == 0);
+  for (int k = 0; k < n_slots; ++k) SVO_REQUIRE(ctx, slots_host[k] >= 0 && slots_host[k] < dst->batch);
+  // a lane takes four 16-byte pieces or more: at most 64 blocks per slot
+  size_t gx = (dst->pyr_bytes / 16 + 1023) / 1024;
+  gx = gx < 1 ? 1 : gx > 64 ? 64 : gx;
+  hipLaunchKernelGGL(pyramid_copy_slots_kernel, dim3((unsigned)gx, (unsigned)n_slots), dim3(256), 0, ctx->stream, dst->base, src->base, dst->pyr_bytes,
+                     slots_dev);
+  SVO_CHECK_HIP(ctx, hipGetLastError());
   return SVO_HIP_OK;
 }
 

@@ -444,12 +444,28 @@ int svo_match_scratch(svo_hip_ctx* ctx, int n_cap, svo_dev::SeedRec** recs, uint
 
 int svo_match_stages_cams(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, const svo_hip_camera* cam, int n_cams,
                           int cap, const int* counters_dev, int counter_stride, const int32_t* level_ref_dev, svo_dev::SeedRec* recs,
-                          uint32_t* pwb_t, int n_pad, int n_pyr_levels, int align_max_iter, bool edgelets) {
+                          uint32_t* pwb_t, int n_pad, int n_pyr_levels, int align_max_iter, bool edgelets, const int* cam_list_dev, int n_listed) {
   if (!ctx || !ref || !cur || !cam || !recs || !pwb_t || !level_ref_dev || !counters_dev) return SVO_HIP_ERR_INVALID;
   SVO_REQUIRE(ctx, n_cams >= 1 && n_cams <= cur->batch && cap > 0 && cap % SEEDS_PER_BLOCK == 0 && cap % ALIGN_PATCHES == 0 && counter_stride >= 1);
   SVO_REQUIRE(ctx, n_pad >= n_cams * cap);
+  SVO_REQUIRE(ctx, !cam_list_dev || (n_listed >= 1 && n_listed <= n_cams));
   DfFrame fr;
   df_pixel_frame(ref, cur, cam, n_pyr_levels, align_max_iter, 1, fr);
+  if (cam_list_dev) {                // the listed cameras' slices only: the grid is n_listed cameras wide
+    const int n_some = n_listed * cap;
+    hipLaunchKernelGGL(df_search_listed_kernel, dim3(n_some / SEEDS_PER_BLOCK), dim3(256), 0, ctx->stream, fr, ref->base, ref->pyr_bytes, cur->base,
+                       cur->pyr_bytes, cap, counters_dev, counter_stride, level_ref_dev, recs, pwb_t, n_pad, cam_list_dev);
+    SVO_CHECK_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(df_align_listed_kernel<false>, dim3(n_some / ALIGN_PATCHES), dim3(ALIGN_BLOCK), 0, ctx->stream, fr, cur->base, cur->pyr_bytes, cap,
+                       counters_dev, counter_stride, n_pad, pwb_t, recs, cam_list_dev);
+    SVO_CHECK_HIP(ctx, hipGetLastError());
+    if (edgelets) {
+      hipLaunchKernelGGL(df_align_listed_kernel<true>, dim3(n_some / ALIGN_PATCHES), dim3(ALIGN_BLOCK), 0, ctx->stream, fr, cur->base, cur->pyr_bytes, cap,
+                         counters_dev, counter_stride, n_pad, pwb_t, recs, cam_list_dev);
+      SVO_CHECK_HIP(ctx, hipGetLastError());
+    }
+    return SVO_HIP_OK;
+  }
   const int n_all = n_cams * cap;
   hipLaunchKernelGGL(df_search_cams_kernel, dim3(n_all / SEEDS_PER_BLOCK), dim3(256), 0, ctx->stream, fr, ref->base, ref->pyr_bytes, cur->base,
                      cur->pyr_bytes, cap, counters_dev, counter_stride, level_ref_dev, recs, pwb_t, n_pad);

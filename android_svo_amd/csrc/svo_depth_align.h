@@ -176,6 +176,21 @@ __global__ __launch_bounds__(ALIGN_BLOCK) void df_align_cams_kernel(DfFrame fr, 
   df_align_quad<ONE_D>(fr, cur_base + (size_t)c * cur_pyr_bytes, n_pad, pwb_t, recs, i, i < c * cap + n_c);
 }
 
+// (the same over the cameras a list names: the layout of df_search_listed_kernel, svo_depth_search.h)
+template <bool ONE_D>
+__global__ __launch_bounds__(ALIGN_BLOCK) void df_align_listed_kernel(DfFrame fr, const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes, int cap,
+                                                                      const int* __restrict__ counters, int counter_stride, int n_pad,
+                                                                      const uint32_t* __restrict__ pwb_t, SeedRec* __restrict__ recs,
+                                                                      const int* __restrict__ cam_list) {
+  const int per_cam = cap / ALIGN_PATCHES;
+  const int j = (int)blockIdx.x / per_cam;
+  const int c = cam_list[j];
+  const int i = (c * per_cam + ((int)blockIdx.x - j * per_cam)) * ALIGN_PATCHES + (threadIdx.x >> 2);
+  int n_c = counters[(size_t)c * counter_stride];
+  n_c = n_c < cap ? n_c : cap;
+  df_align_quad<ONE_D>(fr, cur_base + (size_t)c * cur_pyr_bytes, n_pad, pwb_t, recs, i, i < c * cap + n_c);
+}
+
 // (the alignment stage over the batches of several cameras: the layout of df_search_jobs_kernel, svo_depth_search.h)
 __global__ __launch_bounds__(ALIGN_BLOCK) void df_align_jobs_kernel(DfFrame fr, const DfCamJob* __restrict__ jobs, const int* __restrict__ block_job,
                                                                     const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes, int n_pad,

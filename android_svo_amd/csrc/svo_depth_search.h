@@ -411,6 +411,22 @@ __global__ __launch_bounds__(256, 7) void df_search_cams_kernel(
   df_search_block(fr, fr.cam, ref_base, ref_pyr_bytes, cur_base + (size_t)c * cur_pyr_bytes, c * cap + n_c, level, recs, pwb_t, n_pad, blockIdx.x);
 }
 
+// The same over the cameras a list names (a tracker group's subset call): slice j of the grid -- cap / 16 blocks -- takes camera
+// c = cam_list[j], whose records, counters row and current image lie where c puts them; `eb` is the block's index in the
+// all-cameras layout, which is what the records and the transposed patches are addressed by.
+__global__ __launch_bounds__(256, 7) void df_search_listed_kernel(
+    DfFrame fr, const uint8_t* __restrict__ ref_base, size_t ref_pyr_bytes, const uint8_t* __restrict__ cur_base, size_t cur_pyr_bytes,
+    int cap, const int* __restrict__ counters, int counter_stride, const int32_t* __restrict__ level, SeedRec* __restrict__ recs,
+    uint32_t* __restrict__ pwb_t, int n_pad, const int* __restrict__ cam_list) {
+  const int per_cam = cap / SEEDS_PER_BLOCK;
+  const int j = (int)blockIdx.x / per_cam;
+  const int c = cam_list[j];
+  const int eb = c * per_cam + ((int)blockIdx.x - j * per_cam);
+  int n_c = counters[(size_t)c * counter_stride];
+  n_c = n_c < cap ? n_c : cap;
+  df_search_block(fr, fr.cam, ref_base, ref_pyr_bytes, cur_base + (size_t)c * cur_pyr_bytes, c * cap + n_c, level, recs, pwb_t, n_pad, eb);
+}
+
 // ---- the warp / search stage over the batches of several cameras (svo_hip_seed_batch_update_cameras_async): the 16 records of a
 // block lie inside ONE job of the device-resident table (job boundaries are multiples of 256 records); the job names the slot
 // of its camera's current image, the end of its records and its camera's model in the pass's camera table.

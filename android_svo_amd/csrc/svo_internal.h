@@ -153,6 +153,11 @@ inline int svo_ctx_host_staging(svo_hip_ctx* ctx, size_t need, char** out) {
 }
 
 int svo_pyramid_build_levels(svo_hip_pyramid* pyr, int first_slot, int n_slots, const uint8_t* level0_mapped, size_t mapped_stride);    // levels 1.. from level 0 (svo_ctx.hip)
+// the same for a list of slots (the same n_slots entries in host and in device memory): slot s from level0_mapped + s * mapped_stride
+int svo_pyramid_build_slots(svo_hip_pyramid* pyr, int n_slots, const int* slots_host, const int* slots_dev, const uint8_t* level0_mapped,
+                            size_t mapped_stride);
+// the listed slots of src copied to the same slots of dst (two batches of one shape), one launch on the context stream
+int svo_pyramid_copy_slots(svo_hip_pyramid* dst, const svo_hip_pyramid* src, int n_slots, const int* slots_host, const int* slots_dev);
 
 inline svo_dev::Cam svo_make_cam(const svo_hip_camera& c) {
   svo_dev::Cam d;
@@ -280,6 +285,11 @@ int svo_sia_prepare_from_device(svo_hip_sia* s, int slot, const svo_hip_camera* 
 const svo_dev::FrameState* svo_sia_state_dev(const svo_hip_sia* s, int slot);
 int svo_sia_slot_arrays(svo_hip_sia* s, int slot, svo_dev::FrameConst** fc, double** px, double** f, double** pos, uint8_t** has_point, int* max_n);
 int svo_sia_note_device_slot(svo_hip_sia* s, int slot, const svo_hip_camera* cam, int n_feat_host);
+// svo_hip_sia_run over the n listed slots only (a tracker group's subset call): workgroup j of the fused kernel solves slot
+// slots[j], no other slot's record or arrays are read or written, and the kernel shape follows the listed slots alone (their
+// number, their largest feature count).  slots_host / slots_dev: the same strictly increasing list on both sides.  The fused
+// kernel with the exact arithmetic only (what a tracker's solver is pinned to): anything else is SVO_HIP_ERR_STATE.
+int svo_sia_run_slots(svo_hip_sia* s, int n, const int* slots_host, const int* slots_dev, const svo_hip_sia_params* prm);
 
 // ---- svo_sia.hip <-> svo_nlls.hip: the solver's other NLLSSolver branches (Levenberg-Marquardt, robust weights) run
 // on the streaming solver's buffers.  The view is valid between svo_hip_sia_level_begin and the next call that changes
@@ -329,7 +339,11 @@ namespace svo_dev { struct SeedRec; }
 int svo_match_scratch(svo_hip_ctx* ctx, int n_cap, svo_dev::SeedRec** recs, uint32_t** pwb_t, int* n_pad);
 int svo_match_stages_cams(svo_hip_ctx* ctx, const svo_hip_pyramid* ref, const svo_hip_pyramid* cur, const svo_hip_camera* cam, int n_cams,
                           int cap, const int* counters_dev, int counter_stride, const int32_t* level_ref_dev, svo_dev::SeedRec* recs,
-                          uint32_t* pwb_t, int n_pad, int n_pyr_levels, int align_max_iter, bool edgelets);
+                          uint32_t* pwb_t, int n_pad, int n_pyr_levels, int align_max_iter, bool edgelets, const int* cam_list_dev = nullptr,
+                          int n_listed = 0);
+// (cam_list_dev: the stages run over the n_listed cameras it names, in device memory, and over nothing of any other camera --
+// slice j of the grid takes camera cam_list_dev[j]'s counters row, current image and records, which stay where the camera's
+// index puts them)
 // svo_refine.hip: the pose refinement of a batch whose counts / poses lie n_feat_stride ints / T_stride doubles apart
 // (svo_hip_pose_optimize_batch_dev: 1 and 7).  error_multiplier2_dev: optional, frame b's error multiplier (|fx| of its
 // camera) at [b * error_multiplier2_stride] in device memory; NULL: `error_multiplier2` for every frame.
@@ -337,7 +351,10 @@ int svo_pose_optimize_batch_strided(svo_hip_ctx* ctx, int batch, int max_n, cons
                                     const double* T_f_w_dev, int T_stride, const double* f_dev, const double* pos_dev,
                                     const int32_t* level_dev, uint8_t* has_point_dev, double error_multiplier2,
                                     const double* error_multiplier2_dev, int error_multiplier2_stride,
-                                    double reproj_thresh, int n_iter, svo_hip_pose_opt_result* results_dev);
+                                    double reproj_thresh, int n_iter, svo_hip_pose_opt_result* results_dev,
+                                    const int* frame_list_dev = nullptr, int n_listed = 0);
+// (frame_list_dev: workgroup j refines frame frame_list_dev[j] of the `batch` frames, n_listed workgroups in all; the
+// frames not listed are neither read nor written -- their poses, flags and results stay as they are)
 
 // ---- multi-GPU exchange (svo_comm.hip): RCCL over xGMI, or a host-staged shared-memory transport for bring-up / tests.
 // Both all-reduce in place on the communicator's context stream and give every rank bitwise the same result.

@@ -232,13 +232,14 @@ __device__ __noinline__ void se3_exp_cold(const double* l, double* out) { se3_ex
 
 // EM_PER_FRAME: frame b's error multiplier is em_dev[b * em_stride] (the cameras of a rig each have their own |fx|); else
 // `em_all` for every frame, and the kernel is the one it was.
-template <bool EM_PER_FRAME>
+// LISTED: workgroup j refines frame frame_list[j] (a tracker group's subset call); every array stays indexed by the frame.
+template <bool EM_PER_FRAME, bool LISTED = false>
 __global__ __launch_bounds__(PR_THREADS) void pose_refine_kernel(
     int max_n, const int* __restrict__ n_feat, const double* __restrict__ T_in, const double* __restrict__ f,
     const double* __restrict__ pos, const int* __restrict__ level, uint8_t* __restrict__ has_point, double em_all,
     double reproj_thresh, int n_iter, float* __restrict__ err_ws, double* __restrict__ sq_init_ws,
     double* __restrict__ sq_final_ws, PoseOptOut* __restrict__ out, int n_feat_stride, int T_stride,
-    const double* __restrict__ em_dev, int em_stride) {
+    const double* __restrict__ em_dev, int em_stride, const int* __restrict__ frame_list = nullptr) {
   __shared__ int hist[256];
   __shared__ __attribute__((aligned(16))) unsigned long long s_keys[2][PR_THREADS];
   __shared__ unsigned s_cnt[4][PR_THREADS];
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(PR_THREADS) void pose_refine_kernel(
   __shared__ int s_done, s_iters;
   __shared__ unsigned s_count;
 
-  const int b = blockIdx.x;
+  const int b = LISTED ? frame_list[blockIdx.x] : (int)blockIdx.x;
   const double em = EM_PER_FRAME ? em_dev[(size_t)b * em_stride] : em_all;
   const int n = n_feat[(size_t)b * n_feat_stride];      // (strides: a tracker group reads the counts / poses where its other kernels left them)
   const size_t base = (size_t)b * max_n;
@@ -575,9 +576,11 @@ int svo_pose_optimize_batch_strided(svo_hip_ctx* ctx, int batch, int max_n, cons
                                     const double* T_f_w_dev, int T_stride, const double* f_dev, const double* pos_dev,
                                     const int32_t* level_dev, uint8_t* has_point_dev, double error_multiplier2,
                                     const double* error_multiplier2_dev, int error_multiplier2_stride,
-                                    double reproj_thresh, int n_iter, svo_hip_pose_opt_result* results_dev) {
+                                    double reproj_thresh, int n_iter, svo_hip_pose_opt_result* results_dev,
+                                    const int* frame_list_dev, int n_listed) {
   if (!ctx) return SVO_HIP_ERR_INVALID;
   SVO_REQUIRE(ctx, batch > 0 && max_n > 0 && n_iter >= 0 && n_feat_stride >= 1 && T_stride >= 7);
+  SVO_REQUIRE(ctx, !frame_list_dev || (n_listed >= 1 && n_listed <= batch));
   SVO_REQUIRE(ctx, n_feat_dev && T_f_w_dev && f_dev && pos_dev && level_dev && has_point_dev && results_dev);
   SVO_REQUIRE(ctx, error_multiplier2_dev ? error_multiplier2_stride >= 1 : error_multiplier2 > 0.0);
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
@@ -588,10 +591,12 @@ int svo_pose_optimize_batch_strided(svo_hip_ctx* ctx, int batch, int max_n, cons
   double* sq_init = reinterpret_cast<double*>(ws);
   double* sq_final = sq_init + per;
   float* err = reinterpret_cast<float*>(sq_final + per);
-  auto* kernel = error_multiplier2_dev ? pose_refine_kernel<true> : pose_refine_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3(batch), dim3(PR_THREADS), 0, ctx->stream, max_n, n_feat_dev, T_f_w_dev, f_dev,
+  auto* kernel = frame_list_dev ? (error_multiplier2_dev ? pose_refine_kernel<true, true> : pose_refine_kernel<false, true>)
+                                : (error_multiplier2_dev ? pose_refine_kernel<true> : pose_refine_kernel<false>);
+  hipLaunchKernelGGL(kernel, dim3(frame_list_dev ? n_listed : batch), dim3(PR_THREADS), 0, ctx->stream, max_n, n_feat_dev, T_f_w_dev, f_dev,
                      pos_dev, level_dev, has_point_dev, error_multiplier2, reproj_thresh, n_iter, err, sq_init, sq_final,
-                     reinterpret_cast<PoseOptOut*>(results_dev), n_feat_stride, T_stride, error_multiplier2_dev, error_multiplier2_stride);
+                     reinterpret_cast<PoseOptOut*>(results_dev), n_feat_stride, T_stride, error_multiplier2_dev, error_multiplier2_stride,
+                     frame_list_dev);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   return SVO_HIP_OK;
 }

@@ -901,13 +901,15 @@ SVO_DEV void fused_interp_W(const uint2* F, float w_tl, float w_tr, float w_bl, 
 // that describes the launch (NW, TPW, CK, tiles_young, n_extra, the slot): a tile this frame does not have contributes a
 // row of +0.0, and x + (+0.0) is x bit for bit once the chain has left its initial +0.0 (it can never return to -0.0).
 // The default instances (TORD = false) carry none of this.
-template <int NW, int TPW, int CK, int VARIANT, bool TORD>
+// MAPPED (svo_sia_run_slots: a tracker group's subset call): workgroup j solves slot slot_map[j].  The slot is the one place
+// the workgroup's index enters -- every record and array below is addressed by it -- so the other instances are what they were.
+template <int NW, int TPW, int CK, int VARIANT, bool TORD, bool MAPPED = false>
 __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
     const FrameConst* __restrict__ fc, FrameState* __restrict__ st, const uint8_t* __restrict__ ref_base,
     const uint8_t* __restrict__ cur_base, size_t pyr_bytes, FusedLevels lv, int max_n, const double* __restrict__ px,
     const double* __restrict__ f, const double* __restrict__ pos, const uint8_t* __restrict__ has_point,
     double4* __restrict__ sxyz, double* __restrict__ tile_h, float4* __restrict__ wmem, int max_tiles, FusedParams prm,
-    int tiles_young, int n_extra) {
+    int tiles_young, int n_extra, const int* __restrict__ slot_map = nullptr) {
   using Plan = FusedPlan<TPW, CK>;
   // the LDS left over holds one more tile -- the first one the plan keeps in memory -- for the first n_extra waves
   // (kernels whose waves own five or six tiles are register-bound: for them the extra LDS slot and the deferred
@@ -961,7 +963,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
   if (threadIdx.x == 0) { for (int i = 3; i < 9; ++i) s_stamp[i] = 0; }
 #endif
 
-  const int b = blockIdx.x;
+  const int b = MAPPED ? slot_map[blockIdx.x] : (int)blockIdx.x;
   const FrameConst& c = fc[b];
   LeanCam cam;
   cam.fx = c.cam.fx; cam.fy = c.cam.fy; cam.cx = c.cam.cx; cam.cy = c.cam.cy;
@@ -1850,6 +1852,7 @@ struct svo_hip_sia {
   int batch = 0, max_n = 0;
   const svo_hip_pyramid* ref = nullptr;
   const svo_hip_pyramid* cur = nullptr;
+  const int* run_slots_dev = nullptr;       // svo_sia_run_slots: the list in device memory, for the duration of that call
   // device buffers
   FrameConst* fc = nullptr;
   FrameState* st = nullptr;                 // the frames' Gauss-Newton state (home buffer: results are read from here)
@@ -1954,12 +1957,12 @@ int flush_fc(svo_hip_sia* s) {
   return SVO_HIP_OK;
 }
 
-// One launch of the fused kernel over slots [0, n_launch).
-template <int NW, int TPW, int CK, int VARIANT, bool TORD>
+// One launch of the fused kernel over slots [0, n_launch), or (MAPPED) over the n_launch slots of s->run_slots_dev.
+template <int NW, int TPW, int CK, int VARIANT, bool TORD, bool MAPPED>
 int launch_fused_x(svo_hip_sia* s, int n_launch, const svo_hip_sia_params* prm, size_t lds_bytes, int tiles_young, int n_extra = 0) {
   svo_hip_ctx* ctx = s->ctx;
   // > 64 KiB of dynamic LDS has to be allowed explicitly (per device: set it on every launch, it is cheap)
-  SVO_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&sia_fused_kernel<NW, TPW, CK, VARIANT, TORD>),
+  SVO_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&sia_fused_kernel<NW, TPW, CK, VARIANT, TORD, MAPPED>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   FusedLevels lv;
   memset(&lv, 0, sizeof(lv));
@@ -1971,9 +1974,9 @@ int launch_fused_x(svo_hip_sia* s, int n_launch, const svo_hip_sia_params* prm, 
   fp.max_level = prm->max_level; fp.min_level = prm->min_level; fp.n_iter = prm->n_iter;
   fp.early_stop = prm->early_stop; fp.eps = prm->eps;
   fp.moments_f32 = s->opt_arith == SVO_HIP_SIA_ARITH_MOMENTS_F32 ? 1 : 0;
-  hipLaunchKernelGGL((sia_fused_kernel<NW, TPW, CK, VARIANT, TORD>), dim3(n_launch), dim3(NW * 64), lds_bytes, ctx->stream, s->fc, s->st,
+  hipLaunchKernelGGL((sia_fused_kernel<NW, TPW, CK, VARIANT, TORD, MAPPED>), dim3(n_launch), dim3(NW * 64), lds_bytes, ctx->stream, s->fc, s->st,
                      s->ref->base, s->cur->base, s->ref->pyr_bytes, lv, s->max_n, s->px, s->f, s->pos, s->has_point, s->sxyz, s->tile_h,
-                     s->wmem, s->max_tiles, fp, tiles_young, n_extra);
+                     s->wmem, s->max_tiles, fp, tiles_young, n_extra, MAPPED ? s->run_slots_dev : (const int*)nullptr);
   SVO_CHECK_HIP(ctx, hipGetLastError());
   return SVO_HIP_OK;
 }
@@ -2016,7 +2019,7 @@ int fused_old_share(const svo_hip_sia* s, int max_n, int* per_simd_out) {
 }
 
 // The shape of the fused kernel for a launch of n_launch pairs whose largest frame has max_n patches.
-template <int VARIANT, bool TORD = false>
+template <int VARIANT, bool TORD = false, bool MAPPED = false>
 int launch_fused_shape(svo_hip_sia* s, int n_launch, int max_n, const svo_hip_sia_params* prm) {
   svo_hip_ctx* ctx = s->ctx;
   int per_simd = 1;
@@ -2030,10 +2033,10 @@ int launch_fused_shape(svo_hip_sia* s, int n_launch, int max_n, const svo_hip_si
   if (four) {
     const size_t lds4 = (size_t)4 * (per_simd < 2 ? 1 : 2) * FUSED_WC_BYTES;
     switch (per_simd) {                                                // tiles per wave (3 runs as 4 with an empty slot)
-      case 1: return launch_fused_x<4, 1, 1, VARIANT, TORD>(s, n_launch, prm, lds4, 0);
-      case 2: return launch_fused_x<4, 2, 2, VARIANT, TORD>(s, n_launch, prm, lds4, 0);
+      case 1: return launch_fused_x<4, 1, 1, VARIANT, TORD, MAPPED>(s, n_launch, prm, lds4, 0);
+      case 2: return launch_fused_x<4, 2, 2, VARIANT, TORD, MAPPED>(s, n_launch, prm, lds4, 0);
       case 3:
-      case 4: return launch_fused_x<4, 4, 2, VARIANT, TORD>(s, n_launch, prm, lds4, 0);
+      case 4: return launch_fused_x<4, 4, 2, VARIANT, TORD, MAPPED>(s, n_launch, prm, lds4, 0);
       default: break;
     }
   }
@@ -2046,12 +2049,12 @@ int launch_fused_shape(svo_hip_sia* s, int n_launch, int max_n, const svo_hip_si
   if (n_extra < 0 || n_extra > (tpw > ck ? fused_extra_tiles(tpw, ck, TORD) : 0)) n_extra = 0;
   const size_t lds = (size_t)(FUSED_WAVES * ck + n_extra) * FUSED_WC_BYTES;
   switch (tpw) {                 // tiles of an older wave
-    case 1: return launch_fused_x<8, 1, 1, VARIANT, TORD>(s, n_launch, prm, lds, ty);
-    case 2: return launch_fused_x<8, 2, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty);
-    case 3: return launch_fused_x<8, 3, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty, n_extra);
-    case 4: return launch_fused_x<8, 4, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty, n_extra);
-    case 5: return launch_fused_x<8, 5, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty, n_extra);
-    case 6: return launch_fused_x<8, 6, 2, VARIANT, TORD>(s, n_launch, prm, lds, ty, n_extra);
+    case 1: return launch_fused_x<8, 1, 1, VARIANT, TORD, MAPPED>(s, n_launch, prm, lds, ty);
+    case 2: return launch_fused_x<8, 2, 2, VARIANT, TORD, MAPPED>(s, n_launch, prm, lds, ty);
+    case 3: return launch_fused_x<8, 3, 2, VARIANT, TORD, MAPPED>(s, n_launch, prm, lds, ty, n_extra);
+    case 4: return launch_fused_x<8, 4, 2, VARIANT, TORD, MAPPED>(s, n_launch, prm, lds, ty, n_extra);
+    case 5: return launch_fused_x<8, 5, 2, VARIANT, TORD, MAPPED>(s, n_launch, prm, lds, ty, n_extra);
+    case 6: return launch_fused_x<8, 6, 2, VARIANT, TORD, MAPPED>(s, n_launch, prm, lds, ty, n_extra);
     default: break;
   }
   return svo_fail(ctx, SVO_HIP_ERR_INVALID, "fused SparseImgAlign", "unsupported tiles-per-wave");
@@ -2080,7 +2083,8 @@ bool fused_applies(const svo_hip_sia* s, int n_slots) {
 // slower beside it than alone -- 1.58 ms against 0.45 ms, two different kernels evicting each other from the
 // instruction cache their CUs share -- and so made the step 31-37 % longer.  The per-workgroup branch costs a mixed
 // batch 1.4 % in fixed-work mode and 3 % with the reference's exits, and a pure batch nothing.)
-int run_fused(svo_hip_sia* s, int n_slots, const svo_hip_sia_params* prm) {
+// (slots: the launch covers the n_slots slots it lists -- s->run_slots_dev holds the same list -- not [0, n_slots))
+int run_fused(svo_hip_sia* s, int n_slots, const svo_hip_sia_params* prm, const int* slots = nullptr) {
   svo_hip_ctx* ctx = s->ctx;
   SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
   SVO_REQUIRE(ctx, s->ref && s->cur);
@@ -2095,14 +2099,18 @@ int run_fused(svo_hip_sia* s, int n_slots, const svo_hip_sia_params* prm) {
   bool tiny = false;
   int max_n = 0;
   for (int i = 0; i < n_slots; ++i) {
-    const int n = s->h_fc[i].n_feat;
+    const int n = s->h_fc[slots ? slots[i] : i].n_feat;
     tiny = tiny || (n > 0 && n < FUSED_EXACT_ROW_BELOW);
     if (n > max_n) max_n = n;
   }
   hipEvent_t* ev = next_events(s, s->ev_res, s->ev_res_used);
   if (ev) (void)hipEventRecord(ev[0], ctx->stream);
   // (the fast arithmetic is an option of the plain instance: a batch with a tiny frame runs with exact or f32 moments, as set)
-  if (s->opt_reduction == SVO_HIP_SIA_REDUCTION_TILE_ORDER)     // exact arithmetic only (svo_hip_sia_run has refused the others)
+  if (slots)                                                    // exact arithmetic only (svo_sia_run_slots has refused the others)
+    rc = s->opt_reduction == SVO_HIP_SIA_REDUCTION_TILE_ORDER
+             ? (tiny ? launch_fused_shape<FUSED_EXACT_ROWS, true, true>(s, n_slots, max_n, prm) : launch_fused_shape<FUSED_PLAIN, true, true>(s, n_slots, max_n, prm))
+             : (tiny ? launch_fused_shape<FUSED_EXACT_ROWS, false, true>(s, n_slots, max_n, prm) : launch_fused_shape<FUSED_PLAIN, false, true>(s, n_slots, max_n, prm));
+  else if (s->opt_reduction == SVO_HIP_SIA_REDUCTION_TILE_ORDER)     // exact arithmetic only (svo_hip_sia_run has refused the others)
     rc = tiny ? launch_fused_shape<FUSED_EXACT_ROWS, true>(s, n_slots, max_n, prm) : launch_fused_shape<FUSED_PLAIN, true>(s, n_slots, max_n, prm);
   else
     rc = tiny ? launch_fused_shape<FUSED_EXACT_ROWS>(s, n_slots, max_n, prm)
@@ -2132,6 +2140,25 @@ int svo_sia_prepare_from_device(svo_hip_sia* s, int slot, const svo_hip_camera* 
   s->h_fc[slot].cam = svo_make_cam(*cam);
   s->fc_dirty = false;
   return SVO_HIP_OK;
+}
+
+int svo_sia_run_slots(svo_hip_sia* s, int n, const int* slots_host, const int* slots_dev, const svo_hip_sia_params* prm) {
+  if (!s || !prm || !slots_host || !slots_dev) return SVO_HIP_ERR_INVALID;
+  svo_hip_ctx* ctx = s->ctx;
+  SVO_REQUIRE(ctx, n >= 1 && n <= s->batch);
+  int max_n = 0;
+  for (int i = 0; i < n; ++i) {
+    SVO_REQUIRE(ctx, slots_host[i] >= 0 && slots_host[i] < s->batch && (i == 0 || slots_host[i] > slots_host[i - 1]));
+    if (s->h_fc[slots_host[i]].n_feat > max_n) max_n = s->h_fc[slots_host[i]].n_feat;
+  }
+  // the mapped instances are the fused kernel's exact-arithmetic ones: whatever would take another path is refused
+  if (nlls_branches(s) || s->opt_arith != SVO_HIP_SIA_ARITH_EXACT || s->opt_mode == SVO_HIP_SIA_MODE_STREAM || s->shard_world != 1 ||
+      (max_n + TILE - 1) / TILE > FUSED_MAX_TILES)
+    return svo_fail(ctx, SVO_HIP_ERR_STATE, "svo_sia_run_slots", "a list of slots runs through the fused kernel with the exact arithmetic only");
+  s->run_slots_dev = slots_dev;
+  const int rc = run_fused(s, n, prm, slots_host);
+  s->run_slots_dev = nullptr;
+  return rc;
 }
 
 const svo_dev::FrameState* svo_sia_state_dev(const svo_hip_sia* s, int slot) { return s ? s->st + slot : nullptr; }

@@ -109,6 +109,10 @@ struct svo_hip_tracker_shared {
   TrkCamArgs* args_host = nullptr;          // page-locked: the bytes of the last upload
   TrkCamArgs* args_dev = nullptr;
   bool args_valid = false;                  // args_dev holds args_host
+  // svo_hip_tracker_group_track_some: [0, n_cams) the cameras of the call, [n_cams, 2 n_cams) the ones that sit it out; sent with
+  // every such call (the previous call's kernels are through with both copies: the host waited for them)
+  int* list_host = nullptr;                 // page-locked
+  int* list_dev = nullptr;
   TrkFinishReq* fin_host = nullptr;         // page-locked, mapped: the cameras' requests of svo_hip_tracker_group_finish_frames
   TrkFinishReq* fin_dev = nullptr;
   unsigned long long seq = 0;               // frames tracked: the hand-over kernel stores it behind every camera's block (o_flag)
@@ -339,6 +343,7 @@ static void trk_shared_destroy(svo_hip_tracker_shared* sh) {
   if (sh->img_host) (void)hipHostFree(sh->img_host);
   if (sh->args_host) (void)hipHostFree(sh->args_host);
   if (sh->fin_host) (void)hipHostFree(sh->fin_host);
+  if (sh->list_host) (void)hipHostFree(sh->list_host);
   delete sh;
 }
 
@@ -399,6 +404,8 @@ static int trk_shared_create(svo_hip_ctx* ctx, const svo_hip_camera* cam, const 
   if (rc == SVO_HIP_OK && hipHostGetDevicePointer((void**)&sh->img_dev, sh->img_host, 0) != hipSuccess) rc = SVO_HIP_ERR_DEVICE;
   if (rc == SVO_HIP_OK && hipHostMalloc((void**)&sh->args_host, N * sizeof(TrkCamArgs), hipHostMallocDefault) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
   D(&sh->args_dev, N);
+  if (rc == SVO_HIP_OK && hipHostMalloc((void**)&sh->list_host, 2 * N * sizeof(int), hipHostMallocDefault) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
+  D(&sh->list_dev, 2 * N);
   if (rc == SVO_HIP_OK && hipHostMalloc((void**)&sh->fin_host, N * sizeof(TrkFinishReq), hipHostMallocMapped) != hipSuccess) rc = SVO_HIP_ERR_NOMEM;
   if (rc == SVO_HIP_OK && hipHostGetDevicePointer((void**)&sh->fin_dev, sh->fin_host, 0) != hipSuccess) rc = SVO_HIP_ERR_DEVICE;
   if (rc == SVO_HIP_OK) { sh->args_next.resize(N); sh->waits.resize(N); }
@@ -774,6 +781,106 @@ static int trk_track_all(svo_hip_tracker_shared* sh, const uint8_t* const* level
   return SVO_HIP_OK;
 }
 
+// One frame for the n cameras cam[0..n) of the shared part (strictly increasing, in range, 0 < n < n_cams: the caller has checked);
+// level0[j]: camera cam[j]'s new image.  The chain of trk_track_all with every stage launched n cameras wide: workgroup j, or
+// slice j of a grid, takes camera cam[j] from the list in device memory, and no stage reads or writes anything of a camera that
+// is not listed -- its counters row still holds its own last frame's counts, which the keyframe decision reads.
+// The two frame batches: the new pyramids are built in the batch that is not the last frames'.  When at least half of the cameras
+// track, the batches change roles as always and the pyramids of the cameras that sit out are copied forward (one launch);
+// otherwise they keep their roles and the new pyramids are copied back behind the alignment and the matching, which read them.
+// Either way every camera's last frame lies in frame_pyr[last_idx] afterwards, and the smaller side is what gets copied.
+static int trk_track_some(svo_hip_tracker_shared* sh, int n, const int32_t* cam, const uint8_t* const* level0, const char* who) {
+  svo_hip_ctx* ctx = sh->ctx;
+  const int N = sh->n_cams;
+  svo_hip_tracker* t0 = sh->members[0];
+  const svo_hip_tracker_config& c = t0->cfg;
+  for (int j = 0; j < n; ++j) {
+    const svo_hip_tracker* t = sh->members[(size_t)cam[j]];
+    if (!t->have_map || !t->have_last)
+      return svo_fail(ctx, SVO_HIP_ERR_STATE, who, "svo_hip_tracker_set_map and svo_hip_tracker_set_last_frame come first (every camera of the call)");
+  }
+  SVO_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  int* act = sh->list_host;
+  int* rest = sh->list_host + N;
+  int n_rest = 0;
+  for (int k = 0, j = 0; k < N; ++k) {
+    if (j < n && cam[j] == k) act[j++] = k;
+    else rest[n_rest++] = k;
+  }
+  const int* act_dev = sh->list_dev;
+  const int* rest_dev = sh->list_dev + N;
+  const size_t l0 = (size_t)t0->cam.width * t0->cam.height;
+  for (int j = 0; j < n; ++j) {
+    svo_hip_tracker* t = sh->members[(size_t)act[j]];
+    t->frame_begins();
+    if (level0[j] != reinterpret_cast<const uint8_t*>(t->img_host)) memcpy(t->img_host, level0[j], l0);
+  }
+  // a failure from the first enqueue on: the stream is through with the list and the images before the call returns, and whatever
+  // the half-run chain left in the solver's slots is gathered again
+  auto fail = [&](int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    for (int j = 0; j < n; ++j) sh->members[(size_t)act[j]]->call_failed();
+    return rc;
+  };
+  if (hipMemcpyAsync(sh->list_dev, sh->list_host, 2 * (size_t)N * sizeof(int), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    return fail(svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "upload of the camera list failed"));
+  svo_hip_pyramid* ref = sh->frame_pyr[sh->last_idx];
+  svo_hip_pyramid* cur = sh->frame_pyr[1 - sh->last_idx];
+  const bool flip = 2 * n >= N;
+  int rc = svo_pyramid_build_slots(cur, n, act, act_dev, sh->img_dev, sh->img_stride);
+  if (rc == SVO_HIP_OK && flip) rc = svo_pyramid_copy_slots(cur, ref, n_rest, rest, rest_dev);
+  if (rc == SVO_HIP_OK) rc = svo_hip_sia_set_frames(sh->sia, ref, cur);
+  bool any_edgelet = false;
+  for (int j = 0; j < n && rc == SVO_HIP_OK; ++j) {
+    svo_hip_tracker* t = sh->members[(size_t)act[j]];
+    if (t->need_gather) rc = svo_sia_prepare_from_device(sh->sia, act[j], &t->cam, t->last_n_host, t->last.n, t->last.T_f_w, t->last.px, t->last.f, t->last.point, t->pt_pos);
+    else rc = svo_sia_note_device_slot(sh->sia, act[j], &t->cam, t->last_n_host);
+  }
+  const svo_hip_sia_params sp = trk_sia_params(c);
+  if (rc == SVO_HIP_OK) rc = svo_sia_run_slots(sh->sia, n, act, act_dev, &sp);
+  // (a re-selection owed by a camera that sits out stays owed)
+  for (int j = 0; j < n && rc == SVO_HIP_OK; ++j) {
+    svo_hip_tracker* t = sh->members[(size_t)act[j]];
+    rc = trk_rekey_now(t);
+    any_edgelet = any_edgelet || t->any_edgelet;
+  }
+  SeedRec* recs = nullptr; uint32_t* pwb_t = nullptr; int n_pad = 0;
+  const int stride = sh->rec_stride;
+  if (rc == SVO_HIP_OK) rc = svo_match_scratch(ctx, N * stride, &recs, &pwb_t, &n_pad);     // (every camera keeps its own part: the table stays as it is)
+  if (rc == SVO_HIP_OK) rc = trk_args_table(sh, recs);
+  if (rc != SVO_HIP_OK) return fail(rc);
+  const TrkCamArgs* ad = sh->args_dev;
+  hipLaunchKernelGGL(trk_plan_listed_kernel, dim3(n), dim3(TRK_THREADS), 0, ctx->stream, ad, act_dev);
+  if (hipGetLastError() != hipSuccess) return fail(svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "launch failed"));
+  rc = svo_match_stages_cams(ctx, sh->kf_pyr, cur, &t0->cam, N, stride, sh->counters, 8, sh->cand_level_ref, recs, pwb_t, n_pad, c.n_pyr_levels,
+                             c.align_max_iter, any_edgelet, act_dev, n);
+  if (rc != SVO_HIP_OK) return fail(rc);
+  hipLaunchKernelGGL(trk_replay_listed_kernel, dim3(n), dim3(TRK_THREADS), 0, ctx->stream, ad, act_dev, c.max_fts, c.quality_min_fts);
+  if (hipGetLastError() != hipSuccess) return fail(svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "launch failed"));
+  const FrameState* st0 = svo_sia_state_dev(sh->sia, 0);
+  rc = svo_pose_optimize_batch_strided(ctx, N, c.max_frame_features, sh->counters + 5, 8, st0->T_cur_w, (int)(sizeof(FrameState) / sizeof(double)),
+                                       sh->ft_f, sh->ft_pos, sh->ft_level, sh->ft_has_point, fabs(t0->cam.fx), sh->err_mult, 1,
+                                       c.pose_optim_thresh, c.pose_optim_num_iter, sh->po, act_dev, n);
+  if (rc == SVO_HIP_OK && !flip) rc = svo_pyramid_copy_slots(ref, cur, n, act, act_dev);
+  if (rc != SVO_HIP_OK) return fail(rc);
+  const unsigned long long seq = ++sh->seq;
+  hipLaunchKernelGGL(trk_finish_listed_kernel, dim3(n), dim3(256), 0, ctx->stream, ad, act_dev, seq);
+  if (hipGetLastError() != hipSuccess) return fail(svo_fail(ctx, SVO_HIP_ERR_DEVICE, who, "launch failed"));
+  // the one synchronisation: the sequence number of the cameras of the call (the others keep an older one)
+  for (int j = 0; j < n; ++j) {
+    const svo_hip_tracker* t = sh->members[(size_t)act[j]];
+    sh->waits[(size_t)j] = {t->res_host + t->o_flag, seq};
+  }
+  rc = trk_wait_flags(ctx, sh->waits.data(), n, who, "the frame's kernels did not complete");
+  if (rc != SVO_HIP_OK) return fail(rc);
+  if (flip) sh->last_idx = 1 - sh->last_idx;
+  for (int j = 0; j < n; ++j) {
+    svo_hip_tracker* t = sh->members[(size_t)act[j]];
+    t->frame_tracked(*reinterpret_cast<const svo_hip_track_result*>(t->res_host));
+  }
+  return SVO_HIP_OK;
+}
+
 int svo_hip_tracker_track(svo_hip_tracker* t, const uint8_t* level0, svo_hip_track_result* result, double* feat_px, double* feat_f,
                           int32_t* feat_level, int32_t* feat_point, uint8_t* feat_edgelet, double* feat_grad, int32_t* pt_type,
                           int32_t* pt_n_failed, int32_t* pt_n_succeeded) {
@@ -867,6 +974,28 @@ int svo_hip_tracker_group_track(svo_hip_tracker_group* g, const uint8_t* const* 
   const int rc = trk_track_all(g->sh, level0, "svo_hip_tracker_group_track");
   if (rc != SVO_HIP_OK) return rc;
   if (results) for (int k = 0; k < g->sh->n_cams; ++k) trk_copy_out(g->sh->members[(size_t)k], results + k, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return SVO_HIP_OK;
+}
+
+int svo_hip_tracker_group_track_some(svo_hip_tracker_group* g, int n_active, const int32_t* camera, const uint8_t* const* level0,
+                                     svo_hip_track_result* results) {
+  if (!g || !g->sh) return SVO_HIP_ERR_INVALID;
+  svo_hip_tracker_shared* sh = g->sh;
+  svo_hip_ctx* ctx = sh->ctx;
+  const char* who = "svo_hip_tracker_group_track_some";
+  const int N = sh->n_cams;
+  // every refusal before anything is enqueued or changed
+  SVO_REQUIRE(ctx, n_active >= 0 && n_active <= N);
+  if (n_active == 0) return SVO_HIP_OK;
+  SVO_REQUIRE(ctx, camera != nullptr && level0 != nullptr);
+  for (int j = 0; j < n_active; ++j)
+    SVO_REQUIRE(ctx, camera[j] >= 0 && camera[j] < N && (j == 0 || camera[j] > camera[j - 1]) && level0[j] != nullptr);
+  // every camera (the list can only be the identity then): svo_hip_tracker_group_track's own launches
+  const int rc = n_active == N ? trk_track_all(sh, level0, who) : trk_track_some(sh, n_active, camera, level0, who);
+  if (rc != SVO_HIP_OK) return rc;
+  if (results)
+    for (int j = 0; j < n_active; ++j)
+      trk_copy_out(sh->members[(size_t)camera[j]], results + j, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   return SVO_HIP_OK;
 }
 

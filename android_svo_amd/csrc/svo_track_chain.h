@@ -471,6 +471,17 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_replay_cams_kernel(const TrkC
 __global__ __launch_bounds__(256) void trk_finish_cams_kernel(const TrkCamArgs* __restrict__ args, unsigned long long seq) {
   trk_finish_args(args[blockIdx.x], seq);
 }
+// ... over the cameras a list names (svo_hip_tracker_group_track_some): workgroup j takes camera cams[j]'s entry of the table ...
+__global__ __launch_bounds__(TRK_THREADS) void trk_plan_listed_kernel(const TrkCamArgs* __restrict__ args, const int* __restrict__ cams) {
+  trk_plan_args(args[cams[blockIdx.x]]);
+}
+__global__ __launch_bounds__(TRK_THREADS) void trk_replay_listed_kernel(const TrkCamArgs* __restrict__ args, const int* __restrict__ cams, int max_fts,
+                                                                        int quality_min_fts) {
+  trk_replay_args(args[cams[blockIdx.x]], max_fts, quality_min_fts);
+}
+__global__ __launch_bounds__(256) void trk_finish_listed_kernel(const TrkCamArgs* __restrict__ args, const int* __restrict__ cams, unsigned long long seq) {
+  trk_finish_args(args[cams[blockIdx.x]], seq);
+}
 // ... and the same for a lone tracker with its one entry passed by value, not uploaded: the pointers inside a by-value kernel
 // argument address global memory by the ABI, those read from the table are generic pointers, and every memory access of the
 // bodies becomes a flat instruction (measured: the lone chain 3 us a frame slower through the table kernels)

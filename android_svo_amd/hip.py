@@ -1423,6 +1423,29 @@ class TrackerGroup:
             t._tracked_n_points = t.n_points
         return [self._res[c] for c in range(self.n)]
 
+    def track_some(self, cameras, imgs) -> list:
+        """svo_hip_tracker_group_track_some: one frame of the cameras listed (strictly increasing indices), imgs[j] the image of
+        cameras[j]; the other cameras sit the call out untouched.  Nothing is checked here -- the library refuses a bad list or a
+        missing image (None) itself.  Returns the CTrackResult records of the cameras listed, in list order."""
+        cams = [int(c) for c in cameras]
+        n = len(cams)
+        assert len(imgs) == n
+        idx = (C.c_int32 * max(n, 1))(*cams)
+        ptrs = (C.POINTER(C.c_uint8) * max(n, 1))()
+        res = (CTrackResult * max(n, 1))()
+        keep = []
+        for j in range(n):
+            if imgs[j] is None:
+                continue                       # (a null pointer: the call is refused)
+            im = np.ascontiguousarray(imgs[j], dtype=np.uint8)
+            assert im.shape == (self.cam.height, self.cam.width)
+            keep.append(im)
+            ptrs[j] = im.ctypes.data_as(C.POINTER(C.c_uint8))
+        self.ctx.check(self.ctx.lib.svo_hip_tracker_group_track_some(self.h, n, idx, ptrs, res), "tracker_group_track_some")
+        for c in cams:
+            self.cameras[c]._tracked_n_points = self.cameras[c].n_points
+        return [res[j] for j in range(n)]
+
     def finish_frames(self, requests=None, kf_select_min_dist: float = 0.12) -> list:
         """svo_hip_tracker_group_finish_frames: Tracker.finish_frame for every camera in one launch with one wait.
         requests[c]: None / a list of point indices / (points, n_iter) for camera c (requests = None: no structure step anywhere).

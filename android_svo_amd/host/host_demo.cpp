@@ -12,6 +12,9 @@
 //                                                   <out_dir>/g<w>/, each equal to `track` on <case_dir>/cam<w>
 //        svo_host_demo <case_dir> <out_dir> keyframes [device_seeds] [threaded]   keyframes whose seeds the filter detects and creates
 //                                                   on the device, or (without device_seeds) are detected by the caller and handed in
+//        svo_host_demo <case_dir> <out_dir> trackgroup n staggered   the worlds of the group do not advance together: world w takes part in
+//                                                   every (w + 1)-th call of the group (FrameTrackerGroup::trackSome, svo_hip_tracker_group_track_some)
+//                                                   and sits the others out; the same outputs as trackgroup, and group_schedule.bin
 //        svo_host_demo <case_dir> <out_dir> filtergroup   svo::DepthFilterGroup: the depth filters of n cameras as one device pass per
 //                                                   step, and a lone DepthFilter per camera over the same frames (filter_group_demo);
 //                                                   `filtergroup rig`: every camera with the model of <case_dir>/cam<c>/camera.bin
@@ -90,6 +93,36 @@ struct GroupRendezvous {
   std::vector<Map*> maps;
   std::vector<std::vector<std::pair<FramePtr, size_t>>> overlap;
   std::vector<TrackerCamera::Outcome> out;
+  // a staggered schedule (trackgroup n staggered): the group's calls are numbered, world w takes part in call t when t is a multiple
+  // of w + 1 -- world 0 in every call, world 1 in every other one, ... -- until it has run out of frames; the cameras of a call go
+  // through FrameTrackerGroup::trackSome, the others sit it out
+  bool staggered = false;
+  unsigned long tick = 0;
+  std::vector<char> waiting, finished;                  // per world: its frame waits for its call / it has no frame left
+  std::vector<double> schedule;                         // the calls made: per call the tick and the worlds' membership (n entries of 0 / 1)
+  bool inCall(size_t w) const { return !finished[w] && tick % (w + 1) == 0; }
+  /// make every call whose worlds have all arrived (called with the mutex held, by whichever world moved last)
+  void fire() {
+    while (ok && !failed) {
+      std::vector<int> active;
+      bool all_here = true, anybody_left = false;
+      for (size_t w = 0; w < n; ++w) {
+        anybody_left = anybody_left || !finished[w];
+        if (!inCall(w)) continue;
+        active.push_back((int)w);
+        all_here = all_here && waiting[w];
+      }
+      if (!anybody_left || !all_here) return;
+      if (!active.empty()) {
+        ok = group->trackSome(active, last, cur, maps, overlap, out);
+        schedule.push_back((double)tick);
+        for (size_t w = 0; w < n; ++w) schedule.push_back(std::find(active.begin(), active.end(), (int)w) != active.end() ? 1.0 : 0.0);
+        for (int w : active) waiting[(size_t)w] = 0;
+        cv.notify_all();
+      }
+      ++tick;
+    }
+  }
 };
 struct TrackerPort {
   FrameTracker* lone = nullptr;
@@ -102,6 +135,14 @@ struct TrackerPort {
     GroupRendezvous& r = *rz;
     if (r.failed) return false;
     r.last[w] = last; r.cur[w] = cur; r.maps[w] = &map;
+    if (r.staggered) {
+      r.waiting[w] = 1;
+      r.fire();
+      r.cv.wait(*baton, [&]() { return !r.waiting[w] || r.failed || !r.ok; });
+      if (r.failed || !r.ok) return false;
+      overlap = r.overlap[w]; oc = r.out[w];
+      return true;
+    }
     const unsigned long my_gen = r.generation;
     if (++r.arrived == r.n) {
       r.ok = r.group->trackAll(r.last, r.cur, r.maps, r.overlap, r.out);
@@ -424,7 +465,8 @@ static int track_lone(const std::string& dir, const std::string& out, bool incre
 
 // n copies of the world, one svo::FrameTrackerGroup: every world's outputs must equal the lone tracker's.  rig: n worlds of their
 // own (<dir>/cam<w>), every camera with its own model (one image size, one configuration: that of cam0's manifest)
-static int track_group(const std::string& dir, const std::string& out, int n, bool rig) {
+// staggered: the worlds do not advance together (GroupRendezvous::staggered); group_schedule.bin lists the calls that were made
+static int track_group(const std::string& dir, const std::string& out, int n, bool rig, bool staggered = false) {
   auto world_dir = [&](int w) { return rig ? dir + "/cam" + std::to_string(w) : dir; };
   const std::vector<double> m = read_bin<double>(world_dir(0) + "/track_manifest.bin");
   std::vector<PinholeCamera> cams;
@@ -438,6 +480,7 @@ static int track_group(const std::string& dir, const std::string& out, int n, bo
   GroupRendezvous rz;
   rz.group = &group; rz.n = (size_t)n;
   rz.last.resize((size_t)n); rz.cur.resize((size_t)n); rz.maps.resize((size_t)n); rz.overlap.resize((size_t)n); rz.out.resize((size_t)n);
+  rz.staggered = staggered; rz.waiting.assign((size_t)n, 0); rz.finished.assign((size_t)n, 0);
   std::vector<std::string> errors((size_t)n);
   for (int w = 0; w < n; ++w) (void)::mkdir((out + "/g" + std::to_string(w)).c_str(), 0755);
   std::vector<std::thread> worlds;
@@ -448,6 +491,7 @@ static int track_group(const std::string& dir, const std::string& out, int n, bo
       port.rz = &rz; port.baton = &baton; port.w = (size_t)w;
       try {
         track_demo(world_dir(w), out + "/g" + std::to_string(w), port);
+        if (staggered) { rz.finished[(size_t)w] = 1; rz.fire(); }               // (the others no longer wait for this world)
       } catch (const std::exception& e) {
         errors[(size_t)w] = e.what();
         rz.ok = false; ++rz.failed; ++rz.generation; rz.cv.notify_all();      // let the others go (they fail at their next frame)
@@ -455,7 +499,8 @@ static int track_group(const std::string& dir, const std::string& out, int n, bo
     });
   for (std::thread& t : worlds) t.join();
   for (const std::string& e : errors) if (!e.empty()) throw std::runtime_error(e);
-  std::printf("svo_host_demo trackgroup OK (%d worlds%s)\n", n, rig ? ", a rig" : "");
+  if (staggered) write_bin(out + "/group_schedule.bin", rz.schedule);
+  std::printf("svo_host_demo trackgroup OK (%d worlds%s%s)\n", n, rig ? ", a rig" : "", staggered ? ", staggered" : "");
   return 0;
 }
 
@@ -809,11 +854,13 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n [rig]|filtergroup [rig]|churn|keyframes [device_seeds] [threaded]]\n", argv[0]); return 2; }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n [rig] [staggered]|filtergroup [rig]|churn|keyframes [device_seeds] [threaded]]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {
-      return track_group(dir, out, argc > 4 ? std::atoi(argv[4]) : 2, argc > 5 && std::string(argv[5]) == "rig");
+      bool rig = false, staggered = false;
+      for (int a = 5; a < argc; ++a) { rig = rig || std::string(argv[a]) == "rig"; staggered = staggered || std::string(argv[a]) == "staggered"; }
+      return track_group(dir, out, argc > 4 ? std::atoi(argv[4]) : 2, rig, staggered);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "svo_host_demo FAILED: %s\n", e.what());
       return 1;

@@ -750,6 +750,39 @@ class FrameTrackerGroupT {
     return true;
   }
 
+  /// one frame of the cameras `active` names (strictly increasing indices), the others sit the call out untouched:
+  /// svo_hip_tracker_group_track_some, ONE call with the list and the images in its order.  The vectors are full-size (one
+  /// entry per camera of the group): the entries of cameras not in `active` are neither read nor written -- last, fresh and
+  /// maps may hold anything there, overlap_kfs and out keep what they held (they are resized to the group's size first when
+  /// shorter).  prepare, fetch and apply run on the cameras of the call only.  Returns false on a refusal or a device error.
+  bool trackSome(const std::vector<int>& active, const std::vector<FramePtr>& last, const std::vector<FramePtr>& fresh,
+                 const std::vector<Map*>& maps, std::vector<std::vector<std::pair<FramePtr, size_t> > >& overlap_kfs, std::vector<Outcome>& out) {
+    const size_t n = cameras_.size(), m = active.size();
+    if (!group_ || last.size() != n || fresh.size() != n || maps.size() != n || m > n) return false;
+    for (size_t j = 0; j < m; ++j)
+      if (active[j] < 0 || (size_t)active[j] >= n || (j > 0 && active[j] <= active[j - 1])) return false;
+    std::vector<int32_t> cam(m);
+    std::vector<const uint8_t*> img(m, (const uint8_t*)NULL);
+    for (size_t j = 0; j < m; ++j) {
+      const size_t c = (size_t)active[j];
+      cam[j] = active[j];
+      if (!cameras_[c]->prepare(last[c], fresh[c], *maps[c], &img[j])) return false;
+    }
+    std::vector<svo_hip_track_result> res(m);
+    if (svo_hip_tracker_group_track_some(group_, (int)m, cam.data(), img.data(), res.data()) != SVO_HIP_OK) {
+      fprintf(stderr, "[svo_hip] FrameTrackerGroup::trackSome FAILED: %s\n", svo_hip_last_error(ctx_.get()));
+      return false;
+    }
+    if (overlap_kfs.size() < n) overlap_kfs.resize(n);
+    if (out.size() < n) out.resize(n);
+    for (size_t j = 0; j < m; ++j) {
+      const size_t c = (size_t)active[j];
+      if (!cameras_[c]->fetch(&res[j])) return false;
+      cameras_[c]->apply(res[j], fresh[c], *maps[c], overlap_kfs[c], out[c]);
+    }
+    return true;
+  }
+
  private:
   FrameTrackerGroupT(const FrameTrackerGroupT&);
   FrameTrackerGroupT& operator=(const FrameTrackerGroupT&);

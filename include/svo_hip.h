@@ -840,6 +840,31 @@ int svo_hip_tracker_group_camera(svo_hip_tracker_group* group, int index, svo_hi
  * (may be NULL).  Synchronises once, for all cameras.  The cameras' features and point counters are read afterwards with
  * svo_hip_tracker_last_result on the handles that need them. */
 int svo_hip_tracker_group_track(svo_hip_tracker_group* group, const uint8_t* const* level0, svo_hip_track_result* results);
+/* One frame of SOME cameras: camera[n_active] names them (strictly increasing), level0[j] is camera[j]'s new image (its
+ * svo_hip_tracker_image_buffer: no copy), results[n_active] (may be NULL) camera[j]'s result.  The cameras named are tracked
+ * exactly as svo_hip_tracker_group_track tracks them -- one chain of launches whatever n_active, one synchronisation, features
+ * read afterwards with svo_hip_tracker_last_result -- and every stage is launched n_active cameras wide: a group of 64 with one
+ * camera in the call builds one pyramid, not 64.  n_active == n_cameras (the list is the identity then) makes the launches of
+ * svo_hip_tracker_group_track and gives its bytes; svo_hip_tracker_group_track itself keeps refusing a null image.
+ * A camera that SITS OUT is not touched: its map tables, key points and a pending key-point re-selection (it stays owed), its
+ * last frame's features and pose, the solver slot prepared for its next frame, its result block (svo_hip_tracker_last_result
+ * keeps returning it), the scratch the keyframe decision reads (svo_hip_tracker_finish_frame gives the decision it gave before)
+ * and the bytes of its last frame's pyramid all stay as they were.  Only the cameras named need a map and a last frame: a
+ * camera that was never set up may sit out.
+ * The two frame batches: when at least half of the cameras are named they swap roles as in every tracked frame and the
+ * pyramids of the cameras that sit out are copied into the new "last" batch; otherwise the batches keep their roles and the
+ * new pyramids of the cameras named are copied back into it -- one launch either way, the smaller side moves.  So
+ * svo_hip_tracker_last_frame_pyramid may return either batch after this call, for every camera the same one and with the bytes
+ * of that camera's last frame in its slot: the batch stays BORROWED under the rule stated there (this call is one that tracks).
+ * Outcomes are those of a lone svo_hip_tracker on the same frames in the two ways described above: unconditionally with
+ * SVO_HIP_SIA_REDUCTION_TILE_ORDER on both sides; by default while the SparseImgAlign kernel shape is the same, which the cameras
+ * NAMED choose -- their number and the largest feature count among their last frames.
+ * n_active == 0: SVO_HIP_OK, nothing enqueued.  Refused before anything is enqueued or changed: SVO_HIP_ERR_INVALID for a null
+ * group, n_active outside [0, n_cameras], a null `camera` or `level0` with n_active > 0, an index out of range, a list that is not
+ * strictly increasing, a null image; SVO_HIP_ERR_STATE when a camera named lacks its map or its last frame.  A failure behind the
+ * first enqueue synchronises the stream and has the solver slots of the cameras named gathered again by their next frame. */
+int svo_hip_tracker_group_track_some(svo_hip_tracker_group* group, int n_active, const int32_t* camera /* [n_active] */,
+                                     const uint8_t* const* level0 /* [n_active] */, svo_hip_track_result* results /* [n_active] */);
 /* The outcome of the camera's last tracked frame again (same outputs as svo_hip_tracker_track; any may be NULL): a copy from
  * the camera's page-locked result block, no device call. */
 int svo_hip_tracker_last_result(svo_hip_tracker* trk, svo_hip_track_result* result, double* feat_px, double* feat_f,

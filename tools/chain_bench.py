@@ -328,6 +328,61 @@ def group_cameras(ctx, seq, min_level, cams=(1, 8, 64), repeats=4):
     return out
 
 
+def group_subset(ctx, seq, min_level, n_group=64, n_active=8, repeats=3):
+    """svo_hip_tracker_group_track_some: a group of n_group cameras of which n_active track per call, rotating (call i: cameras
+    i * n_active ... modulo n_group), every camera through the sequence's frames in order.  Milliseconds per call, beside the
+    full call of a group of n_active and of a group of n_group (svo_hip_tracker_group_track); every camera's last pose bit-equal
+    to a lone tracker's (one camera count and one feature count per call, as alone: the same kernel shape)."""
+    assert 0 < n_active < n_group and n_group % n_active == 0
+    mp = tc.sequence_map(seq)
+    n = len(seq["px0"])
+    idx = np.arange(n, dtype=np.int32)
+    cfg = dict(max_keyframes=2, max_points=1024, max_obs=1024, max_kf_features=1024, max_candidates=16, max_items=1024,
+               max_frame_features=1024, grid_size=tc.CELL, max_fts=tc.MAX_FTS, klt_min_level=min_level)
+    lone = hip.Tracker(ctx, seq["cam"], **cfg)
+    lone.upload_keyframe(0, seq["pyrs"][0][0])
+    lone.set_map(mp)
+    lone.set_last_frame(seq["T0"], seq["px0"], seq["f0"], idx, kf_slot=0)
+    for k in range(1, len(seq["pyrs"])):
+        want = lone.track(seq["pyrs"][k][0])["T_f_w"]
+    lone.destroy()
+    n_frames = len(seq["pyrs"]) - 1
+    out = {}
+    for name, n_cam, n_act in (("subset", n_group, n_active), ("full_%d" % n_active, n_active, n_active), ("full_%d" % n_group, n_group, n_group)):
+        grp = hip.TrackerGroup(ctx, seq["cam"], n_cam, **cfg)
+        bufs = [t.image_buffer() for t in grp.cameras]
+        for t in grp.cameras:
+            t.upload_keyframe(0, seq["pyrs"][0][0])
+        rounds = n_cam // n_act                                        # calls until every camera has had its frame
+        dt, n_calls = 0.0, 0
+        for rep in range(repeats + 1):
+            for t in grp.cameras:
+                t.set_map(mp)
+                t.set_last_frame(seq["T0"], seq["px0"], seq["f0"], idx, kf_slot=0)
+            ctx.sync()
+            t0 = time.perf_counter()
+            t_copy = 0.0
+            for k in range(1, n_frames + 1):
+                for r in range(rounds):
+                    act = list(range(r * n_act, (r + 1) * n_act))
+                    tc0 = time.perf_counter()
+                    for c in act:
+                        bufs[c][:] = seq["pyrs"][k][0]
+                    t_copy += time.perf_counter() - tc0
+                    if n_act == n_cam:
+                        grp.track(bufs)
+                    else:
+                        grp.track_some(act, [bufs[c] for c in act])
+            if rep > 0:
+                dt += time.perf_counter() - t0 - t_copy
+                n_calls += n_frames * rounds
+            for c in range(n_cam):
+                assert list(grp.cameras[c].last_result()["T_f_w"]) == list(want), "%s: camera %d differs from the lone tracker" % (name, c)
+        out[name + "_ms_per_call"] = 1e3 * dt / n_calls
+        grp.destroy()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
@@ -337,7 +392,13 @@ def main():
     ap.add_argument("--cameras", action="store_true", help="only the multi-camera figure (1 / 2 / 4 / 8 trackers on as many host threads)")
     ap.add_argument("--camera-counts", default="1,2,4,8")
     ap.add_argument("--group-only", action="store_true", help="only svo_hip_tracker_group_track for --camera-counts (tools/trace_group.sh)")
+    ap.add_argument("--subset", default=None, metavar="N:K", help="only svo_hip_tracker_group_track_some: a group of N cameras, K per call, rotating")
     args = ap.parse_args()
+    if args.subset:
+        n_group, n_active = (int(v) for v in args.subset.split(":"))
+        seq = tc.make_sequence(n_frames=args.frames)
+        print(json.dumps({"group_subset": dict(group_subset(hip.Context(0), seq, args.min_level, n_group, n_active), n_group=n_group, n_active=n_active)}))
+        return
     if args.group_only:
         seq = tc.make_sequence(n_frames=args.frames)
         print(json.dumps({"group_frames_per_s_by_cameras": group_cameras(hip.Context(0), seq, args.min_level, cams=tuple(int(c) for c in args.camera_counts.split(",")))}))
