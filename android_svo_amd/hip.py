@@ -1471,3 +1471,96 @@ class TrackerGroup:
                 t.h = C.c_void_p()
             self.ctx.lib.svo_hip_tracker_group_destroy(self.h)
             self.h = C.c_void_p()
+
+
+# ---- the bootstrap: KLT tracking of the first frame's features (KltHomographyInit, S/initialization.cpp) -----------------
+class CKltParams(C.Structure):                # svo_hip_klt_params
+    _fields_ = [("win_size", C.c_int), ("max_level", C.c_int), ("max_iter", C.c_int), ("eps", C.c_double),
+                ("min_eig_threshold", C.c_double)]
+
+
+class CKltResult(C.Structure):                # svo_hip_klt_result
+    _fields_ = [("n_in", C.c_int), ("n_tracked", C.c_int), ("n_levels", C.c_int), ("disparity_median", C.c_double)]
+
+
+class KltTracker:
+    """svo_hip_klt: addFirstFrame / trackKlt / the disparity median of up to n_cameras cameras of one image size."""
+
+    GUARD = 5            # guard elements behind every array download() hands to the library
+
+    def __init__(self, ctx: Context, width: int, height: int, n_cameras: int = 1, max_features: int = 1024, **params):
+        self.ctx, self.width, self.height, self.n_cameras, self.max_features = ctx, width, height, n_cameras, max_features
+        prm = CKltParams()
+        ctx.check(ctx.lib.svo_hip_klt_default_params(C.byref(prm)), "klt_default_params")
+        for k, v in params.items():
+            if not hasattr(prm, k):
+                raise TypeError("unknown KLT parameter %r" % k)
+            setattr(prm, k, v)
+        self.params = prm
+        self.h = C.c_void_p()
+        ctx.check(ctx.lib.svo_hip_klt_create(ctx.h, width, height, n_cameras, max_features, C.byref(prm), C.byref(self.h)), "klt_create")
+
+    def level_shapes(self):
+        n, w, h = C.c_int(0), (C.c_int * MAX_LEVELS)(), (C.c_int * MAX_LEVELS)()
+        self.ctx.check(self.ctx.lib.svo_hip_klt_info(self.h, C.byref(n), w, h), "klt_info")
+        return [(h[i], w[i]) for i in range(n.value)]
+
+    def set_reference(self, camera: int, pyr: Pyramid, slot: int, px, f):
+        p = np.ascontiguousarray(px, dtype=np.float32).reshape(-1, 2)
+        ff = _f64(f).reshape(-1, 3)
+        assert len(p) == len(ff)
+        self.ctx.check(self.ctx.lib.svo_hip_klt_set_reference(self.h, camera, pyr.h if pyr is not None else None, slot, len(p),
+                                                              _ptr(p, C.c_float), _ptr(ff, C.c_double)), "klt_set_reference")
+
+    def set_reference_detected(self, camera: int, pyr: Pyramid, slot: int, cam, n_pyr_levels: int = 3, cell_size: int = 20,
+                               detection_threshold: float = 10.0) -> int:
+        n = C.c_int32(0)
+        c = make_camera(cam) if cam is not None else None
+        self.ctx.check(self.ctx.lib.svo_hip_klt_set_reference_detected(
+            self.h, camera, pyr.h if pyr is not None else None, slot, C.byref(c) if c is not None else None, n_pyr_levels, cell_size,
+            C.c_double(detection_threshold), C.byref(n)), "klt_set_reference_detected")
+        return n.value
+
+    def set_flow(self, camera: int, px_cur):
+        p = np.ascontiguousarray(px_cur, dtype=np.float32).reshape(-1, 2)
+        self.ctx.check(self.ctx.lib.svo_hip_klt_set_flow(self.h, camera, len(p), _ptr(p, C.c_float)), "klt_set_flow")
+
+    def track(self, cameras, cur: Pyramid, slots, cams) -> list:
+        """svo_hip_klt_track: one dict per listed camera (n_in, n_tracked, n_levels, disparity_median)."""
+        cameras, slots = [int(c) for c in cameras], [int(s) for s in slots]
+        n = len(cameras)
+        assert len(slots) == n and len(cams) == n
+        ca, sa = (C.c_int * max(n, 1))(*cameras), (C.c_int * max(n, 1))(*slots)
+        cm = (CCamera * max(n, 1))(*[c if isinstance(c, CCamera) else make_camera(c) for c in cams])
+        res = (CKltResult * max(n, 1))()
+        self.ctx.check(self.ctx.lib.svo_hip_klt_track(self.h, n, ca, cur.h if cur is not None else None, sa, cm, res), "klt_track")
+        return [dict(n_in=r.n_in, n_tracked=r.n_tracked, n_levels=r.n_levels, disparity_median=r.disparity_median) for r in res[:n]]
+
+    def download(self, camera: int) -> dict:
+        """The camera's lists; every array is handed over with guard elements behind its capacity, checked afterwards."""
+        m, g = self.max_features, self.GUARD
+        bufs = dict(px_ref=np.full((m + g, 2), -777.0, np.float32), px_cur=np.full((m + g, 2), -777.0, np.float32),
+                    f_ref=np.full((m + g, 3), -777.0), f_cur=np.full((m + g, 3), -777.0), disparity=np.full(m + g, -777.0),
+                    index=np.full(m + g, -777, np.int32))
+        n = C.c_int32(-1)
+        self.ctx.check(self.ctx.lib.svo_hip_klt_download(
+            self.h, camera, C.byref(n), _ptr(bufs["px_ref"], C.c_float), _ptr(bufs["px_cur"], C.c_float), _ptr(bufs["f_ref"], C.c_double),
+            _ptr(bufs["f_cur"], C.c_double), _ptr(bufs["disparity"], C.c_double), _ptr(bufs["index"], C.c_int32)), "klt_download")
+        k = n.value
+        for name, b in bufs.items():
+            if not (b[k:] == -777).all():
+                raise SvoHipError("svo_hip_klt_download wrote behind the %d entries of %s" % (k, name))
+        out = {name: b[:k].copy() for name, b in bufs.items()}
+        out["n"] = k
+        return out
+
+    def download_level(self, camera: int, level: int, current: bool = False) -> np.ndarray:
+        shp = self.level_shapes()[level]
+        out = np.empty(shp, dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.svo_hip_klt_download_level(self.h, camera, 1 if current else 0, level, _ptr(out, C.c_uint8)), "klt_download_level")
+        return out
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.svo_hip_klt_destroy(self.h)
+            self.h = C.c_void_p()

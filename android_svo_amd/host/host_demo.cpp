@@ -21,6 +21,11 @@
 //        svo_host_demo <case_dir> <out_dir> churn   SURVEY 8(b) "Threading": latency of SparseImgAlign::run on the tracking
 //                                                   thread while a second thread (own context) creates seed batches, runs a
 //                                                   pass and drops them at keyframe rate -- and with that thread idle
+//        svo_host_demo <case_dir> <out_dir> klt     the bootstrap of n cameras: svo::initialization::KltInit (hip_bridge::KltInitT,
+//                                                   svo_hip_klt_*) over klt_meta.bin / klt_images.bin / klt_px.bin -- camera 0's first
+//                                                   frame detected on the device, the others from the given features -- then three
+//                                                   frames, each ONE device call for all cameras; the lists of camera c after frame k
+//                                                   under <out_dir>/klt_c<c>_k<k>_*.bin, the return codes in klt_results.bin
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -832,7 +837,80 @@ static int filter_group_demo(const std::string& dir, const std::string& out, boo
   return 0;
 }
 
+// ---- the bootstrap: klt_meta.bin = [width, height, n_cameras, n_images, n_features, min_features, min_tracked, min_disparity,
+// then per camera fx fy cx cy k1 k2 p1 p2 k3] (doubles), klt_images.bin = n_images level-0 images back to back (image 0: the
+// first frame), klt_px.bin = n_features x 2 floats.  Camera c tracks image 1 + (k + c) % (n_images - 1) in frame k.
+static int klt_demo(const std::string& dir, const std::string& out) {
+  using namespace svo::initialization;
+  const std::vector<double> m = read_bin<double>(dir + "/klt_meta.bin");
+  const int w = (int)m[0], h = (int)m[1], nc = (int)m[2], ni = (int)m[3], nf = (int)m[4];
+  hip_bridge::KltInitGates gates;
+  gates.min_features = (size_t)m[5]; gates.min_tracked = (size_t)m[6]; gates.min_disparity = m[7];
+  std::vector<svo_hip_camera> cams((size_t)nc);
+  for (int c = 0; c < nc; ++c) {
+    PinholeCamera pc;
+    pc.width = w; pc.height = h; pc.fx = m[8 + 9 * c]; pc.fy = m[9 + 9 * c]; pc.cx = m[10 + 9 * c]; pc.cy = m[11 + 9 * c];
+    for (int k = 0; k < 5; ++k) pc.d[k] = m[12 + 9 * c + k];
+    cams[(size_t)c] = pc.toC();
+  }
+  const std::vector<uint8_t> images = read_bin<uint8_t>(dir + "/klt_images.bin");
+  const std::vector<float> pxf = read_bin<float>(dir + "/klt_px.bin");
+  if (images.size() != (size_t)w * h * ni || pxf.size() != (size_t)2 * nf) throw std::runtime_error("klt case: sizes");
+  svo_hip_ctx* ctx = nullptr;
+  hip_bridge::check(svo_hip_ctx_create(&ctx, 0, nullptr), nullptr, "ctx_create");
+  svo_hip_pyramid* pyr = nullptr;
+  hip_bridge::check(svo_hip_pyramid_create(ctx, w, h, 3, ni, &pyr), ctx, "pyramid_create");
+  hip_bridge::check(svo_hip_pyramid_upload_level0_batch_and_build(pyr, 0, ni, images.data()), ctx, "pyramid_build");
+  hip_bridge::check(svo_hip_ctx_sync(ctx), ctx, "sync");
+  std::vector<double> results;
+  {
+    KltInit init(ctx, w, h, nc, 1024, gates);
+    if (!init.ok()) throw std::runtime_error("klt_create");
+    std::vector<Point2f> px;
+    std::vector<Vector3d> f;
+    for (int i = 0; i < nf; ++i) {
+      px.push_back(Point2f(pxf[2 * i], pxf[2 * i + 1]));
+      f.push_back(Vector3d{{0.001 * pxf[2 * i], 0.001 * pxf[2 * i + 1], 1.0}});
+    }
+    for (int c = 0; c < nc; ++c)
+      results.push_back(c == 0 ? init.addFirstFrameDetected(0, pyr, 0, cams[0], 3, 20, 10.0) : init.addFirstFrame(c, pyr, 0, px, f));
+    std::vector<int> listed((size_t)nc), slots((size_t)nc);
+    std::vector<InitResult> res((size_t)nc);
+    for (int k = 0; k < 3; ++k) {
+      for (int c = 0; c < nc; ++c) { listed[(size_t)c] = c; slots[(size_t)c] = 1 + (k + c) % (ni - 1); }
+      if (!init.trackSecondFrames(nc, listed.data(), pyr, slots.data(), cams.data(), res.data())) throw std::runtime_error("klt_track");
+      for (int c = 0; c < nc; ++c) {
+        const KltInit::Lists& l = init.lists(c);
+        std::vector<float> a, b;
+        std::vector<double> fr, fc;
+        for (size_t i = 0; i < l.px_ref_.size(); ++i) {
+          a.push_back(l.px_ref_[i].x); a.push_back(l.px_ref_[i].y); b.push_back(l.px_cur_[i].x); b.push_back(l.px_cur_[i].y);
+          for (int j = 0; j < 3; ++j) { fr.push_back(l.f_ref_[i][j]); fc.push_back(l.f_cur_[i][j]); }
+        }
+        const std::string base = out + "/klt_c" + std::to_string(c) + "_k" + std::to_string(k);
+        write_bin(base + "_px_ref.bin", a); write_bin(base + "_px_cur.bin", b); write_bin(base + "_f_ref.bin", fr); write_bin(base + "_f_cur.bin", fc);
+        write_bin(base + "_disparity.bin", l.disparities_); write_bin(base + "_index.bin", l.index_);
+        results.push_back((double)res[(size_t)c]); results.push_back(l.disparity_median_);
+        std::printf("klt camera %d frame %d: %zu tracked, median disparity %.3f px, result %d\n", c, k, l.px_ref_.size(), l.disparity_median_, (int)res[(size_t)c]);
+      }
+    }
+  }
+  write_bin(out + "/klt_results.bin", results);
+  svo_hip_pyramid_destroy(pyr);
+  svo_hip_ctx_destroy(ctx);
+  std::printf("klt OK (%d cameras)\n", nc);
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 3 && std::string(argv[3]) == "klt") {
+    try {
+      return klt_demo(argv[1], argv[2]);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "klt demo failed: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc > 3 && std::string(argv[3]) == "filtergroup") {
     try {
       return filter_group_demo(argv[1], argv[2], argc > 4 && std::string(argv[4]) == "rig");
@@ -854,7 +932,7 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n [rig] [staggered]|filtergroup [rig]|churn|keyframes [device_seeds] [threaded]]\n", argv[0]); return 2; }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n [rig] [staggered]|filtergroup [rig]|churn|keyframes [device_seeds] [threaded]|klt]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {

@@ -42,6 +42,7 @@
 #include "svo_dropin/slot_table.h"
 #include "svo_dropin/depth_filter_batch.h"
 #include "svo_dropin/frame_tracker_batch.h"
+#include "svo_dropin/klt_init_hip.h"
 
 namespace svo {
 
@@ -1019,6 +1020,17 @@ class DepthFilterGroup {
   svo_hip_ctx* ctx_ = nullptr;
   std::unique_ptr<hip_bridge::PyramidCache> kf_pyr_, cur_pyr_;
 };
+
+/// svo::initialization::KltHomographyInit's KLT half (I/initialization.h:30-57, S/initialization.cpp:32-75,180-226) over
+/// hip_bridge::KltInitT: addFirstFrame / addFirstFrameDetected, trackSecondFrame(s) with the reference's gates, and the lists
+/// px_ref_, px_cur_, f_ref_, f_cur_, disparities_ as trackKlt leaves them, for one camera or for all cameras of a group in
+/// one device call.  computeFundamental and what follows (:79-140) stay the caller's.
+namespace initialization {
+struct Point2f { float x, y; Point2f() : x(0.f), y(0.f) {} Point2f(float a, float b) : x(a), y(b) {} };     // cv::Point2f
+struct KltTypes { typedef initialization::Point2f Point2f; typedef svo::Vector3d Vector3d; };
+typedef hip_bridge::KltInitResult InitResult;
+typedef hip_bridge::KltInitT<KltTypes> KltInit;
+}  // namespace initialization
 
 }  // namespace svo
 

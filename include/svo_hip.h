@@ -1202,6 +1202,63 @@ int svo_hip_seed_batch_create_detected(svo_hip_ctx* ctx, const svo_hip_pyramid* 
                                        svo_hip_seed_batch** batch, int32_t* n, double* px, double* f, int32_t* level,
                                        float* score);
 
+/* ---- the bootstrap on the device: KLT tracking of the first frame's features ---------------------------------------
+ * KltHomographyInit (I/initialization.h, S/initialization.cpp): addFirstFrame (:32-51) keeps the first frame's features,
+ * addSecondFrame (:61-75) tracks them into every following frame with trackKlt (:180-226) -- cv::calcOpticalFlowPyrLK with a
+ * 30 x 30 window, maxLevel 4, 30 iterations, eps 0.001, OPTFLOW_USE_INITIAL_FLOW -- erases the lost ones for good, forms the
+ * bearings f_cur and the disparities, and returns NO_KEYFRAME until their median (vk::getMedian: the order statistic of rank
+ * n / 2) reaches Config::initMinDisparity().  A handle holds that state for n_cameras cameras of one image size; any subset
+ * of them is tracked by one call.  computeFundamental / computeHomography (:228-329) stay on the host.
+ *
+ * OpenCV is not part of the reference's tree: PARITY UNPINNED.  The algorithm is written down in tests/klt_reference.py
+ * (Gaussian pyramid by cv::pyrDown's integer arithmetic, levels while both sides exceed the window; Scharr derivatives;
+ * 14-bit bilinear weights; the iteration and its exits) and the device computes that model's numbers bit for bit.  The
+ * departures from OpenCV are listed in DESIGN.md section 7: the five window sums are exact integer sums converted to float
+ * once; samples beyond the image are BORDER_REFLECT_101 values, derivatives beyond it are zero; the median of no disparity
+ * is NaN. */
+typedef struct svo_hip_klt svo_hip_klt;
+typedef struct { int win_size, max_level, max_iter; double eps, min_eig_threshold; } svo_hip_klt_params;  /* 30, 4, 30, 1e-3, 1e-4 */
+typedef struct { int n_in, n_tracked, n_levels; double disparity_median; } svo_hip_klt_result;
+int svo_hip_klt_default_params(svo_hip_klt_params* params);                                     /* trackKlt's constants (:189-201) */
+/* All device and page-locked memory of the handle is taken here: svo_hip_klt_track makes no allocator call.  params may be
+ * NULL.  SVO_HIP_ERR_INVALID: win_size outside 3..30 (the window's template lives in LDS), an image not larger than the
+ * window, n_cameras or max_features < 1. */
+int svo_hip_klt_create(svo_hip_ctx* ctx, int width, int height, int n_cameras, int max_features, const svo_hip_klt_params* params,
+                       svo_hip_klt** out);
+int svo_hip_klt_destroy(svo_hip_klt* klt);
+/* the Gaussian pyramid's shape: n_levels and the level sizes (arrays of SVO_HIP_MAX_LEVELS, each may be NULL) */
+int svo_hip_klt_info(const svo_hip_klt* klt, int* n_levels, int* level_width, int* level_height);
+/* addFirstFrame (:32-51) with the features from the host: px[n][2] as the reference's cv::Point2f, f[n][3]; the image is
+ * level 0 of pyramid slot `slot` (copied: the caller's pyramid may change afterwards).  px_cur starts as px_ref (:49).
+ * n = 0 is legal.  The `< 100 features` gate of :42 is the caller's.  Synchronises. */
+int svo_hip_klt_set_reference(svo_hip_klt* klt, int camera, const svo_hip_pyramid* pyr, int slot, int n, const float* px, const double* f);
+/* addFirstFrame as one call (detectFeatures, :154-174): svo_hip_detect_features_dev -- same kernels, refusals and threshold
+ * quirk, no occupancy -- straight into the handle, px rounded to f32 as cv::Point2f(ftr->px[0], ftr->px[1]) rounds it.
+ * *n = the number of features found.  If that exceeds max_features the call returns SVO_HIP_ERR_INVALID and the camera is
+ * left without a reference (the count is known only after the detection).  Synchronises. */
+int svo_hip_klt_set_reference_detected(svo_hip_klt* klt, int camera, const svo_hip_pyramid* pyr, int slot, const svo_hip_camera* cam,
+                                       int n_pyr_levels, int cell_size, double detection_threshold, int32_t* n);
+/* OPTFLOW_USE_INITIAL_FLOW with a motion prior (the remark at :196): px_cur[n][2] replaces the flow the next call starts
+ * from; n must be the camera's current feature count. */
+int svo_hip_klt_set_flow(svo_hip_klt* klt, int camera, int n, const float* px_cur);
+/* trackKlt (:180-226) and the disparity median (:72) for the n listed cameras in one set of launches: camera cameras[i]
+ * reads its current image from level 0 of slot slots[i] of `cur` (any pyramid batch of the context with the handle's image
+ * size: a user's, or a tracker group's frame batch through svo_hip_tracker_last_frame_pyramid) and forms its bearings with
+ * cams[i].  Lost features leave the camera's lists for good, px_cur is carried to the next call as its initial flow.  One
+ * synchronisation.  n_tracked = 0 gives a NaN median.  Before anything is enqueued: SVO_HIP_ERR_INVALID for a camera out of
+ * range or listed twice, a pyramid of another size or context, a slot out of range; SVO_HIP_ERR_STATE for a camera
+ * without a reference. */
+int svo_hip_klt_track(svo_hip_klt* klt, int n, const int* cameras, const svo_hip_pyramid* cur, const int* slots,
+                      const svo_hip_camera* cams /*[n]*/, svo_hip_klt_result* results /*[n]*/);
+/* the camera's lists as trackKlt leaves them (:203-225): px_ref[n][2], px_cur[n][2], f_ref[n][3], f_cur[n][3], disparity[n],
+ * index[n] (each surviving feature's position in the set_reference order); each may be NULL.  f_cur and disparity are
+ * defined after a svo_hip_klt_track.  Synchronises. */
+int svo_hip_klt_download(svo_hip_klt* klt, int camera, int32_t* n, float* px_ref, float* px_cur, double* f_ref, double* f_cur,
+                         double* disparity, int32_t* index);
+/* a level of the camera's Gaussian pyramid (tests): the previous image's (current = 0, levels 0..) or the last tracked
+ * image's (current = 1, levels 1..: its level 0 stays in the caller's pyramid) */
+int svo_hip_klt_download_level(svo_hip_klt* klt, int camera, int current, int level, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif
