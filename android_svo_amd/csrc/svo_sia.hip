@@ -706,7 +706,7 @@ SVO_DEV LppGeom lpp_project(const double* T, const double* q2, const LeanCam& ca
 // they are processed: alternating, LDS first, so that every tile read from memory has a predecessor whose computation
 // covers the latency of its prefetch
 template <int TPW, int CK>
-struct FusedPlan {
+struct FusedPlanLoops {
   static constexpr bool in_lds(int p) {
     int l = CK, g = TPW - CK;
     bool last_l = false, pick_l = false;
@@ -721,6 +721,28 @@ struct FusedPlan {
     int c = 0;
     for (int i = 0; i < p; ++i) c += in_lds(i) ? 1 : 0;
     return c;
+  }
+  static constexpr unsigned lds_mask() {       // bit p: position p is an LDS tile
+    unsigned m = 0;
+    for (int p = 0; p < TPW; ++p) m |= in_lds(p) ? 1u << p : 0u;
+    return m;
+  }
+};
+// The same plan as one constant.  The functions above are loops without an unroll pragma in a file built with
+// -fno-unroll-loops: called with the k of an unrolled tile loop they stayed scalar loops in the kernel (position 2 of a
+// four-tile wave counted its LDS slot in a nested loop, two taken back-branches per pass, in front of its LDS reads at
+// every evaluation).  A shift and a population count of a constant fold wherever k is known.
+template <int TPW, int CK>
+struct FusedPlan : FusedPlanLoops<TPW, CK> {
+  using FusedPlanLoops<TPW, CK>::in_lds;
+  using FusedPlanLoops<TPW, CK>::lds_slot;
+  static constexpr unsigned LDS_MASK = FusedPlanLoops<TPW, CK>::lds_mask();
+  static constexpr bool lds_at(int p) { return ((LDS_MASK >> p) & 1u) != 0; }
+  static constexpr int slot_at(int p) { return __builtin_popcount(LDS_MASK & ((1u << p) - 1u)); }
+  static constexpr bool same_as_loops() {
+    for (int p = 0; p < TPW; ++p)
+      if (lds_at(p) != in_lds(p) || slot_at(p) != lds_slot(p)) return false;
+    return true;
   }
 };
 
@@ -911,6 +933,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
     double4* __restrict__ sxyz, double* __restrict__ tile_h, float4* __restrict__ wmem, int max_tiles, FusedParams prm,
     int tiles_young, int n_extra, const int* __restrict__ slot_map = nullptr) {
   using Plan = FusedPlan<TPW, CK>;
+  static_assert(Plan::same_as_loops(), "the constant plan is the plan of in_lds / lds_slot");
   // the LDS left over holds one more tile -- the first one the plan keeps in memory -- for the first n_extra waves
   // (kernels whose waves own five or six tiles are register-bound: for them the extra LDS slot and the deferred
   // outside-the-image correction below cost more in spills than they save -- measured at 2500 patches: 2.02 ms
@@ -929,6 +952,14 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
   constexpr bool WIN_FOUR = TPW == 4 && (VARIANT != FUSED_PLAIN || TORD);
   constexpr bool WIN_DECIDE = !LEAN && !(TPW == 4 && NW == 4) && !(TPW == 3 && VARIANT == FUSED_EXACT_ROWS && !TORD);
   constexpr bool WIN_COEF_FIRST = !LEAN && !(TPW == 4 && NW == 4) && !WIN_FOUR;
+  // PLAN_CONST: in the evaluation the LDS tile plan is a constant (FusedPlan::LDS_MASK) instead of loops that a wave runs per
+  // tile (it issues one instruction per ~5.4 cycles whatever the instruction is).  Taken, as above, by the shapes whose
+  // allocation it leaves alone: with it the exact-rows instances with three tiles per wave spill 4 to 9 VGPRs instead of 0 or
+  // 1, and <8,4,2,1,true> 38 instead of 34.  Where the patches of a level are STORED the plan stays the loops in every shape:
+  // as a constant there it cost the four-tile shapes 40 spilled VGPRs (10 -> 50 in <8,4,2,0>) and the five-tile ones two or three.
+  constexpr bool PLAN_CONST = !(VARIANT == FUSED_EXACT_ROWS && (TPW == 3 || (TPW == 4 && NW == 8 && TORD)));
+  auto plan_lds = [](int p) -> bool { return PLAN_CONST ? Plan::lds_at(p) : Plan::in_lds(p); };
+  auto plan_slot = [](int p) -> int { return PLAN_CONST ? Plan::slot_at(p) : Plan::lds_slot(p); };
   const bool extra_lds = wave_of_thread() < n_extra;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   // The interpolated reference patch of every feature -- the 32 values W from which reference value, dx and dy of its
@@ -1271,8 +1302,8 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
 
         // this tile's interpolated patches: from LDS, or what was asked for while the previous tile was computed
         float4 Wq[8];
-        if (Plan::in_lds(k)) {
-          const float4* src = wc + (size_t)((Plan::lds_slot(k) * NW + wave) * 8) * TILE + lane;
+        if (plan_lds(k)) {
+          const float4* src = wc + (size_t)((plan_slot(k) * NW + wave) * 8) * TILE + lane;
 #pragma unroll
           for (int c4 = 0; c4 < 8; ++c4) Wq[c4] = src[c4 * TILE];
         } else if (k == P_EXTRA && extra_lds) {                // wave-uniform: this wave's extra LDS tile
@@ -1287,7 +1318,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sia_fused_kernel(
           gq[(k + 1) & 1] = lpp_project(T, q2, cam, X[k + 1], (fl[k + 1] & F_VISIBLE) != 0, scale, colsf, rowsf, stride);
 #pragma unroll
           for (int j = 0; j < 5; ++j) Crq[(k + 1) & 1][j] = load_row8(cur_img + (unsigned)(gq[(k + 1) & 1].off + j * stride));
-          if (!Plan::in_lds(k + 1)) {
+          if (!plan_lds(k + 1)) {
             const int tile_n = tile_of(k + 1) < n_tiles ? tile_of(k + 1) : (tile < n_tiles ? tile : 0);
             const float4* src = wmem + ((size_t)b * max_tiles + tile_n) * 8 * TILE + lane;
             // (a wave that keeps this tile in LDS asks for the same 1 KiB eight times instead: no branch, no traffic)
