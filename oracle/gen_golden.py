@@ -505,6 +505,27 @@ def gen_reproject_map_ref():
     np.savez_compressed(os.path.join(OUT, "reproject_map_ref.npz"), **out)
 
 
+def gen_reproject_paths_ref():
+    """Reprojector::reprojectMap executed by the reference's own compiled code on the constructed families of
+    tests/reproject_families.py (grids and frames on both sides of the planning kernel's LDS limits, keyframe selections with
+    exact distance ties under Options::max_n_kfs of 1, 10 and 16, values on both sides of every comparison).  Results only: the
+    inputs are regenerated from the family code and guarded by CRCs.  Every key feature is given (key_override holds no -2)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import reproject_families as rf
+    out = {}
+    for cs in rf.all_cases():
+        name = cs["name"]
+        r = refpy.reproject_map(rf.reference_view(cs), max_fts=cs["cfg"]["max_fts"], key_override=cs["kf_key_point"],
+                                max_n_kfs=cs["cfg"]["reproj_max_n_kfs"])
+        assert (r["kf_key_point"] == cs["kf_key_point"]).all(), name          # the harness found every key feature it was told to use
+        out[name + "_crc"] = np.array(rf.input_crc(cs), dtype=np.uint64)
+        out[name + "_n"] = np.array([r["n_matches"], r["n_trials"]], dtype=np.int64)
+        for k in rf.RESULT_KEYS:
+            out[name + "_" + k] = r[k]
+        print("reproject_paths_ref", name, r["n_matches"], r["n_trials"], "overlap", list(r["overlap_kf"]), "deleted", int(r["unlinked"].sum()))
+    np.savez_compressed(os.path.join(OUT, "reproject_paths_ref.npz"), **out)
+
+
 CAMERA_REF_CASES = (
     # name, width, height, fx, fy, cx, cy, (k1, k2, p1, p2, k3)
     ("pinhole_vga", 640, 480, 500.0, 500.0, 319.5, 239.5, (0.0, 0.0, 0.0, 0.0, 0.0)),
@@ -565,6 +586,7 @@ def main():
     if "--map-only" in sys.argv:
         assert refpy.available(), "build oracle/_ref first: make -C oracle ref"
         gen_reproject_map_ref()
+        gen_reproject_paths_ref()
         return
     assert refpy.available(), "build oracle/_ref first: make -C oracle ref"
     os.makedirs(OUT, exist_ok=True)
@@ -579,6 +601,7 @@ def main():
         gen_shitomasi_ref()
     gen_reproject_ref()
     gen_reproject_map_ref()
+    gen_reproject_paths_ref()
     gen_camera_ref()
     for fn in sorted(os.listdir(OUT)):
         print(fn, os.path.getsize(os.path.join(OUT, fn)))

@@ -67,6 +67,10 @@ static bool pt_obs_nonempty(const svo::Point* p) { return !p->obs_.empty(); }
 static thread_local double g_dist[5] = {0, 0, 0, 0, 0};
 extern "C" void ref_set_distortion(const double* d5) { for (int i = 0; i < 5; ++i) g_dist[i] = d5 ? d5[i] : 0.0; }
 
+// Reprojector::Options::max_n_kfs of the next ref_reproject_map* calls of this thread (0: the reference's own default, 10)
+static thread_local int g_reproj_max_n_kfs = 0;
+extern "C" void ref_set_reproj_max_n_kfs(int n) { g_reproj_max_n_kfs = n; }
+
 #ifdef REF_RUN_TRACKER_BINDING
 // what the last ref_reproject_map_keys call of this build (the frame-tracker binding in place of the Reprojector) left
 static int g_tracker_ok = 0, g_tracker_pose_optimised = 0;
@@ -575,6 +579,7 @@ int ref_reproject_map_keys(int width, int height, double fx, double fy, double c
   }
 #else
   svo::Reprojector* rp = new svo::Reprojector(&cam, *map);
+  if (g_reproj_max_n_kfs > 0) rp->options_.max_n_kfs = (size_t)g_reproj_max_n_kfs;
   rp->reprojectMap(frame, overlap);
   *n_matches = rp->n_matches_;
   *n_trials = rp->n_trials_;

@@ -370,14 +370,20 @@ def camera_is_in_frame(width, height, obs, boundary, level):
 
 
 # ---- the whole Reprojector::reprojectMap on a real svo::Map (ref_objects.cpp: ref_reproject_map) ----
-def reproject_map(cs, max_fts=1200, n_pyr_levels=3, key_override=None, library=None):
+def reproject_map(cs, max_fts=1200, n_pyr_levels=3, key_override=None, library=None, max_n_kfs=None):
     """cs: a case of android_svo_amd.synth.make_map_case.  library: another build of the same harness (the one linked with
     the PATCHED reprojector of include/svo_dropin/reprojector.patch: tests/test_gpu_dropin_binding.py).  Returns the reference's outputs, incl. the key points its own
     Frame::setKeyPoints chose for every keyframe (an input of the oracle / HIP forms of the call).
     key_override [n_kf][5] (-2: keep the reference's choice, -1: empty slot, else point index): the key features to start
     from; kf_key_point is then what the call started from and kf_key_point_after what Map::safeDeletePoint ->
-    Frame::removeKeyPoint left behind."""
+    Frame::removeKeyPoint left behind.  max_n_kfs: Reprojector::Options::max_n_kfs for this call (None: the reference's 10)."""
     cam, n_kf, n_pts, n_obs = cs["cam"], cs["n_kf"], cs["n_points"], len(cs["obs_point"])
+    if max_n_kfs is not None:
+        (library or lib()).ref_set_reproj_max_n_kfs(C.c_int(int(max_n_kfs)))
+        try:
+            return reproject_map(cs, max_fts, n_pyr_levels, key_override, library)
+        finally:
+            (library or lib()).ref_set_reproj_max_n_kfs(C.c_int(0))
     kp = (C.POINTER(C.POINTER(C.c_uint8)) * n_kf)()
     keep = []
     for k in range(n_kf):
