@@ -5,29 +5,11 @@
 //   KltHomographyInit::addSecondFrame   S/initialization.cpp:61-75    (the tracking and the median; the gates are the host's)
 //   trackKlt                            S/initialization.cpp:180-226  (svo_hip_klt_track)
 //
-// computeFundamental / computeHomography (:228-329, RANSAC) stay on the host.  The kernels are in svo_klt_device.h.
+// computeFundamental (:260-329) and the rest of addSecondFrame (:77-138) are svo_two_view_impl.h; computeHomography (:232-258, the
+// path the reference has switched off) is not built.  The kernels are in svo_klt_device.h.
 #include "svo_klt_device.h"
 
 using namespace svo_klt;
-
-struct svo_hip_klt {
-  svo_hip_ctx* ctx = nullptr;
-  int width = 0, height = 0, n_cameras = 0, max_features = 0;
-  svo_hip_klt_params prm;
-  KltLevels lv;
-  KltDev dev;
-  char* dev_block = nullptr;
-  KltJob* jobs_dev = nullptr;
-  char* host_block = nullptr;             // page-locked: [jobs][result blocks][detection count]
-  KltJob* jobs_host = nullptr;
-  KltResultBlock* res_host = nullptr;
-  KltResultBlock* res_host_dev = nullptr;
-  int32_t* det_n_host = nullptr;
-  int32_t* det_n_host_dev = nullptr;
-  std::vector<int> n_host;                // features a camera holds
-  std::vector<char> has_ref;
-  unsigned long long seq = 0;
-};
 
 namespace {
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -148,6 +130,7 @@ int svo_hip_klt_create(svo_hip_ctx* ctx, int width, int height, int n_cameras, i
   k->det_n_host_dev = reinterpret_cast<int32_t*>(host_dev + h_jobs + h_res);
   k->n_host.assign(nc, 0);
   k->has_ref.assign(nc, 0);
+  k->has_cur.assign(nc, 0);
   *out = k;
   return SVO_HIP_OK;
 }
@@ -156,6 +139,7 @@ int svo_hip_klt_destroy(svo_hip_klt* k) {
   if (!k) return SVO_HIP_ERR_INVALID;
   (void)hipSetDevice(k->ctx->device);
   (void)hipStreamSynchronize(k->ctx->stream);
+  svo_tv_release(k);
   (void)hipFree(k->dev_block); ++k->ctx->n_frees;
   (void)hipHostFree(k->host_block); ++k->ctx->n_frees;
   delete k;
@@ -212,6 +196,7 @@ int svo_hip_klt_set_reference(svo_hip_klt* k, int camera, const svo_hip_pyramid*
   SVO_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   k->n_host[camera] = n;
   k->has_ref[camera] = 1;
+  k->has_cur[camera] = 0;
   return SVO_HIP_OK;
 }
 
@@ -252,11 +237,12 @@ int svo_hip_klt_set_reference_detected(svo_hip_klt* k, int camera, const svo_hip
   const int n_det = *k->det_n_host;
   *n = n_det;
   if (n_det > k->max_features) {                       // known only now: the camera is left WITHOUT a reference
-    k->n_host[camera] = 0; k->has_ref[camera] = 0;
+    k->n_host[camera] = 0; k->has_ref[camera] = 0; k->has_cur[camera] = 0;
     return svo_fail(ctx, SVO_HIP_ERR_INVALID, "svo_hip_klt_set_reference_detected", "more features than max_features");
   }
   k->n_host[camera] = n_det;
   k->has_ref[camera] = 1;
+  k->has_cur[camera] = 0;
   return SVO_HIP_OK;
 }
 
@@ -327,6 +313,7 @@ int svo_hip_klt_track(svo_hip_klt* k, int n, const int* cameras, const svo_hip_p
     results[i].n_in = r.n_in; results[i].n_tracked = r.n_tracked; results[i].n_levels = k->lv.n_levels;
     results[i].disparity_median = r.median;
     k->n_host[c] = r.n_tracked;
+    k->has_cur[c] = 1;
   }
   return SVO_HIP_OK;
 }
@@ -365,3 +352,6 @@ int svo_hip_klt_download_level(svo_hip_klt* k, int camera, int current, int leve
 }
 
 }  // extern "C"
+
+// the two-view stage on the same handle: svo_hip_klt_two_view / _download_two_view / _set_lists
+#include "svo_two_view_impl.h"

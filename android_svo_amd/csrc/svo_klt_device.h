@@ -10,57 +10,9 @@
 // once, and an f32 chain in which every operation is rounded on its own (-ffp-contract=off; roots and quotients through f64,
 // which rounds to the correctly rounded f32 result).
 #pragma once
-#include "svo_internal.h"
+#include "svo_klt_types.h"
 
 namespace svo_klt {
-using namespace svo_dev;
-
-constexpr int KLT_MAX_WIN = 30;                       // the template of a wave: 3 x 900 int16 in LDS
-constexpr int KLT_TPL = 15 * 64;                      // 900 rounded up to whole waves
-constexpr int KLT_WAVES = 4;                          // features per 256-thread block
-
-// the Gaussian pyramid of one image: level l is w[l] x h[l] bytes at off[l] (level 0 of the current image is read where the
-// caller's svo_hip_pyramid holds it)
-struct KltLevels {
-  int n_levels;
-  int w[SVO_HIP_MAX_LEVELS], h[SVO_HIP_MAX_LEVELS];
-  unsigned off[SVO_HIP_MAX_LEVELS];
-};
-
-// one listed camera of a call
-struct KltJob {
-  int cam, pad;
-  const uint8_t* cur_l0;                              // level 0 of the current image
-  char* result;                                       // the camera's page-locked result block (device address)
-  unsigned long long seq;
-  Cam model;
-};
-
-// the handle's device arrays, [camera][max_features] each
-struct KltDev {
-  float *px_ref, *px_cur;                             // x 2
-  double *f_ref, *f_cur;                              // x 3
-  double* disparity;
-  int32_t* index;
-  uint8_t* status;
-  int32_t* n;                                         // [camera]
-  uint8_t *prev_pyr, *cur_pyr;                        // [camera][pyr_bytes]
-  size_t pyr_bytes;
-  int max_features;
-};
-
-struct KltPrm {
-  int win, max_level, max_iter;
-  double eps2;
-  float min_eig;
-};
-
-// the result block of a camera in page-locked memory
-struct KltResultBlock {
-  unsigned long long seq;
-  int n_in, n_tracked;
-  double median;
-};
 
 // BORDER_REFLECT_101 for an index at most n - 1 beyond the image (what a window and its derivative neighbourhood reach);
 // clamped behind it, so that no read leaves the image whatever the index

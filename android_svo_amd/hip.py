@@ -1483,8 +1483,24 @@ class CKltResult(C.Structure):                # svo_hip_klt_result
     _fields_ = [("n_in", C.c_int), ("n_tracked", C.c_int), ("n_levels", C.c_int), ("disparity_median", C.c_double)]
 
 
+class CTwoViewParams(C.Structure):            # svo_hip_two_view_params
+    _fields_ = [("reproj_thresh", C.c_double), ("min_inliers", C.c_int), ("map_scale", C.c_double), ("n_hypotheses", C.c_int),
+                ("seed", C.c_ulonglong)]
+
+
+class CTwoViewResult(C.Structure):            # svo_hip_two_view_result
+    _fields_ = [("status", C.c_int), ("n_in", C.c_int), ("hypothesis", C.c_int), ("hypothesis_count", C.c_int), ("candidate", C.c_int),
+                ("candidate_count", C.c_int), ("n_inliers", C.c_int), ("n_points", C.c_int), ("depth_median", C.c_double),
+                ("scale", C.c_double), ("T_cur_from_ref", C.c_double * 7), ("T_cur_w", C.c_double * 7)]
+
+
+TWO_VIEW_OK, TWO_VIEW_TOO_FEW, TWO_VIEW_NO_MODEL, TWO_VIEW_CHEIRALITY, TWO_VIEW_FEW_INLIERS = range(5)
+TWO_VIEW_MAX_HYPOTHESES = 4096
+
+
 class KltTracker:
-    """svo_hip_klt: addFirstFrame / trackKlt / the disparity median of up to n_cameras cameras of one image size."""
+    """svo_hip_klt: addFirstFrame / trackKlt / the disparity median of up to n_cameras cameras of one image size, and the
+    two-view stage on their lists (computeFundamental and the rest of addSecondFrame)."""
 
     GUARD = 5            # guard elements behind every array download() hands to the library
 
@@ -1553,6 +1569,85 @@ class KltTracker:
         out = {name: b[:k].copy() for name, b in bufs.items()}
         out["n"] = k
         return out
+
+    def set_lists(self, camera: int, px_ref, px_cur, f_ref, f_cur):
+        """svo_hip_klt_set_lists: the camera's lists from the host (a matcher of the caller's own, the tests)"""
+        pr, pc = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 2) for a in (px_ref, px_cur))
+        fr, fc = (_f64(a).reshape(-1, 3) for a in (f_ref, f_cur))
+        assert len(pr) == len(pc) == len(fr) == len(fc)
+        self.ctx.check(self.ctx.lib.svo_hip_klt_set_lists(self.h, int(camera), len(pr), _ptr(pr, C.c_float), _ptr(pc, C.c_float), _ptr(fr, C.c_double),
+                                                          _ptr(fc, C.c_double)), "klt_set_lists")
+
+    def two_view(self, cameras, cams, T_ref_w=None, **params) -> list:
+        """svo_hip_klt_two_view: one dict per listed camera (the fields of svo_hip_two_view_result)."""
+        cameras = [int(c) for c in cameras]
+        n = len(cameras)
+        assert len(cams) == n
+        prm = CTwoViewParams()
+        self.ctx.check(self.ctx.lib.svo_hip_two_view_default_params(C.byref(prm)), "two_view_default_params")
+        for k, v in params.items():
+            if not hasattr(prm, k):
+                raise TypeError("unknown two-view parameter %r" % k)
+            setattr(prm, k, v)
+        ca = (C.c_int * max(n, 1))(*cameras)
+        cm = (CCamera * max(n, 1))(*[c if isinstance(c, CCamera) else make_camera(c) for c in cams])
+        T = None
+        if T_ref_w is not None:
+            T = _f64(T_ref_w).reshape(-1, 7)
+            assert len(T) == n
+        res = (CTwoViewResult * max(n, 1))()
+        self.ctx.check(self.ctx.lib.svo_hip_klt_two_view(self.h, n, ca, cm, None if T is None else _ptr(T, C.c_double), C.byref(prm), res),
+                       "klt_two_view")
+        return [dict(status=r.status, n_in=r.n_in, hypothesis=r.hypothesis, hypothesis_count=r.hypothesis_count, candidate=r.candidate,
+                     candidate_count=r.candidate_count, n_inliers=r.n_inliers, n_points=r.n_points, depth_median=r.depth_median,
+                     scale=r.scale, T_cur_from_ref=np.array(r.T_cur_from_ref[:]), T_cur_w=np.array(r.T_cur_w[:])) for r in res[:n]]
+
+    def download_two_view(self, camera: int) -> dict:
+        """What the camera's last two_view left on the device; every array is handed over with guard elements, checked afterwards.
+        xyz_in_cur is None unless the status was OK or FEW_INLIERS."""
+        m, g, H = self.max_features, self.GUARD, TWO_VIEW_MAX_HYPOTHESES
+        bufs = dict(xyz_in_cur=np.full((m + g, 3), -777.0), mask=np.full(m + g, 177, np.uint8), inliers=np.full(m + g, -777, np.int32),
+                    point_index=np.full(m + g, -777, np.int32), point_pos=np.full((m + g, 3), -777.0), counts=np.full(H + g, -777, np.int32))
+        st, n, ni, npt, nh = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        self.ctx.check(self.ctx.lib.svo_hip_klt_download_two_view(
+            self.h, int(camera), C.byref(st), C.byref(n), _ptr(bufs["xyz_in_cur"], C.c_double), _ptr(bufs["mask"], C.c_uint8), C.byref(ni),
+            _ptr(bufs["inliers"], C.c_int32), C.byref(npt), _ptr(bufs["point_index"], C.c_int32), _ptr(bufs["point_pos"], C.c_double),
+            C.byref(nh), _ptr(bufs["counts"], C.c_int32)), "klt_download_two_view")
+        have_xyz = st.value in (TWO_VIEW_OK, TWO_VIEW_FEW_INLIERS)             # the statuses behind the cheirality gate
+        sizes = dict(xyz_in_cur=n.value if have_xyz else 0, mask=n.value, inliers=ni.value, point_index=npt.value, point_pos=npt.value,
+                     counts=nh.value)
+        for name, b in bufs.items():
+            fill = 177 if name == "mask" else -777
+            if not (b[sizes[name]:] == fill).all():
+                raise SvoHipError("svo_hip_klt_download_two_view wrote behind the %d entries of %s" % (sizes[name], name))
+        out = {name: b[:sizes[name]].copy() for name, b in bufs.items()}
+        if not have_xyz:
+            out["xyz_in_cur"] = None
+        out.update(status=st.value, n=n.value, n_inliers=ni.value, n_points=npt.value)
+        return out
+
+    def map_tables(self, camera: int, result: dict, T_ref_w=None, kf_slots=(0, 1)) -> dict:
+        """The first map as the index tables Tracker.set_map takes, from the camera's two_view result (status OK) and what it left on
+        the device (:117-138): two keyframes (ref, cur), every point of type unknown with its two observations in Point::obs_
+        order [ref, cur] (addFrameRef pushes to the front; cur is added first), level 0, no edgelets, kf_ftr_point of each
+        frame in creation order, no candidates."""
+        if result["status"] != TWO_VIEW_OK:
+            raise SvoHipError("map_tables needs a two-view result with status OK")
+        lists, tv = self.download(camera), self.download_two_view(camera)
+        idx = tv["point_index"].astype(np.int64)
+        m = len(idx)
+        obs_px, obs_f = np.empty((2 * m, 2)), np.empty((2 * m, 3))
+        obs_px[0::2], obs_px[1::2] = lists["px_ref"][idx].astype(np.float64), lists["px_cur"][idx].astype(np.float64)
+        obs_f[0::2], obs_f[1::2] = lists["f_ref"][idx], lists["f_cur"][idx]
+        pts = np.arange(m, dtype=np.int32)
+        T0 = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0]) if T_ref_w is None else _f64(T_ref_w).reshape(7)
+        return dict(kf_slot=np.array(kf_slots, np.int32), T_kf_w=np.stack([T0, _f64(result["T_cur_w"])]),
+                    kf_key_point=np.full((2, 5), -1, np.int32), kf_ftr_offset=np.array([0, m, 2 * m], np.int32),
+                    kf_ftr_point=np.concatenate([pts, pts]), pt_pos=tv["point_pos"].reshape(m, 3), pt_type=np.full(m, 2, np.int32),
+                    pt_n_failed=np.zeros(m, np.int32), pt_n_succeeded=np.zeros(m, np.int32),
+                    pt_obs_offset=(2 * np.arange(m + 1)).astype(np.int32), obs_kf=np.tile(np.array([0, 1], np.int32), m), obs_px=obs_px,
+                    obs_f=obs_f, obs_level=np.zeros(2 * m, np.int32), obs_edgelet=np.zeros(2 * m, np.uint8),
+                    obs_grad=np.tile(np.array([1.0, 0.0]), (2 * m, 1)), cand_point=np.zeros(0, np.int32))
 
     def download_level(self, camera: int, level: int, current: bool = False) -> np.ndarray:
         shp = self.level_shapes()[level]

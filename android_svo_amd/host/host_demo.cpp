@@ -902,7 +902,82 @@ static int klt_demo(const std::string& dir, const std::string& out) {
   return 0;
 }
 
+// ---- the bootstrap's second half: boot_meta.bin = [width, height, fx, fy, cx, cy, n, reproj_thresh, min_inliers, map_scale,
+// n_hypotheses, seed, T_ref_w[7]] (doubles); boot_px_ref.bin / boot_px_cur.bin = n x 2 floats, boot_f_ref.bin / boot_f_cur.bin =
+// n x 3 doubles: the lists of a matcher.  Lists -> two-view on the device -> the twin's first map -> its flatten written out.
+static int bootstrap_demo(const std::string& dir, const std::string& out) {
+  using namespace svo::initialization;
+  const std::vector<double> m = read_bin<double>(dir + "/boot_meta.bin");
+  if (m.size() != 19) throw std::runtime_error("bootstrap case: boot_meta.bin");
+  PinholeCamera cam;
+  cam.width = (int)m[0]; cam.height = (int)m[1]; cam.fx = m[2]; cam.fy = m[3]; cam.cx = m[4]; cam.cy = m[5];
+  const size_t n = (size_t)m[6];
+  svo_hip_two_view_params prm;
+  svo_hip_two_view_default_params(&prm);
+  prm.reproj_thresh = m[7]; prm.min_inliers = (int)m[8]; prm.map_scale = m[9]; prm.n_hypotheses = (int)m[10]; prm.seed = (unsigned long long)m[11];
+  const auto pr = read_bin<float>(dir + "/boot_px_ref.bin"), pc = read_bin<float>(dir + "/boot_px_cur.bin");
+  const auto fr = read_bin<double>(dir + "/boot_f_ref.bin"), fc = read_bin<double>(dir + "/boot_f_cur.bin");
+  if (pr.size() != 2 * n || pc.size() != 2 * n || fr.size() != 3 * n || fc.size() != 3 * n) throw std::runtime_error("bootstrap case: sizes");
+  std::vector<Point2f> px_ref, px_cur;
+  std::vector<Vector3d> f_ref, f_cur;
+  for (size_t i = 0; i < n; ++i) {
+    px_ref.push_back(Point2f(pr[2 * i], pr[2 * i + 1])); px_cur.push_back(Point2f(pc[2 * i], pc[2 * i + 1]));
+    f_ref.push_back(Vector3d{{fr[3 * i], fr[3 * i + 1], fr[3 * i + 2]}}); f_cur.push_back(Vector3d{{fc[3 * i], fc[3 * i + 1], fc[3 * i + 2]}});
+  }
+  svo_hip_ctx* ctx = nullptr;
+  hip_bridge::check(svo_hip_ctx_create(&ctx, 0, nullptr), nullptr, "ctx_create");
+  svo_hip_pyramid* pyr = nullptr;
+  const std::vector<uint8_t> blank((size_t)cam.width * cam.height, 0);                // the two-view stage reads no image
+  hip_bridge::check(svo_hip_pyramid_create(ctx, cam.width, cam.height, 1, 1, &pyr), ctx, "pyramid_create");
+  hip_bridge::check(svo_hip_pyramid_upload_level0_batch_and_build(pyr, 0, 1, blank.data()), ctx, "pyramid_build");
+  hip_bridge::check(svo_hip_ctx_sync(ctx), ctx, "sync");
+  std::vector<double> results;
+  {
+    hip_bridge::KltInitGates gates;
+    gates.min_features = 0;
+    KltInit init(ctx, cam.width, cam.height, 1, 1024, gates);
+    if (!init.ok()) throw std::runtime_error("klt_create");
+    if (init.addFirstFrame(0, pyr, 0, px_ref, f_ref) != hip_bridge::KLT_SUCCESS) throw std::runtime_error("addFirstFrame");
+    if (!init.setLists(0, px_ref, px_cur, f_ref, f_cur)) throw std::runtime_error("setLists");
+    FramePtr frame_ref(new Frame(&cam, {blank})), frame_cur(new Frame(&cam, {blank}));
+    frame_ref->T_f_w_ = SE3(m.data() + 12);
+    const InitResult r = init.addSecondFrame(0, frame_ref.get(), frame_cur.get(), &prm);
+    const KltInit::TwoView& tv = init.twoView(0);
+    results = {(double)r, (double)tv.status_, (double)tv.inliers_.size(), (double)tv.point_index_.size(), tv.depth_median_, tv.scale_};
+    results.insert(results.end(), tv.T_cur_from_ref_, tv.T_cur_from_ref_ + 7);
+    results.insert(results.end(), tv.T_cur_w_, tv.T_cur_w_ + 7);
+    Map map;
+    if (r == hip_bridge::KLT_SUCCESS) { map.addKeyframe(frame_ref); map.addKeyframe(frame_cur); }
+    const MapTables t = flattenMap(map);
+    write_bin(out + "/boot_kf_slot.bin", t.kf_slot); write_bin(out + "/boot_T_kf_w.bin", t.T_kf_w); write_bin(out + "/boot_kf_key_point.bin", t.kf_key_point);
+    write_bin(out + "/boot_kf_ftr_offset.bin", t.kf_ftr_offset); write_bin(out + "/boot_kf_ftr_point.bin", t.kf_ftr_point);
+    write_bin(out + "/boot_pt_pos.bin", t.pt_pos); write_bin(out + "/boot_pt_type.bin", t.pt_type); write_bin(out + "/boot_pt_n_failed.bin", t.pt_n_failed);
+    write_bin(out + "/boot_pt_n_succeeded.bin", t.pt_n_succeeded); write_bin(out + "/boot_pt_obs_offset.bin", t.pt_obs_offset);
+    write_bin(out + "/boot_obs_kf.bin", t.obs_kf); write_bin(out + "/boot_obs_px.bin", t.obs_px); write_bin(out + "/boot_obs_f.bin", t.obs_f);
+    write_bin(out + "/boot_obs_level.bin", t.obs_level); write_bin(out + "/boot_obs_edgelet.bin", t.obs_edgelet); write_bin(out + "/boot_obs_grad.bin", t.obs_grad);
+    write_bin(out + "/boot_cand_point.bin", t.cand_point);
+    std::vector<int32_t> inl(tv.inliers_.begin(), tv.inliers_.end());
+    std::vector<double> xyz;
+    for (const Vector3d& v : tv.xyz_in_cur_) xyz.insert(xyz.end(), v.v, v.v + 3);
+    write_bin(out + "/boot_inliers.bin", inl); write_bin(out + "/boot_xyz_in_cur.bin", xyz);
+    std::printf("bootstrap: %zu correspondences, status %d, %zu inliers, %zu points, result %d\n", n, tv.status_, tv.inliers_.size(), tv.point_index_.size(), (int)r);
+  }
+  write_bin(out + "/boot_results.bin", results);
+  svo_hip_pyramid_destroy(pyr);
+  svo_hip_ctx_destroy(ctx);
+  std::printf("bootstrap OK\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 3 && std::string(argv[3]) == "bootstrap") {
+    try {
+      return bootstrap_demo(argv[1], argv[2]);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "bootstrap demo failed: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc > 3 && std::string(argv[3]) == "klt") {
     try {
       return klt_demo(argv[1], argv[2]);
@@ -932,7 +1007,7 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n [rig] [staggered]|filtergroup [rig]|churn|keyframes [device_seeds] [threaded]|klt]\n", argv[0]); return 2; }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s case_dir out_dir [track [incremental] [times] [kf_every E] [max_kfs N] [full_remove] [new_seeds S] [max_points N] [compact] [reloc_at K]|trackgroup n [rig] [staggered]|filtergroup [rig]|churn|keyframes [device_seeds] [threaded]|klt|bootstrap]\n", argv[0]); return 2; }
   const std::string dir = argv[1], out = argv[2];
   if (argc > 3 && std::string(argv[3]) == "trackgroup") {
     try {

@@ -1029,7 +1029,97 @@ namespace initialization {
 struct Point2f { float x, y; Point2f() : x(0.f), y(0.f) {} Point2f(float a, float b) : x(a), y(b) {} };     // cv::Point2f
 struct KltTypes { typedef initialization::Point2f Point2f; typedef svo::Vector3d Vector3d; };
 typedef hip_bridge::KltInitResult InitResult;
-typedef hip_bridge::KltInitT<KltTypes> KltInit;
+
+/// KltHomographyInit on the twin types: the bridge's lists and device calls, and addSecondFrame's second half (:77-138).
+class KltInit : public hip_bridge::KltInitT<KltTypes> {
+ public:
+  typedef hip_bridge::KltInitT<KltTypes> Base;
+  KltInit(svo_hip_ctx* ctx, int width, int height, int n_cameras, int max_features, const hip_bridge::KltInitGates& gates = hip_bridge::KltInitGates())
+      : Base(ctx, width, height, n_cameras, max_features, gates) {}
+
+  /// :117-138 for one camera: for every feature of the point list, in its order, a Point at `pos` with its Feature in the
+  /// current frame (added first) and in the reference frame (added second: Point::obs_ reads [ref, cur]), level 0.  Returns
+  /// the number of points created.
+  static size_t createFirstPoints(const Lists& l, const TwoView& tv, Frame* frame_ref, Frame* frame_cur) {
+    for (size_t k = 0; k < tv.point_index_.size(); ++k) {
+      const size_t i = (size_t)tv.point_index_[k];
+      Point* new_point = new Point(tv.point_pos_[k]);                                                   // :125-126
+      Feature* ftr_cur = new Feature(frame_cur, Vector2d{{(double)l.px_cur_[i].x, (double)l.px_cur_[i].y}}, l.f_cur_[i], 0);   // :121, :129
+      ftr_cur->point = new_point;
+      frame_cur->addFeature(ftr_cur);
+      new_point->addFrameRef(ftr_cur);
+      Feature* ftr_ref = new Feature(frame_ref, Vector2d{{(double)l.px_ref_[i].x, (double)l.px_ref_[i].y}}, l.f_ref_[i], 0);   // :122, :134
+      ftr_ref->point = new_point;
+      frame_ref->addFeature(ftr_ref);
+      new_point->addFrameRef(ftr_ref);
+    }
+    return tv.point_index_.size();
+  }
+
+  /// addSecondFrame from :77 on, for a camera whose lists the last trackSecondFrames (or setLists) left: computeFundamental, the
+  /// gates, scale and pose on the device (computeTwoView with the reference frame's camera and pose), then frame_cur->T_f_w_
+  /// (:108-115) and the first points (:117-138).  FAILURE (:89, :307, or a refused call) changes neither frame.
+  InitResult addSecondFrame(int camera, Frame* frame_ref, Frame* frame_cur, const svo_hip_two_view_params* params = nullptr) {
+    const InitResult r = computeTwoView(camera, frame_ref->cam_->toC(), frame_ref->T_f_w_.p, params);
+    if (r != hip_bridge::KLT_SUCCESS) return hip_bridge::KLT_FAILURE;
+    frame_cur->T_f_w_ = SE3(twoView(camera).T_cur_w_);
+    createFirstPoints(lists(camera), twoView(camera), frame_ref, frame_cur);
+    return hip_bridge::KLT_SUCCESS;
+  }
+};
+
+/// svo::Map as the index tables of svo_hip_tracker_map, in the order FrameTrackerT::uploadMap walks it (keyframes_, fts_,
+/// Point::obs_, candidates_); kf_slot is the keyframe's position.  What a freshly bootstrapped map looks like to the tracker.
+struct MapTables {
+  std::vector<int32_t> kf_slot, kf_key_point, kf_ftr_offset, kf_ftr_point, pt_type, pt_n_failed, pt_n_succeeded, pt_obs_offset, obs_kf, obs_level,
+      cand_point;
+  std::vector<double> T_kf_w, pt_pos, obs_px, obs_f, obs_grad;
+  std::vector<uint8_t> obs_edgelet;
+};
+inline MapTables flattenMap(Map& map) {
+  MapTables t;
+  std::map<const Point*, int> index_of_point;
+  std::vector<const Point*> points;
+  std::map<int, int> index_of_frame;
+  auto point_index = [&](const Point* p) {
+    auto it = index_of_point.find(p);
+    if (it != index_of_point.end()) return it->second;
+    const int i = (int)points.size();
+    points.push_back(p); index_of_point[p] = i;
+    return i;
+  };
+  t.kf_ftr_offset.push_back(0); t.pt_obs_offset.push_back(0);
+  int k = 0;
+  for (const FramePtr& kf : map.keyframes_) {
+    index_of_frame[kf->id_] = k;
+    t.kf_slot.push_back(k++);
+    t.T_kf_w.insert(t.T_kf_w.end(), kf->T_f_w_.p, kf->T_f_w_.p + 7);
+    for (const Feature* ftr : kf->fts_) if (ftr->point != nullptr) t.kf_ftr_point.push_back(point_index(ftr->point));
+    t.kf_ftr_offset.push_back((int32_t)t.kf_ftr_point.size());
+    for (size_t j = 0; j < 5; ++j) {
+      const Feature* kp = j < kf->key_pts_.size() ? kf->key_pts_[j] : nullptr;
+      t.kf_key_point.push_back(kp && kp->point ? point_index(kp->point) : -1);
+    }
+  }
+  for (auto& c : map.point_candidates_.candidates_) t.cand_point.push_back(point_index(c.first));
+  for (size_t p = 0; p < points.size(); ++p) {
+    const Point* pt = points[p];
+    for (int j = 0; j < 3; ++j) t.pt_pos.push_back(pt->pos_[j]);
+    t.pt_type.push_back((int)pt->type_); t.pt_n_failed.push_back(pt->n_failed_reproj_); t.pt_n_succeeded.push_back(pt->n_succeeded_reproj_);
+    for (const Feature* o : pt->obs_) {
+      auto fi = index_of_frame.find(o->frame->id_);
+      if (fi == index_of_frame.end()) continue;
+      t.obs_kf.push_back(fi->second);
+      t.obs_px.push_back(o->px[0]); t.obs_px.push_back(o->px[1]);
+      for (int j = 0; j < 3; ++j) t.obs_f.push_back(o->f[j]);
+      t.obs_level.push_back(o->level);
+      t.obs_edgelet.push_back(o->type == Feature::EDGELET ? 1 : 0);
+      t.obs_grad.push_back(o->grad[0]); t.obs_grad.push_back(o->grad[1]);
+    }
+    t.pt_obs_offset.push_back((int32_t)t.obs_kf.size());
+  }
+  return t;
+}
 }  // namespace initialization
 
 }  // namespace svo

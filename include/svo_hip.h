@@ -1208,7 +1208,8 @@ int svo_hip_seed_batch_create_detected(svo_hip_ctx* ctx, const svo_hip_pyramid* 
  * 30 x 30 window, maxLevel 4, 30 iterations, eps 0.001, OPTFLOW_USE_INITIAL_FLOW -- erases the lost ones for good, forms the
  * bearings f_cur and the disparities, and returns NO_KEYFRAME until their median (vk::getMedian: the order statistic of rank
  * n / 2) reaches Config::initMinDisparity().  A handle holds that state for n_cameras cameras of one image size; any subset
- * of them is tracked by one call.  computeFundamental / computeHomography (:228-329) stay on the host.
+ * of them is tracked by one call.  computeFundamental (:260-329) and the rest of addSecondFrame (:77-138) follow below
+ * (svo_hip_klt_two_view); computeHomography (:232-258), the planar path the reference has switched off, is not built.
  *
  * OpenCV is not part of the reference's tree: PARITY UNPINNED.  The algorithm is written down in tests/klt_reference.py
  * (Gaussian pyramid by cv::pyrDown's integer arithmetic, levels while both sides exceed the window; Scharr derivatives;
@@ -1258,6 +1259,74 @@ int svo_hip_klt_download(svo_hip_klt* klt, int camera, int32_t* n, float* px_ref
 /* a level of the camera's Gaussian pyramid (tests): the previous image's (current = 0, levels 0..) or the last tracked
  * image's (current = 1, levels 1..: its level 0 stays in the caller's pyramid) */
 int svo_hip_klt_download_level(svo_hip_klt* klt, int camera, int current, int level, uint8_t* out);
+
+/* ---- the bootstrap on the device: pose and first map points from the KLT lists -----------------------------------------
+ * The rest of KltHomographyInit::addSecondFrame (S/initialization.cpp:77-138) on the lists a svo_hip_klt handle holds:
+ * computeFundamental (:260-329) -- cv::findFundamentalMat(FM_RANSAC) and cv::recoverPose restated, then the reference's own
+ * vk::computeInliers and Quaterniond(R) --, the init_min_inliers gate (:85), the scene-depth median over ALL xyz_in_cur and
+ * the map scale (:92-105), the second frame's pose (:108-115), and for every inlier the gate of :123 and its position in the
+ * world (:125).  The Point and Feature objects of :126-136 are the host's.
+ *
+ * OpenCV is not part of the reference's tree: PARITY UNPINNED.  The algorithm is written down in tests/two_view_reference.py
+ * and the device computes that model's numbers bit for bit.  A fixed number of hypotheses replaces OpenCV's adaptive count;
+ * hypothesis h samples 8 distinct correspondences as a function of (seed, h, draw, n) alone, solves the 8-point system on
+ * Hartley-normalised coordinates by Gaussian elimination with complete pivoting, and is scored by the count of
+ * correspondences whose larger squared epipolar distance is <= (reproj_thresh / errorMultiplier2)^2; the winner is the
+ * highest count, the lowest index among equals.  Its four pose candidates are ranked by the number of masked
+ * correspondences with both ray parameters of vk::triangulateFeatureNonLin positive.  DESIGN.md section 7 lists the
+ * departures. */
+enum {
+  SVO_HIP_TWO_VIEW_OK = 0,            /* pose, scale and points are valid */
+  SVO_HIP_TWO_VIEW_TOO_FEW = 1,       /* fewer than 8 correspondences */
+  SVO_HIP_TWO_VIEW_NO_MODEL = 2,      /* every hypothesis degenerate */
+  SVO_HIP_TWO_VIEW_CHEIRALITY = 3,    /* the gate of :305: fewer than half of the correspondences in front of both cameras */
+  SVO_HIP_TWO_VIEW_FEW_INLIERS = 4    /* the gate of :85 */
+};
+#define SVO_HIP_TWO_VIEW_MAX_HYPOTHESES 4096
+typedef struct {
+  double reproj_thresh;               /* 2.0: Config::poseOptimThresh() (:81) */
+  int min_inliers;                    /* 40: Config::initMinInliers() (:85) */
+  double map_scale;                   /* 1.0: Config::mapScale() (:105) */
+  int n_hypotheses;                   /* 1024; 1..SVO_HIP_TWO_VIEW_MAX_HYPOTHESES */
+  unsigned long long seed;            /* 0 */
+} svo_hip_two_view_params;
+typedef struct {
+  int status, n_in;
+  int hypothesis, hypothesis_count;   /* the winner and its inlier count (-1, -1 before a model) */
+  int candidate, candidate_count;     /* the chosen one of (R1, u3), (R1, -u3), (R2, u3), (R2, -u3) and its cheirality count */
+  int n_inliers, n_points;            /* 0 unless status is OK: a failure leaves no inliers and no points (the reference
+                                       * leaves the previous attempt's inliers_ in place at :307 -- not kept) */
+  double depth_median, scale;         /* rank n_in / 2 of all xyz_in_cur.z (NaN if one of them is NaN); map_scale / median */
+  double T_cur_from_ref[7];           /* T_f_w[7] layout; NaN before the cheirality gate is passed */
+  double T_cur_w[7];                  /* the second frame's pose with the rescaled translation (:108-115); NaN unless OK */
+} svo_hip_two_view_result;
+int svo_hip_two_view_default_params(svo_hip_two_view_params* params);
+/* computeFundamental and addSecondFrame :85-125 for the n listed cameras in one set of launches and one synchronisation.
+ * cams[i] gives camera cameras[i] its errorMultiplier2 (|fx|) and its image size for the gate of :123; T_ref_w[i][7] is the
+ * first frame's pose (NULL: identity for every camera, the reference's first frame); params may be NULL.  The KLT lists are
+ * read, never written.  The handle's two-view memory is taken by its first call; later calls make no allocator call.  A
+ * status other than OK is a result, not an error.  Before anything is enqueued: SVO_HIP_ERR_INVALID for a camera out of
+ * range or listed twice, a camera model without size or focal length, reproj_thresh or map_scale not positive and finite,
+ * min_inliers < 0, n_hypotheses outside 1..4096; SVO_HIP_ERR_STATE for a camera without a reference, or without a
+ * svo_hip_klt_track / svo_hip_klt_set_lists since its reference was set (f_cur undefined).  A refused call leaves lists and
+ * earlier results as they were. */
+int svo_hip_klt_two_view(svo_hip_klt* klt, int n, const int* cameras, const svo_hip_camera* cams /*[n]*/,
+                         const double* T_ref_w /*[n][7] or NULL*/, const svo_hip_two_view_params* params,
+                         svo_hip_two_view_result* results /*[n]*/);
+/* what the camera's last svo_hip_klt_two_view left on the device (xyz_in_cur_ and inliers_ of :82, the points of :119-125);
+ * every output may be NULL.  status: the call's status again (it says which outputs are written); n: the correspondences; xyz_in_cur[n][3] (written for status OK and FEW_INLIERS only);
+ * mask[n]: the winner's inlier flags (zeros before a model); inliers[n_inliers]; point_index[n_points]: the feature's position
+ * in the camera's lists, in inlier order, with point_pos[n_points][3]; hypothesis_count[n_hypotheses]: every hypothesis' inlier
+ * count, -1 for a degenerate sample (n_hypotheses = 0 for TOO_FEW).  SVO_HIP_ERR_STATE: no two-view call since the camera's
+ * lists were last set.  Synchronises. */
+int svo_hip_klt_download_two_view(svo_hip_klt* klt, int camera, int32_t* status, int32_t* n, double* xyz_in_cur, uint8_t* mask, int32_t* n_inliers,
+                                  int32_t* inliers, int32_t* n_points, int32_t* point_index, double* point_pos,
+                                  int32_t* n_hypotheses, int32_t* hypothesis_count);
+/* the camera's lists from the host, for callers with a matcher of their own: px_ref[n][2], px_cur[n][2], f_ref[n][3],
+ * f_cur[n][3] replace what trackKlt left (:203-225), index becomes 0..n-1, the disparities are undefined until the next
+ * svo_hip_klt_track.  The camera must have a reference (SVO_HIP_ERR_STATE) and n <= max_features.  Synchronises. */
+int svo_hip_klt_set_lists(svo_hip_klt* klt, int camera, int n, const float* px_ref, const float* px_cur, const double* f_ref,
+                          const double* f_cur);
 
 #ifdef __cplusplus
 }
