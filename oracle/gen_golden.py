@@ -526,6 +526,45 @@ def gen_reproject_paths_ref():
     np.savez_compressed(os.path.join(OUT, "reproject_paths_ref.npz"), **out)
 
 
+def gen_align_paths_ref():
+    """feature_alignment::align2D / align1D and Matcher::findMatchDirect executed by the reference's own compiled code on the constructed
+    families of tests/align_families.py (borders at entry and later, every exit class, rollbacks, degenerate Hessians, full-contrast
+    templates; frame tests, det(A) on both sides of every search-level threshold under Config::nPyrLevels() of 1, 3 and 5, shrinking and
+    clipped warps).  Results only: the inputs are regenerated from the family code and guarded by CRCs.  Left out, by name: the cases
+    af.ORACLE_ONLY (a NaN warp: the reference aligns whatever patch the Matcher held before) and af.DEVICE_CONTRACT (keyframe slots out
+    of range: the reference has no slots)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import align_families as af
+    out = {}
+    for kind in ("2d", "1d"):
+        cases = [c for c in af.align_cases(kind) if c.name not in af.ORACLE_ONLY]
+        ok, px, hinv = np.zeros(len(cases), np.uint8), np.zeros((len(cases), 2)), np.zeros(len(cases))
+        for i, c in enumerate(cases):
+            if kind == "2d":
+                ok[i], px[i] = refpy.align2d(c.img, c.pwb, c.ref_patch, c.n_iter, c.px)
+            else:
+                ok[i], px[i], hinv[i] = refpy.align1d(c.img, c.dir, c.pwb, c.ref_patch, c.n_iter, c.px)
+        out["align%s_names" % kind] = np.array([c.name for c in cases])
+        out["align%s_crc" % kind] = np.array(af.align_input_crc(cases), dtype=np.uint64)
+        out["align%s_ok" % kind], out["align%s_px" % kind] = ok, px
+        if kind == "1d":
+            out["align1d_hinv"] = hinv
+        print("align_paths_ref align" + kind, len(cases), "converged", int(ok.sum()))
+    cam, _, kf_poses, kf_pyr = af.md_scene()
+    for g in af.md_groups():
+        items = [it for it in g.items if it.name not in af.ORACLE_ONLY + af.DEVICE_CONTRACT]
+        ok, px, sl = np.zeros(len(items), np.uint8), np.zeros((len(items), 2)), np.zeros(len(items), np.int32)
+        for i, it in enumerate(items):
+            r = refpy.find_match_direct(cam, kf_pyr[it.slot], g.cur_pyr, kf_poses[it.slot], g.T_cur_w, it.px_ref, it.f_ref, it.level, it.pt, it.px_cur,
+                                        edgelet=it.edgelet, grad=it.grad, n_pyr_levels=g.n_pyr_levels)
+            ok[i], px[i], sl[i] = r["ok"], r["px_cur"], r["search_level"]
+        out[g.name + "_names"] = np.array([it.name for it in items])
+        out[g.name + "_crc"] = np.array(af.md_input_crc(g), dtype=np.uint64)
+        out[g.name + "_ok"], out[g.name + "_px"], out[g.name + "_sl"] = ok, px, sl
+        print("align_paths_ref", g.name, len(items), "matched", int(ok.sum()), "levels", sorted(set(sl.tolist())))
+    np.savez_compressed(os.path.join(OUT, "align_paths_ref.npz"), **out)
+
+
 CAMERA_REF_CASES = (
     # name, width, height, fx, fy, cx, cy, (k1, k2, p1, p2, k3)
     ("pinhole_vga", 640, 480, 500.0, 500.0, 319.5, 239.5, (0.0, 0.0, 0.0, 0.0, 0.0)),
@@ -583,6 +622,10 @@ def main():
         assert refpy.available(), "build oracle/_ref first: make -C oracle ref"
         gen_sia_nlls_ref()
         return
+    if "--align-paths-only" in sys.argv:
+        assert refpy.available(), "build oracle/_ref first: make -C oracle ref"
+        gen_align_paths_ref()
+        return
     if "--map-only" in sys.argv:
         assert refpy.available(), "build oracle/_ref first: make -C oracle ref"
         gen_reproject_map_ref()
@@ -602,6 +645,7 @@ def main():
     gen_reproject_ref()
     gen_reproject_map_ref()
     gen_reproject_paths_ref()
+    gen_align_paths_ref()
     gen_camera_ref()
     for fn in sorted(os.listdir(OUT)):
         print(fn, os.path.getsize(os.path.join(OUT, fn)))

@@ -71,6 +71,10 @@ extern "C" void ref_set_distortion(const double* d5) { for (int i = 0; i < 5; ++
 static thread_local int g_reproj_max_n_kfs = 0;
 extern "C" void ref_set_reproj_max_n_kfs(int n) { g_reproj_max_n_kfs = n; }
 
+// Config::nPyrLevels() during the next ref_find_match_direct calls of this thread (0: the reference's own default, 3)
+static thread_local int g_match_n_pyr_levels = 0;
+extern "C" void ref_set_match_n_pyr_levels(int n) { g_match_n_pyr_levels = n; }
+
 #ifdef REF_RUN_TRACKER_BINDING
 // what the last ref_reproject_map_keys call of this build (the frame-tracker binding in place of the Reprojector) left
 static int g_tracker_ok = 0, g_tracker_pose_optimised = 0;
@@ -291,7 +295,10 @@ int ref_find_match_direct(int width, int height, double fx, double fy, double cx
   std::memset(m->patch_, 0, sizeof(m->patch_));
   m->search_level_ = -1;
   Eigen::Vector2d p(px_cur[0], px_cur[1]);
+  const size_t n_pyr_before = svo::Config::nPyrLevels();
+  if (g_match_n_pyr_levels > 0) svo::Config::nPyrLevels() = (size_t)g_match_n_pyr_levels;
   const bool ok = m->findMatchDirect(*ftr->point, *cur.f, p);
+  svo::Config::nPyrLevels() = n_pyr_before;
   px_cur[0] = p[0]; px_cur[1] = p[1];
   *search_level = m->search_level_;
   delete m;

@@ -248,7 +248,14 @@ def find_epipolar_match_direct(cam, ref_pyr, cur_pyr, T_ref_w, T_cur_w, px_ref, 
 
 
 def find_match_direct(cam, ref_pyr, cur_pyr, T_ref_w, T_cur_w, px_ref, f_ref, level_ref, pt_pos, px_cur, edgelet=False,
-                      grad=(1.0, 0.0)):
+                      grad=(1.0, 0.0), n_pyr_levels=None):
+    """n_pyr_levels: Config::nPyrLevels() for this call (None: the reference's 3)"""
+    if n_pyr_levels is not None:
+        lib().ref_set_match_n_pyr_levels(C.c_int(int(n_pyr_levels)))
+        try:
+            return find_match_direct(cam, ref_pyr, cur_pyr, T_ref_w, T_cur_w, px_ref, f_ref, level_ref, pt_pos, px_cur, edgelet, grad)
+        finally:
+            lib().ref_set_match_n_pyr_levels(C.c_int(0))
     rp, cp = orc.pyr_ptrs(ref_pyr), orc.pyr_ptrs(cur_pyr)
     Tr, Tc, p, ff, pp, g = f64(T_ref_w), f64(T_cur_w), f64(px_ref), f64(f_ref), f64(pt_pos), f64(grad)
     pc = f64(px_cur).copy()

@@ -1087,7 +1087,10 @@ int svo_orc_warp_affine(const double A[4], const uint8_t* img_ref, int cols, int
       ppy *= (1 << search_level);
       const float qx = (a00 * ppx + a01 * ppy) + prx;
       const float qy = (a10 * ppx + a11 * ppy) + pry;
-      if (qx < 0 || qy < 0 || qx >= cols - 1 || qy >= rows - 1)
+      /* A NaN coordinate (an infinite inverse of an exactly singular A: inf * 0, inf - inf) passes the reference's test
+       * `qx < 0 || qy < 0 || qx >= cols-1 || qy >= rows-1` and is interpolated -- a read outside the image.  Here, as on
+       * the device, such a sample is 0: the test is written so that a NaN fails it. */
+      if (!(qx >= 0 && qy >= 0 && qx < cols - 1 && qy < rows - 1))
         *pp = 0;
       else
         *pp = (uint8_t)svo_orc_interpolate_8u(img_ref, cols, qx, qy);
